@@ -3,13 +3,18 @@
 
 The HEADLINE (`value`, `dtype: "f32_split"`) is measured on fp32 tensors end to end (train_acr.py:137, autocast(enabled=False))
 with the model's matrix products evaluated as six bf16-MFMA terms of a three-way operand split (24 mantissa bits per operand,
-fp32 accumulate: ACR(..., math="f32_split"); every fp32 parity test runs under it at the fp32 tolerances).  The
-same invocation then runs the exact-fp32-MFMA arithmetic (sub-record `"f32"`, the previous rounds' headline) and the bf16
-training mode of this build (bf16 tensors + bf16 MFMA, fp32 master weights / accumulate / softmax / loss; parity pinned by
-tests/test_model_gpu.py::test_bf16_train_step_448; sub-record `"bf16"` -- never `value`).  ACR_BENCH_HEADLINE=f32 puts the
-exact arithmetic back in front.
+fp32 accumulate: ACR(..., math="f32_split"); every fp32 parity test runs under it at the fp32 tolerances).  A plain
+run does only what that figure needs: set-up, W warm-up steps, K timed steps, the result line.  With --full the same invocation
+then also runs the exact-fp32-MFMA arithmetic (sub-record `"f32"`, the previous rounds' headline) and the bf16 training mode of
+this build (bf16 tensors + bf16 MFMA, fp32 master weights / accumulate / softmax / loss; parity pinned by
+tests/test_model_gpu.py::test_bf16_train_step_448; sub-record `"bf16"` -- never `value`), the per-kernel roofline probes, the
+CAM-generation record, the CPU baseline and (N > 1) the exchange diagnostics.  ACR_BENCH_HEADLINE=f32 puts the exact arithmetic
+back in front.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+        --dump-outputs DIR: after the timed steps, what the last timed step handed its caller (loss terms, a seeded sample of
+        the updated parameters and of the step's gradients) as DIR/<name>.npy -- inputs are seeded, so two builds compare
+        output for output.
         N = 1: runs in this process.  N > 1 without WORLD_SIZE in the environment: this process touches no GPU, starts
         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...`
         as a CHILD, relays its one JSON line and exits with its return code.
@@ -62,9 +67,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=16, help="images per GPU (BASELINE configs[1]: 16)")
     ap.add_argument("--size", type=int, default=448)
     ap.add_argument("--dtype", choices=["both", "f32", "f32_split", "bf16"], default=os.environ.get("ACR_BENCH_DTYPE", "both"),
-                    help="both (default): three runs from one invocation -- f32_split (fp32 tensors, split products on the bf16 MFMA) is the "
-                         "headline `value`, the exact-fp32 run rides along as the sub-record 'f32' and the bf16 training mode as 'bf16' "
+                    help="both (default): f32_split (fp32 tensors, split products on the bf16 MFMA) is the headline `value`; with --full "
+                         "the exact-fp32 run rides along as the sub-record 'f32' and the bf16 training mode as 'bf16' "
                          "(ACR_BENCH_HEADLINE=f32 swaps the two fp32 arithmetics); f32 / f32_split / bf16: that run only (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the other precisions, roofline probes, CAM-generation record, CPU baseline and N > 1 exchange diagnostics "
+                         "(a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss terms, seeded samples of parameters and gradients) as DIR/<name>.npy")
     ap.add_argument("--classes", type=int, default=20)
     ap.add_argument("--alpha", type=int, default=125)
     ap.add_argument("--amp", choices=["master", "autocast"], default="master",
@@ -544,8 +554,36 @@ def log(msg):
 _T0 = time.time()
 
 
-def run_mode(args, dtype, world, rank, dev):
-    """Build the model in `dtype`, do W untimed + K timed steps (barrier + synchronize on both sides, max over ranks)."""
+DUMP_SAMPLE = 1 << 20                # positions sampled from the parameters / gradients by --dump-outputs (4 MB each as float32)
+
+
+def dump_outputs(out_dir, model, terms):
+    """--dump-outputs: what a caller of train_step holds after the LAST timed step, as float32 / float64 .npy files: the loss and
+    its terms (<term>.npy), the parameters that step's update left (params_sample.npy) and the gradients it computed
+    (grads_sample.npy).  The two model-sized arrays are a fixed sample: DUMP_SAMPLE positions, drawn from a seeded generator, of
+    model.parameters() concatenated in order (all of them when there are fewer)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in terms.items():
+        np.save(os.path.join(out_dir, "%s.npy" % k), np.array([float(v.detach())], np.float64))
+    params = list(model.parameters())
+    n = sum(p.numel() for p in params)
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator(device="cpu").manual_seed(1234)).sort().values
+    idx = idx.to(params[0].device)
+    for name, ts in (("params_sample", [p.detach() for p in params]),
+                     ("grads_sample", [p.grad.detach() if p.grad is not None else torch.zeros_like(p) for p in params])):
+        flat = torch.cat([t.reshape(-1).float() for t in ts])
+        np.save(os.path.join(out_dir, name + ".npy"), flat[idx].cpu().numpy().astype(np.float32))
+        del flat
+    log("outputs of the last timed step written to %s" % out_dir)
+
+
+def run_mode(args, dtype, world, rank, dev, dump_dir=None):
+    """Build the model in `dtype`, do W untimed + K timed steps (barrier + synchronize on both sides, max over ranks); with
+    `dump_dir`, write what the last timed step computed there (dump_outputs)."""
     from acr_wsss_amd.DPT.ACR import ACR
     from acr_wsss_amd.train import MasterWeights, PolyOptimizer, train_step
     from acr_wsss_amd.dp import GradSync, broadcast_parameters
@@ -604,6 +642,8 @@ def run_mode(args, dtype, world, rank, dev):
     ops.KERNEL_TIMER = None
     live = {k: sum(v) / len(v) for k, v in timer.collect().items()} if timer is not None else {}
     log("%s: timed %d steps in %.3f s" % (dtype, args.steps, elapsed))
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, model, terms)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -614,7 +654,7 @@ def run_mode(args, dtype, world, rank, dev):
     # them, so that the line itself says how much of a step the exchange exposed (`exposed_ms` = ms_step - ms_compute_only) and
     # what the all-reduce costs when nothing hides it -- the first real 8-GPU run is then a diagnosis, not a single number.
     diag = None
-    if sync is not None:
+    if sync is not None and args.full:
         def span(fn, n):
             if world > 1:
                 dist.barrier()
@@ -705,11 +745,14 @@ def main():
     if args.infer_only:
         print(json.dumps({"infer": infer_record(args, dev, not args.no_cpu_baseline)}), flush=True)
         return
+    if not args.full:                                      # a plain run: the headline's set-up, warm-up and timed steps, nothing else
+        modes = modes[:1]
+        args.no_roofline = args.no_infer = args.no_cpu_baseline = True
 
-    runs = {m: run_mode(args, m, world, rank, dev) for m in modes}
+    runs = {m: run_mode(args, m, world, rank, dev, args.dump_outputs if m == modes[0] else None) for m in modes}
     lives = {m: runs[m].pop("_live_ms", {}) for m in modes}
     syncs = {m: runs[m].pop("_sync", None) for m in modes}
-    dist_info = dist_record(args, world, rank, local, dev, {"sync": {m: syncs[m] for m in modes}}) if world > 1 else None
+    dist_info = dist_record(args, world, rank, local, dev, {"sync": {m: syncs[m] for m in modes}}) if (world > 1 and args.full) else None
     if rank == 0:
         head = runs[modes[0]]                              # fp32 unless a single dtype was asked for
         head_live = lives[modes[0]]

@@ -1,6 +1,6 @@
 """Dense-CRF stage, CPU side: the numpy restatement of the permutohedral lattice against fixtures generated
 from the reference's own C++ (tests/golden/crf_lattice_*.npz, make_crf_golden.py) -- bit for bit -- and, where
-oracle/_ref/libpermuto_ref.so was built, against that library live on fresh inputs; sanity of the mean-field restatement (its
+oracle/_ref/libpermuto_ref.so was built, against that library live; sanity of the mean-field restatement (its
 parity is unpinned: pydensecrf is not available); the product has no CPU path."""
 import os
 
@@ -35,18 +35,21 @@ def test_oracle_lattice_matches_reference_fixtures(tag):
 
 
 def test_oracle_lattice_matches_compiled_reference_live():
+    """The reference's lattice on seeded inputs (make_crf_golden.live_cases): its tables and outputs as stored in
+    crf_lattice_live.npz and, where oracle/_ref/libpermuto_ref.so was built, the library itself run live on the same inputs."""
+    from make_crf_golden import live_cases
+    g = np.load(os.path.join(GOLD, "crf_lattice_live.npz"))
     lib = C.load_ref()
-    if lib is None:
-        pytest.skip("oracle/_ref not built here (needs /root/reference: make -C oracle)")
-    rng = np.random.default_rng(7)
-    for (h, w, k, sxy, srgb) in ((30, 45, 3, 80, 13), (25, 25, 1, 8, 5), (50, 20, 6, 40, 3)):
-        img = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
-        img[h // 2:] = img[h // 2, 0]                                          # flat half: many pixels per lattice point
-        vals = rng.standard_normal((h * w, k)).astype(np.float32)
-        for feat in (C.bilateral_features(img, sxy, srgb), C.spatial_features(h, w, 3), C.spatial_features(h, w, 0.7)):
+    for i, (img, vals, feats) in enumerate(live_cases()):
+        assert np.array_equal(img, g["c%d_img" % i]) and np.array_equal(vals, g["c%d_vals" % i])
+        for j, feat in enumerate(feats):
+            key = "c%d_f%d_" % (i, j)
+            off, wts, m, out = g[key + "offsets"], g[key + "weights"], int(g[key + "M"]), g[key + "filter"]
+            if lib is not None:
+                off2, wts2, m2 = C.ref_lattice_tables(lib, feat)
+                out2, _ = C.ref_lattice_filter(lib, feat, vals)
+                assert m2 == m and np.array_equal(off2, off) and np.array_equal(wts2, wts) and np.array_equal(out2, out)
             lat = C.lattice_init(feat)
-            off, wts, m = C.ref_lattice_tables(lib, feat)
-            out, _ = C.ref_lattice_filter(lib, feat, vals)
             assert lat["M"] == m and np.array_equal(lat["offsets"], off) and np.array_equal(lat["weights"], wts)
             assert np.array_equal(C.lattice_compute(lat, vals), out)
 

@@ -216,10 +216,46 @@ def test_rccl_one_rank_group_runs_the_exchange():
     assert diff.max() <= 2e-3 * ref.abs().max() and diff.mean() <= 1e-5 * ref.abs().max(), (diff.max(), diff.mean())
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the headline's warm-up and timed steps and the result line, nothing else -- no other
+    precision, roofline, CAM-generation or CPU-baseline record.  --dump-outputs writes what the last timed step computed, and two
+    runs with the same arguments write the same arrays: seeded inputs, and at the bench geometry (448^2, batch 16) a step is
+    bit-reproducible from process to process."""
+    import json
+    import subprocess
+    import numpy as np
+    recs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert rec["dtype"] == "f32_split" and rec["unit"] == "img/s" and rec["higher_is_better"] is True and rec["steps"] == 3
+    assert abs(rec["value"] - 16 * 1e3 / rec["ms_per_step"]) <= 0.02 * rec["value"]
+    for k in ("f32", "bf16", "roofline", "infer", "cpu_baseline", "dist"):
+        assert k not in rec, k
+    assert sorted(rec["loss_step0"]) == ["f32_split"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "cls_align.npy", "aff_align.npy", "params_sample.npy", "grads_sample.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == pytest.approx(rec["loss"], rel=1e-4, abs=1e-5)
+    assert np.abs(np.load(tmp_path / "a" / "grads_sample.npy")).max() > 0
+
+
 def test_bench_two_ranks_gloo_rehearsal(tmp_path):
     """bench.py's N > 1 path executed end to end THROUGH ITS SELF-LAUNCH: `python bench.py --gpus 2` with no WORLD_SIZE in the
-    environment (the driver's command shape) must start the two ranks itself (child torch.distributed.run, one process per
-    rank), relay ONE JSON line and return the child's code.  The ranks share cuda:0 with gloo collectives (`--backend gloo`:
+    environment (the driver's command shape, here with --full) must start the two ranks itself (child torch.distributed.run, one
+    process per rank), relay ONE JSON line and return the child's code.  The ranks share cuda:0 with gloo collectives (`--backend gloo`:
     RCCL needs one GPU per rank and the test box has one).  Checks the contract fields: whole-job img/s over both ranks,
     weak scaling, the split-product fp32 headline with the exact-fp32 and bf16 sub-records, `roofline` on the line (rank 0's
     probe; the CPU baseline is switched off here for time, its N > 1 placement is the same code path as N = 1) and the `dist`
@@ -228,7 +264,7 @@ def test_bench_two_ranks_gloo_rehearsal(tmp_path):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "2",
            "--batch", "2", "--size", "224", "--backend", "gloo", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]

@@ -484,6 +484,38 @@ def test_bench_self_launch_builds_the_drivers_command(monkeypatch, capsys):
     assert bench.self_launch(args) == 3
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every loss term as a float64 .npy, the parameters and gradients as float32 values at DUMP_SAMPLE
+    fixed (seeded, sorted) positions of model.parameters() concatenated in order -- all of them when there are fewer; a parameter
+    without a gradient counts as zeros.  Plain run: --full is off, nothing is dumped unless asked."""
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 4 and args.warmup == 2
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(64, 300), torch.nn.Linear(300, 10), torch.nn.Linear(3, 3))
+    x = torch.randn(5, 64)
+    loss = model[1](model[0](x)).square().mean()
+    loss.backward()                                             # model[2] gets no gradient
+    terms = {"loss": loss, "cls_align": loss * 0.5}
+    flat_p = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in model.parameters()])
+    bench.dump_outputs(str(tmp_path / "all"), model, terms)
+    assert sorted(os.listdir(tmp_path / "all")) == ["cls_align.npy", "grads_sample.npy", "loss.npy", "params_sample.npy"]
+    l = np.load(tmp_path / "all" / "loss.npy")
+    assert l.dtype == np.float64 and l.shape == (1,) and l[0] == float(loss.detach())
+    assert np.array_equal(np.load(tmp_path / "all" / "params_sample.npy"), flat_p.numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "grads_sample.npy"), flat_g.numpy())
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), model, terms)
+    ps, gs = np.load(tmp_path / "s1" / "params_sample.npy"), np.load(tmp_path / "s1" / "grads_sample.npy")
+    assert ps.dtype == np.float32 and ps.shape == gs.shape == (1000,)
+    assert np.array_equal(ps, np.load(tmp_path / "s2" / "params_sample.npy")) and np.array_equal(gs, np.load(tmp_path / "s2" / "grads_sample.npy"))
+    assert np.isin(ps, flat_p.numpy()).all() and np.isin(gs, flat_g.numpy()).all()
+
+
 @pytest.mark.parametrize("backbone,layout", [("vitb_hybrid", "state_dict_layout.json"), ("deit_distilled", "state_dict_layout_distil.json"),
                                              ("vitb", "state_dict_layout_vitb.json"), ("deit", "state_dict_layout_deit.json")])
 def test_state_dict_layout_equals_the_references(backbone, layout):
