@@ -175,11 +175,10 @@ SIGNATURES = {
                                       c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
 }
 
-# acr_option (include/acr_hip.h): kernel-variant selectors of the library's explicit option table, name -> code.  Set through
-# set_option() by tests and lab scripts only; round 6 removed the environment variables that used to feed them at load time
-# (every A/B they served is recorded and settled) -- the library itself never reads the environment.
-OPTIONS = {"gemm_variant": 0, "gemm_nowide": 1, "gemm_regstage": 2, "wgrad_variant": 3, "wgrad_waves": 4, "dq_variant": 5,
-           "gemm_f32_regstage": 6, "attn_delta_1head": 7, "gemm_f32_notail": 9, "attn_f32_nosplittail": 10, "gemm_x3_inkernel": 11, "gn_plan": 12}
+# acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through
+# set_option() by a test only (it cross-checks two delta kernels that both ship); every other A/B the table once served is settled
+# and retired -- the library itself never reads the environment.
+OPTIONS = {"attn_delta_1head": 7}
 
 _lib = None
 

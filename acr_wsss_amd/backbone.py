@@ -68,24 +68,24 @@ class StdConv2dSame(nn.Conv2d):
 
     def forward(self, x):
         w_hat = self._w_hat if self._w_hat is not None else self.standardized_weight()
-        if self.hip_3x3 and self.stride[0] == 2 and self.kernel_size[0] in (3, 7) and ops.conv_s2_fusable(x, w_hat, 2, self.acr_math):
+        if self.stride[0] == 2 and self.kernel_size[0] in (3, 7) and ops.conv_s2_fusable(x, w_hat, 2, self.acr_math):
             # the stem's 7x7 and the two stride-2 3x3 convolutions under split products: space-to-depth + tap-table implicit GEMM
             # (SAME padding = the taps' validity masks; no padded copy, no library kernel, no layout transposes)
             return ops.conv_s2(x, w_hat, self._w_imgs)
         if self.dynamic_pad:
             x = pad_same(x, self.kernel_size[0], self.stride[0])
-        if self.hip_1x1 and self.hip_1x1_strided and self.kernel_size == (1, 1) and self.stride[0] == 2 and x.is_cuda:
+        if self.kernel_size == (1, 1) and self.stride[0] == 2 and x.is_cuda:
             # the two stride-2 1x1 convolutions (the shortcuts of stages 1 and 2; SAME padding is empty for a 1x1 kernel:
             # y[i][j] = W x[2i][2j]): subsample first, then the same NCHW GEMM kernels as every other 1x1 -- the library ran
             # them as layout transposes + a Tensile GEMM; autograd's slice backward scatters the input gradient back
             xs = ops.subsample2(x)
             if ops.conv1x1_fusable(xs, w_hat, 1):
                 return ops.conv1x1(xs, w_hat, self._w_hat_t, self.acr_math, self._w_imgs)
-        if self.hip_1x1 and ops.conv1x1_fusable(x, w_hat, self.stride[0]):
+        if ops.conv1x1_fusable(x, w_hat, self.stride[0]):
             return ops.conv1x1(x, w_hat, self._w_hat_t, self.acr_math, self._w_imgs)   # NCHW 1x1 conv = per-sample MFMA GEMM, no layout transposes
-        if self.hip_3x3 and not self.dynamic_pad and ops.conv3x3_fusable(x, w_hat, self.stride[0], self.acr_math):
+        if not self.dynamic_pad and ops.conv3x3_fusable(x, w_hat, self.stride[0], self.acr_math):
             return ops.conv3x3(x, w_hat, self._w_imgs)                     # split-product implicit GEMM, no layout transposes
-        if (self.hip_3x3 and self.pad_narrow and not self.dynamic_pad and x.dim() == 4 and 4 <= x.shape[3] < 16 and x.shape[3] % 4 == 0
+        if (not self.dynamic_pad and x.dim() == 4 and 4 <= x.shape[3] < 16 and x.shape[3] % 4 == 0
                 and self.kernel_size == (3, 3)):
             # maps narrower than the kernels' 16-pixel rows (CAM generation at scale 0.5: 12 x 12 in the last stage): zero columns on
             # the right ARE the SAME padding of the last real column, so the convolution of the widened map, cut back, is the result
@@ -98,14 +98,10 @@ class StdConv2dSame(nn.Conv2d):
         """(conv(x), x_skip): x_skip is what a parallel branch (the shortcut) should read -- on the HIP 1x1 path its
         gradient is then added inside the input-gradient GEMM."""
         w_hat = self._w_hat if self._w_hat is not None else self.standardized_weight()
-        if self.hip_1x1 and x.requires_grad and ops.conv1x1_fusable(x, w_hat, self.stride[0]):
+        if x.requires_grad and ops.conv1x1_fusable(x, w_hat, self.stride[0]):
             return ops.conv1x1_skip(x, w_hat, self._w_hat_t, self.acr_math, self._w_imgs)
         return self.forward(x), x
 
-    hip_1x1 = True
-    hip_1x1_strided = True      # A/B: stride-2 1x1 convolutions as subsample + HIP GEMM
-    hip_3x3 = True      # A/B: the stem's 3x3 convolutions under f32_split on csrc/conv3x3.hip
-    pad_narrow = True      # A/B: maps of 4 / 8 / 12 columns widened to 16 instead of the library
     acr_math = 0            # _lib.MATH code of the fp32 products (set_math)
 
     _w_hat = None           # set for one forward by ResNetV2 when all weights are standardised in one fused launch
@@ -119,14 +115,13 @@ class StdConv2dSame(nn.Conv2d):
         if self.acr_math != 1 or w_hat.dtype != torch.float32 or not w_hat.is_cuda:
             return None
         co, ci, k, _ = w_hat.shape
-        if k == 1 and self.hip_1x1 and ops.CONV1X1_WIMG and ops.F32_HIP_CONV1X1 and ci % 32 == 0 and co % 32 == 0 and (
-                self.stride[0] == 1 or (self.stride[0] == 2 and self.hip_1x1_strided)):
+        if k == 1 and ci % 32 == 0 and co % 32 == 0 and self.stride[0] in (1, 2):
             return ((w_hat, 0, co, ci, ci, ci, 0, 1),               # W (co x ci)
                     (w_hat, 0, ci, co, 1, co, 0, ci))               # W^T (ci x co): the input gradient's operand
-        if k == 3 and self.stride[0] == 1 and not self.dynamic_pad and self.hip_3x3 and ops.CONV3X3_WIMG and ci % 16 == 0 and co % 16 == 0:
+        if k == 3 and self.stride[0] == 1 and not self.dynamic_pad and ops.CONV3X3_WIMG and ci % 16 == 0 and co % 16 == 0:
             return ((w_hat, 0, co, 9 * ci, 9 * ci, ci, 1, 9),        # packed w[co][t * ci + c]
                     (w_hat, 8, ci, 9 * co, 9, co, -1, 9 * ci))       # input-gradient pack w[o][c][8 - t'] as (ci x 9 co)
-        if self.stride[0] == 2 and self.hip_3x3 and ops.CONV_S2_HIP and co % 16 == 0:
+        if self.stride[0] == 2 and co % 16 == 0:
             # stride 2 (ops.ConvS2Fn), for inputs of even height and width: the forward pack, and for the 3x3s the four pixel-phase
             # packs of the input gradient (two small gather / permute copies of the weight first)
             if k == 3 and ci % 16 == 0:
@@ -159,10 +154,8 @@ class GroupNormAct(nn.GroupNorm):
 
 
 class MaxPool2dSame(nn.Module):
-    hip_pool = True
-
     def forward(self, x):
-        if self.hip_pool and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.dim() == 4 and not torch.is_autocast_enabled():
+        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.dim() == 4 and not torch.is_autocast_enabled():
             ph, pw = _same_pad(x.shape[-2], 3, 2), _same_pad(x.shape[-1], 3, 2)
             return ops.maxpool3x3s2_same(x, ph // 2, pw // 2, ph, pw)       # -inf SAME padding folded into the kernel
         return F.max_pool2d(pad_same(x, 3, 2, value=-float("inf")), 3, 2)
@@ -227,7 +220,6 @@ class ResNetV2(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
-    fused_weight_std = True
     _frozen = None                # (key, w_hats, transposed) of the last forward with frozen weights
     frozen_generation = 0         # bumped whenever that cache is rebuilt (PrefixGraph holds pointers into it)
 
@@ -291,13 +283,13 @@ class ResNetV2(nn.Module):
         """Bring the frozen standardised-weight cache up to date on the current stream (no-op while a weight wants a gradient)."""
         convs = [m for m in self.modules() if isinstance(m, StdConv2dSame)]
         w = convs[0].weight
-        if self.fused_weight_std and w.is_cuda and w.dtype == dtype and all(c.weight.dtype == dtype for c in convs) \
+        if w.is_cuda and w.dtype == dtype and all(c.weight.dtype == dtype for c in convs) \
                 and not any(c.weight.requires_grad for c in convs):
             self._standardised(convs, w)
 
     def forward(self, x, taps=None):
         convs = None
-        if self.fused_weight_std and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and not torch.is_autocast_enabled():
+        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and not torch.is_autocast_enabled():
             # one HIP launch standardises all 52 conv weights (and one more in backward) instead of ~10 tiny
             # kernels per convolution and direction
             convs = [m for m in self.modules() if isinstance(m, StdConv2dSame)]
@@ -361,25 +353,17 @@ class Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden, dim)
 
     def forward(self, x, resid=None):
-        """fc2(gelu(fc1(x))) [+ resid].  On the bf16 path fc2 runs on the hand-written GEMM with the block's residual
-        add fused into its epilogue (ties hipBLASLt on this long-K shape and saves the add kernel); fc1 and the
-        input gradients stay on hipBLASLt, which is faster on the short-K / wide-N shapes (scripts/bench_gemm.py)."""
-        # fc1: forward and input gradient on hipBLASLt (faster on this short-K / wide-N shape), weight and bias gradient
-        # on the hand-written split-M TN GEMM / column-sum kernels (scripts/bench_gemm.py)
-        if Mlp.fused and Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_fusable(x, self.fc1, self.fc2):
+        """fc2(gelu(fc1(x))) [+ resid].  bf16 and fp32 CUDA tensors run both GEMMs on the hand-written kernels with GELU / GELU'
+        and the block's residual add inside their epilogues; anything else takes the two Linears one by one."""
+        if Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_fusable(x, self.fc1, self.fc2):
             return ops.mlp(x, self.fc1, self.fc2, resid)     # GELU / GELU' inside the GEMM epilogues
-        if (Mlp.fused and Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_f32_usable(x, self.fc1, self.fc2)
+        if (Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_f32_usable(x, self.fc1, self.fc2)
                 and not torch.is_autocast_enabled()):
             return ops.mlp_f32(x, self.fc1, self.fc2, resid, self.acr_math)  # reference precision: fp32 GEMMs, same fusion
-        lib = Mlp.mlp_on_lib                                 # A/B: fc1 forward and the MLP input gradients on hipBLASLt
-        h = self.act(ops.linear_or_hip(x, self.fc1, None, Attention.hip_linear, hip_dx=not lib, hip_fwd=not lib, math=self.acr_math))
-        return ops.linear_or_hip(h, self.fc2, resid, Attention.hip_linear, hip_dx=not lib, hip_fwd=Mlp.fc2_hip_fwd, math=self.acr_math)
+        h = self.act(ops.linear_or_hip(x, self.fc1, None, Attention.hip_linear, math=self.acr_math))
+        return ops.linear_or_hip(h, self.fc2, resid, Attention.hip_linear, math=self.acr_math)
 
     acr_math = 0            # _lib.MATH code of the fp32 products (set_math)
-
-    fused = True
-    mlp_on_lib = False
-    fc2_hip_fwd = True     # A/B: fc2 forward on the hand-written GEMM (fused residual)
 
 
 class Attention(nn.Module):
@@ -415,7 +399,7 @@ class Attention(nn.Module):
         proj GEMM epilogue on the bf16 path).  ``x_image``: x is the output of ops.layer_norm_image (it exists only as that image)."""
         self._override = {}
         qkv = ops.linear_or_hip(x, self.qkv, None, self.hip_linear, math=self.acr_math, x_image=x_image)  # packed (B, T, 3*H*64): no permute copy
-        if (self.acr_math == 1 and ops.ATTN_O_IMAGE and self.hip_linear and ops.X3_IMAGES and ops.linear_f32_usable(qkv, self.proj.weight)
+        if (self.acr_math == 1 and self.hip_linear and ops.X3_IMAGES and ops.linear_f32_usable(qkv, self.proj.weight)
                 and not torch.is_autocast_enabled() and ops._f32_ok(self.proj.weight, self.proj.bias, resid)):
             # split products: o leaves the attention forward as proj's operand image (no image pass over o)
             o, self.last_pm, oimg = ops.attention_core_oimg(qkv, self.num_heads, stack, layer, self, self.acr_math)
@@ -469,19 +453,17 @@ class Block(nn.Module):
 
     def forward(self, x, stack=None, layer=0):
         math = self.attn.acr_math
-        if (Attention.hip_linear and Mlp.fused and isinstance(self.mlp.act, nn.GELU) and ops.ln_image_usable(x, self.norm1, self.attn.qkv, math, self.hip_norm)
-                and ops.ln_image_usable(x, self.norm2, self.mlp.fc1, self.mlp.acr_math, self.hip_norm) and ops.mlp_f32_usable(x, self.mlp.fc1, self.mlp.fc2)):
+        if (Attention.hip_linear and isinstance(self.mlp.act, nn.GELU) and ops.ln_image_usable(x, self.norm1, self.attn.qkv, math)
+                and ops.ln_image_usable(x, self.norm2, self.mlp.fc1, self.mlp.acr_math) and ops.mlp_f32_usable(x, self.mlp.fc1, self.mlp.fc2)):
             # split products: LN(x) is read by one Linear only, as an image -- the LayerNorm writes that image, no fp32 copy
             h, skip, hi = ops.layer_norm_image(x, self.norm1)
             x = self.attn(h, stack, layer, resid=skip, x_image=hi)
             h, skip, hi = ops.layer_norm_image(x, self.norm2)
             return ops.mlp_f32(h, self.mlp.fc1, self.mlp.fc2, skip, self.mlp.acr_math, hi)
-        h, skip = ops.layer_norm_skip(x, self.norm1, self.hip_norm)         # skip aliases x (gradient fused in LN bwd)
+        h, skip = ops.layer_norm_skip(x, self.norm1)                        # skip aliases x (gradient fused in LN bwd)
         x = self.attn(h, stack, layer, resid=skip)
-        h, skip = ops.layer_norm_skip(x, self.norm2, self.hip_norm)
+        h, skip = ops.layer_norm_skip(x, self.norm2)
         return self.mlp(h, resid=skip)
-
-    hip_norm = True         # bf16 mode: LayerNorm on acr_layernorm_*_bf16
 
 
 class PrefixGraph:
@@ -807,7 +789,7 @@ class VisionTransformer(nn.Module):
         # gradient bucket until the step's end, scripts/lab/grad_arrival_order.py)
         pos = self._resize_pos_embed(self.pos_embed, h // self.patch_size[1], w // self.patch_size[0])
         pe = self.patch_embed.proj
-        if (isinstance(self.patch_embed, HybridEmbed) and StdConv2dSame.hip_1x1 and pe.bias is not None
+        if (isinstance(self.patch_embed, HybridEmbed) and pe.bias is not None
                 and ops.conv1x1_fusable(x, pe.weight, pe.stride[0])):
             x = ops.conv1x1(x, pe.weight, None, self.acr_math)                                   # 1024 -> 768 projection on the NCHW GEMM kernels
             prefix = self.cls_token[0] if self.dist_token is None else torch.cat([self.cls_token[0], self.dist_token[0]], 0)

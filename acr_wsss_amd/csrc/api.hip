@@ -27,17 +27,14 @@ extern "C" int acr_version(void) { return ACR_ABI_VERSION; }
 extern "C" const char* acr_last_error(void) { return g_err; }
 
 // ---- explicit option table (the library's only process-wide state; see include/acr_hip.h) ------------------
-static std::atomic<int32_t> g_opt[ACR_OPT_COUNT_] = {{2}, {0}, {0}, {2}, {8}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {3}};
+static std::atomic<int32_t> g_delta_1head{0};     // ACR_OPT_ATTN_DELTA_1HEAD
 
-int32_t acr_opt(int option) { return g_opt[option].load(std::memory_order_relaxed); }
+int32_t acr_opt(int option) { return option == ACR_OPT_ATTN_DELTA_1HEAD ? g_delta_1head.load(std::memory_order_relaxed) : INT32_MIN; }
 
 extern "C" int acr_set_option(int32_t option, int32_t value) {
-    ACR_CHECK_ARG(option >= 0 && option < ACR_OPT_COUNT_, "acr_set_option: unknown option %d", option);
-    g_opt[option].store(value, std::memory_order_relaxed);
+    ACR_CHECK_ARG(option == ACR_OPT_ATTN_DELTA_1HEAD, "acr_set_option: unknown option %d", option);
+    g_delta_1head.store(value, std::memory_order_relaxed);
     return ACR_OK;
 }
 
-extern "C" int32_t acr_get_option(int32_t option) {
-    if (option < 0 || option >= ACR_OPT_COUNT_) return INT32_MIN;
-    return acr_opt(option);
-}
+extern "C" int32_t acr_get_option(int32_t option) { return acr_opt(option); }

@@ -877,11 +877,10 @@ void acr_attn_bwd_bf16(const acr_attn_desc* d, const void* q, const void* k, con
     // delta kernel: D_i = rowsum(dO o O) only; with G the dQ sweep adds rho_i/H and rewrites delta before dK/dV reads it
     hipLaunchKernelGGL((attn_delta_bf16_kernel<false>), grid, dim3(128), 0, st, g, (const bf16_t*)q, (const bf16_t*)k,
                        (const bf16_t*)o, (const bf16_t*)d_o, lse2, (const float*)nullptr, (int64_t)0, (int64_t)0, delta);
-    // 2: 2-wave sweep, 4: 4-wave sweep.  Measured at B=32, H=12, T=785: with G both take 217 us (the sweep is bound by its
-    // MFMA -> softmax -> MFMA dependency chain at 2 waves/SIMD, not by load latency); without G (CAM inference, plain
-    // attention) the 4-wave sweep is 9 % faster (127 vs 139 us) and uses 168 registers.  Default: by HAS_G.
-    const int dq_env = acr_opt(ACR_OPT_DQ_VARIANT);
-    const int dq_variant = dq_env ? dq_env : (gm ? 2 : 4);
+    // dQ sweep: 2-wave with G, 4-wave without.  Measured at B=32, H=12, T=785: with G both take 217 us (the sweep is bound by
+    // its MFMA -> softmax -> MFMA dependency chain at 2 waves/SIMD, not by load latency); without G (CAM inference, plain
+    // attention) the 4-wave sweep is 9 % faster (127 vs 139 us) and uses 168 registers.
+    const int dq_variant = gm ? 2 : 4;
     const dim3 grid4(d->B * d->H * ((d->T + 127) / 128));
 #define ACR_BWD_LAUNCH(HG)                                                                                          \
     if (dq_variant == 4)                                                                                             \

@@ -708,7 +708,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_sres_kernel(AttnGeom g, const
 // launchers (called from attn_f32.hip)
 // ---------------------------------------------------------------------------------------------
 // one leftover 32-row block per (b, h) and enough full workgroups for the split to pay (see "Split tail" above)
-static bool split_tail(int NB) { return acr_opt(ACR_OPT_ATTN_F32_NOSPLITTAIL) == 0 && (NB & 3) == 1 && NB >= 5; }
+static bool split_tail(int NB) { return (NB & 3) == 1 && NB >= 5; }
 
 void acr_attn_fwd_f32_sres(const AttnGeom& g, const float* q, const float* k, const float* v, float* o, float* lse2, float* scores,
                            float* pmean, int64_t pmean_sb, int64_t pmean_st, hipStream_t st) {

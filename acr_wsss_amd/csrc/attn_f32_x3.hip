@@ -857,7 +857,7 @@ int64_t acr_attn_x3_bwd_ws_floats(const AttnGeom& g) {                  // delta
     return (((int64_t)g.B * g.H * g.T + 3) & ~(int64_t)3) + 3 * ((int64_t)g.B * g.T * g.H * 64) / 2;
 }
 // one leftover 32-row block beyond a whole number of workgroups (nw blocks each), and at least one full workgroup
-static bool x3_split_tail(int NB, int nw) { return acr_opt(ACR_OPT_ATTN_F32_NOSPLITTAIL) == 0 && (NB % nw) == 1 && NB > nw; }
+static bool x3_split_tail(int NB, int nw) { return (NB % nw) == 1 && NB > nw; }
 static X3Geom x3_geom(const AttnGeom& g) {
     X3Geom x;
     x.B = g.B; x.H = g.H; x.T = g.T; x.D = g.H * 64; x.scale = g.scale;
@@ -884,7 +884,7 @@ void acr_attn_fwd_f32_x3(const AttnGeom& g, const float* q, const float* k, cons
     const int64_t n8 = (int64_t)g.B * g.T * g.H * 8;
     hipLaunchKernelGGL(x3_split_kernel, dim3((unsigned)((n8 + 255) / 256), 3), dim3(256), 0, st, a);
     const int NB = (g.T + 31) / 32;
-    // measured (scripts/lab/attn_gen.py, A/B through ACR_OPT_ATTN_F32_NOSPLITTAIL): the forward's split tails pay from NB = 33 on
+    // measured (scripts/lab/attn_gen.py against ordinary leftover workgroups; that A/B exists up to commit 101ac4b): the forward's split tails pay from NB = 33 on
     // (T = 1025: 0.624 -> 0.612 ms, T = 2305 at B = 2: 0.355 -> 0.342 ms) but not at T = 785 (0.705 -> 0.724 ms: a tail workgroup's
     // 6-7 unpipelined exact-fp32 steps take about as long as the 25 pipelined split-product steps of a three-per-CU full one)
     // (the split-tail bodies write fp32 o only: a launch that also writes o's image keeps the leftover block on an ordinary workgroup)

@@ -233,215 +233,26 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_dma_kernel(const bf16_t* __r
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// 256x256 tile variant: 4 waves (2 x 2), each owning a 128x128 accumulator (16 MFMA tiles, 256 accumulator registers).
-// The 128x128 kernel above gives every wave a 64x64 tile (4 fragment reads per 4 MFMAs) and relies on a second
-// workgroup per CU to hide its DMA waits.  Here: 8 fragment reads per 16 MFMAs, ONE workgroup per CU, and everything is
-// hidden inside the wave's own instruction stream (same recipe as gemm_tn_bf16_big_kernel below, where it is derived):
-//  * ring of FOUR 32-deep K stages (32 KiB each), filled three stages ahead, counted vmcnt waits;
-//  * the 8 DMA instructions of a stage are spread one per 4 MFMAs (a burst parks the in-order wave in the memory
-//    pipe's issue queue while the matrix pipe drains);
-//  * fragment reads are inline asm with counted lgkmcnt waits, one 16-deep slice ahead of the MFMAs; the asm outputs
-//    are early-clobber: the reads land asynchronously, so an output tuple must never share a register with the address
-//    operand of a later read in the same statement;
-//  * the barrier that publishes stage kt+1 sits between the two slices of stage kt.
-// LDS rows are 64 bytes (4 x 16-byte chunks); chunk c of row r sits at physical chunk c ^ ((r >> 2) & 3), so the 16
-// rows of a ds_read_b128 lane group cover 16 distinct 16-byte slots of the 256-byte bank row.
-// ---------------------------------------------------------------------------------------------------------------
-#define GB_BN 256
-#define GB_BK 32
-
-// MT = 32-row A fragments per wave: the workgroup tile is (64 MT) x 256, MT = 4 -> 256 rows, MT = 5 -> 320 rows.
-// Why 320: with M = 25 120 tokens and N = 768 (proj, fc2 forward, qkv / proj input gradients) a 256-row tile gives
-// 99 x 3 = 297 workgroups -- 1.16 waves of the 256 CUs, i.e. two rounds with the second 16 % full -- while 320 rows give
-// 79 x 3 = 237 workgroups: ONE round on 93 % of the CUs.  The host picks MT so that the tile count fits one round when
-// it can (gb_pick_mt).  LDS: 4 stages x (64 MT + 256) x 64 B = 128 KiB (MT 4) / 144 KiB (MT 5).
-template <bool BIAS, bool RESID, int MT>
-__global__ __launch_bounds__(256) void gemm_nt_bf16_big_kernel(const bf16_t* __restrict__ A, int64_t lda,
-                                                               const bf16_t* __restrict__ B, int64_t ldb,
-                                                               const bf16_t* __restrict__ bias,
-                                                               const bf16_t* __restrict__ R, int64_t ldr,
-                                                               bf16_t* __restrict__ Y, int64_t ldy, int M, int N, int K) {
-    constexpr int BM = 64 * MT;
-    constexpr int STAGE = (BM + GB_BN) * GB_BK;            // elements per stage: A tile (BM x 32) then B tile (256 x 32)
-    constexpr int ND = MT + 4;                             // DMA instructions per stage and thread: MT for A, 4 for B
-    __shared__ __attribute__((aligned(1024))) bf16_t smem[4 * STAGE];
-    typedef __attribute__((address_space(3))) void* lds_vp;
-    typedef const __attribute__((address_space(1))) void* glb_vp;
-    const int ntn = (N + GB_BN - 1) / GB_BN;
-    const int id = acr_xcd_remap(blockIdx.x, gridDim.x);
-    const int tm = id / ntn, tn = id % ntn;
-    const int m0 = tm * BM, n0 = tn * GB_BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int r = lane & 31, hh = lane >> 5;
-    const int nk = K / GB_BK;
-    // DMA instruction q of a stage: q < MT: A rows (wave * MT + q) * 16 .. +15; q >= MT: B rows (wave * 4 + q - MT) * 16 ..
-    uint32_t doff[ND];
-#pragma unroll
-    for (int q = 0; q < ND; ++q) {
-        const int row = (q < MT ? wave * MT + q : wave * 4 + q - MT) * 16 + (lane >> 2);
-        const int lc = (lane & 3) ^ ((row >> 2) & 3);
-        doff[q] = (q < MT) ? (uint32_t)(((int64_t)min(m0 + row, M - 1) * lda + lc * 8) * 2)
-                           : (uint32_t)(((int64_t)min(n0 + row, N - 1) * ldb + lc * 8) * 2);
-    }
-    auto dma = [&](int kt, int q) {
-        const char* base = (q < MT) ? reinterpret_cast<const char*>(A + kt * GB_BK) : reinterpret_cast<const char*>(B + kt * GB_BK);
-        bf16_t* dst = smem + (kt & 3) * STAGE +
-                      ((q < MT) ? (wave * MT + q) * 16 * GB_BK : BM * GB_BK + (wave * 4 + q - MT) * 16 * GB_BK);
-        __builtin_amdgcn_global_load_lds((glb_vp)(base + doff[q]), (lds_vp)dst, 16, 0, 0);
-    };
-    f32x16 acc[MT][4];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    bf16x8 a0[MT], b0[4], a1[MT], b1[4];
-    const int ra = wm * (32 * MT) + r, rb = wn * 128 + r;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) bf16_t*)smem;
-    const uint32_t swa = (ra >> 2) & 3, swb = (rb >> 2) & 3;
-    // byte address of this lane's fragment row for K slice ks: row * 64 + ((2 ks + hh) ^ sw) * 16; +32 rows = +2048 B
-    const uint32_t oa0 = lds0 + ra * 64 + ((hh ^ swa) << 4), oa1 = lds0 + ra * 64 + (((2 + hh) ^ swa) << 4);
-    const uint32_t ob0 = lds0 + BM * GB_BK * 2 + rb * 64 + ((hh ^ swb) << 4);
-    const uint32_t ob1 = lds0 + BM * GB_BK * 2 + rb * 64 + (((2 + hh) ^ swb) << 4);
-    // fragment reads and their waits are inline asm (see the header of this section); outputs early-clobber
-#define GB_RD1(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
-#define GB_READA(dst, addr)                                                                                          \
-    { GB_RD1(dst[0], addr, 0); GB_RD1(dst[1], addr, 2048); GB_RD1(dst[2], addr, 4096); GB_RD1(dst[3], addr, 6144);    \
-      if (MT == 5) GB_RD1(dst[MT - 1], addr, 8192); }
-#define GB_READB(dst, addr)                                                                                          \
-    { GB_RD1(dst[0], addr, 0); GB_RD1(dst[1], addr, 2048); GB_RD1(dst[2], addr, 4096); GB_RD1(dst[3], addr, 6144); }
-    // wait until at most `cnt` LDS reads are outstanding, tied to the fragments that must have landed
-#define GB_WAITF(cnt, x, y)                                                                                          \
-    asm volatile("s_waitcnt lgkmcnt(" #cnt ")"                                                                       \
-                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[MT - 1]), "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]))
-#define GB_MFMAS(x, y)                                                                                               \
-    _Pragma("unroll") for (int i_ = 0; i_ < MT; ++i_) _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                \
-        acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[i_], y[j_], acc[i_][j_], 0, 0, 0)
-    // MODE 0: steady state (issues stage kt+3); 1: a later stage exists but nothing left to issue; 2: last stage.  The
-    // loop is peeled so that each body is straight-line code: the scheduler groups can interleave it, and the
-    // accumulators never meet at a control-flow merge (a merge made the register allocator spill them).
-    auto body = [&](int kt, auto mode_tag) {
-        constexpr int MODE = decltype(mode_tag)::value;
-        const uint32_t so = (uint32_t)(kt & 3) * (STAGE * 2), so2 = (uint32_t)((kt + 1) & 3) * (STAGE * 2);
-        GB_READA(a1, oa1 + so);                             // slice 1 of stage kt
-        GB_READB(b1, ob1 + so);
-        if (MT == 4) { GB_WAITF(8, a0, b0); } else { GB_WAITF(9, a0, b0); }
-        if (MODE == 0) {
-#pragma unroll
-            for (int q = 0; q < MT; ++q) dma(kt + 3, q);    // A part of stage kt+3, spread over this slice's MFMAs
-        }
-        GB_MFMAS(a0, b0);
-        if (MODE == 0) {
-#pragma unroll
-            for (int q = 0; q < MT; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-        GB_WAITF(0, a1, b1);                                // this wave holds every fragment of stage kt
-        if (MODE <= 1) {
-            // stage kt+1 must have landed; stage kt+2 (ND) and the A part of stage kt+3 (MT) may stay in flight
-            if (MODE == 0) {
-                if (MT == 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("s_barrier" ::: "memory");
-            GB_READA(a0, oa0 + so2);                        // slice 0 of stage kt+1
-            GB_READB(b0, ob0 + so2);
-        }
-        if (MODE == 0) {
-#pragma unroll
-            for (int q = MT; q < ND; ++q) dma(kt + 3, q);   // B part
-        }
-        GB_MFMAS(a1, b1);
-        if (MODE == 0) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, MT, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < ND; ++q) dma(0, q);
-    if (nk > 1) {
-#pragma unroll
-        for (int q = 0; q < ND; ++q) dma(1, q);
-    }
-    if (nk > 2) {
-#pragma unroll
-        for (int q = 0; q < ND; ++q) dma(2, q);
-    }
-    if (nk > 2) { if (MT == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); }
-    else if (nk > 1) { if (MT == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); }
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    GB_READA(a0, oa0);
-    GB_READB(b0, ob0);
-    {
-        int kt = 0;
-        for (; kt + 3 < nk; ++kt) body(kt, std::integral_constant<int, 0>{});
-        for (; kt + 1 < nk; ++kt) body(kt, std::integral_constant<int, 1>{});
-        body(kt, std::integral_constant<int, 2>{});
-    }
-#undef GB_RD1
-#undef GB_READA
-#undef GB_READB
-#undef GB_WAITF
-#undef GB_MFMAS
-    __syncthreads();                                        // all fragment reads done before LDS is reused below
-    // Epilogue through LDS, 32 rows x 64 columns of the wave's tile at a time (wave-private 8 KiB), 16-byte stores
-    float* stile = reinterpret_cast<float*>(smem) + wave * 2048;
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int qn = 0; qn < 2; ++qn) {
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) stile[acr_krow(reg, hh) * 64 + nt * 32 + r] = acc[t][qn * 2 + nt][reg];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int idx = lane + 64 * i;
-                const int lrow = idx >> 3, c8 = (idx & 7) * 8;
-                const int row = m0 + wm * (32 * MT) + t * 32 + lrow, col = n0 + wn * 128 + qn * 64 + c8;
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(stile + lrow * 64 + c8);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(stile + lrow * 64 + c8 + 4);
-                if (row < M && col < N) {
-                    float y[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if (BIAS) {
-                        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(bias + col);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) y[e] += (float)bv[e];
-                    }
-                    if (RESID) {
-                        const bf16x8 rv = *reinterpret_cast<const bf16x8*>(R + (int64_t)row * ldr + col);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) y[e] += (float)rv[e];
-                    }
-                    bf16x8 o;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = (bf16_t)y[e];
-                    *reinterpret_cast<bf16x8*>(Y + (int64_t)row * ldy + col) = o;
-                }
-            }
-        }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // 320x256 tile, EIGHT waves (2 x 4, each 160x64: 10 accumulators = 160 registers, two waves per SIMD).  Made for the
 // N = 768 GEMMs of the block (proj / fc2 forward, qkv / proj input gradients) at M = 25 120 tokens: 79 x 3 = 237
 // workgroups = ONE round on 93 % of the CUs, where 128x128 tiles need 2.3 rounds of two-per-CU slots and 256x256 tiles
-// 1.16 rounds.  Same ring recipe as the 256x256 kernel (four 32-deep stages, counted vmcnt, asm fragment reads one
-// slice ahead, DMA spread over the MFMAs, barrier between the slices); two waves per SIMD additionally overlap each
-// other's waits.  A stage is 36 DMA instructions (20 A + 16 B row groups); every wave issues 5, the last four slots
-// re-load B groups 12..15 (same bytes to the same LDS addresses) so that the counted waits are uniform.
+// 1.16 rounds.  Everything is hidden inside the waves' own instruction streams (the ring recipe of
+// gemm_tn_bf16_wide_kernel below, where it is derived):
+//  * ring of FOUR 32-deep K stages, filled three stages ahead, counted vmcnt waits;
+//  * the DMA instructions of a stage are spread over the MFMAs (a burst parks the in-order wave in the memory pipe's
+//    issue queue while the matrix pipe drains);
+//  * fragment reads are inline asm with counted lgkmcnt waits, one 16-deep slice ahead of the MFMAs; the asm outputs
+//    are early-clobber: the reads land asynchronously, so an output tuple must never share a register with the address
+//    operand of a later read in the same statement;
+//  * the barrier that publishes stage kt+1 sits between the two slices of stage kt;
+//  * two waves per SIMD additionally overlap each other's waits.
+// A stage is 36 DMA instructions (20 A + 16 B row groups); every wave issues 5, the last four slots re-load B groups
+// 12..15 (same bytes to the same LDS addresses) so that the counted waits are uniform.  LDS rows are 64 bytes (4 x
+// 16-byte chunks); chunk c of row r sits at physical chunk c ^ ((r >> 2) & 3), so the 16 rows of a ds_read_b128 lane
+// group cover 16 distinct 16-byte slots of the 256-byte bank row.
 // ---------------------------------------------------------------------------------------------------------------
+#define GB_BN 256
+#define GB_BK 32
 #define GW_BM 320
 #define GW_STAGE ((GW_BM + GB_BN) * GB_BK)         // elements per stage = 36 KiB
 
@@ -637,11 +448,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_bf16_wide_kernel(const bf16_t*
     }
 }
 
-// MT = 5 (320-row tiles, one round of the CUs for the N = 768 shapes) is not instantiated: its 160x128 wave tile needs
-// 320 accumulator registers, more than the 256 AGPRs, and hipcc spills ~450 registers instead of keeping the rest of the
-// accumulators in arch VGPRs (measured: 512 VGPR, 464 spills).  Fixing the quantisation of these shapes needs stream-K.
-static int gb_pick_mt(int M, int N) { (void)M; (void)N; return 4; }
-
 extern "C" int acr_linear_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, const void* bias,
                                const void* resid, int64_t ldr, void* y, int64_t ldy, int32_t M, int32_t N, int32_t K,
                                void* stream) {
@@ -653,33 +459,24 @@ extern "C" int acr_linear_bf16(const void* a, int64_t lda, const void* b, int64_
     const int64_t tiles = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
     ACR_CHECK_ARG(tiles < (1ll << 31), "acr_linear_bf16: grid too large");
     const dim3 grid((unsigned)tiles);
-    const int mt = gb_pick_mt(M, N);
     // 320x256 tiles (8 waves) whenever they give the chip enough workgroups: at M = 25 120 tokens they take 36 / 86 / 105
     // / 120 / 142 us on proj, qkv-dX, qkv, fc2, fc1 (820-1030 TF) against 43 / 112 / 126 / 156 / 189 us for the 128x128
     // kernel; the N = 768 shapes fit ONE round of the CUs (79 x 3 = 237 workgroups).  Small problems keep 128x128 tiles.
     const int64_t tilesw = (int64_t)((M + GW_BM - 1) / GW_BM) * ((N + GB_BN - 1) / GB_BN);
-    const bool env_nowide = acr_opt(ACR_OPT_GEMM_NOWIDE) != 0;
-    const bool wide_ok = !env_nowide && tilesw >= 200;
+    const bool wide_ok = tilesw >= 200;
     const dim3 gridw((unsigned)tilesw);
-    const dim3 grid3((unsigned)(((M + 64 * mt - 1) / (64 * mt)) * ((N + GB_BN - 1) / GB_BN)));
     hipStream_t st = (hipStream_t)stream;
-    const int env_variant = acr_opt(ACR_OPT_GEMM_VARIANT);   // 2: 128x128x64 2-stage, 3: 256x256x32 4-stage
     // LDS-DMA kernel stores 8-column (16-byte) groups: needs N, ldy, ldr multiples of 8 and 16-byte aligned y/bias/resid
     const bool vec_ok = (N % 8) == 0 && (ldy % 8) == 0 && (ldr % 8) == 0 && ((uintptr_t)y & 15) == 0 &&
                         ((uintptr_t)bias & 15) == 0 && ((uintptr_t)resid & 15) == 0;
-    const bool env_regstage = acr_opt(ACR_OPT_GEMM_REGSTAGE) != 0;       // A/B switch for the older variant
-    const bool use_regstage = env_regstage || !vec_ok;
 #define ACR_GEMM_LAUNCH(BI, RE)                                                                                       \
-    if (use_regstage)                                                                                                 \
+    if (!vec_ok)                                                                                                      \
         hipLaunchKernelGGL((gemm_nt_bf16_kernel<BI, RE>), grid, dim3(256), 0, st, (const bf16_t*)a, lda,               \
                            (const bf16_t*)b, ldb, (const bf16_t*)bias, (const bf16_t*)resid, ldr, (bf16_t*)y, ldy, M, N, K); \
-    else if (env_variant == 4 || (env_variant == 2 && wide_ok))                                                       \
+    else if (wide_ok)                                                                                                 \
         hipLaunchKernelGGL((gemm_nt_bf16_wide_kernel<BI, RE>), gridw, dim3(512), 0, st, (const bf16_t*)a, lda,         \
                            (const bf16_t*)b, ldb, (const bf16_t*)bias, (const bf16_t*)resid, ldr, (bf16_t*)y, ldy, M, N, K); \
-    else if (env_variant == 3) {                                                                                      \
-            hipLaunchKernelGGL((gemm_nt_bf16_big_kernel<BI, RE, 4>), grid3, dim3(256), 0, st, (const bf16_t*)a, lda,   \
-                               (const bf16_t*)b, ldb, (const bf16_t*)bias, (const bf16_t*)resid, ldr, (bf16_t*)y, ldy, M, N, K); \
-    } else                                                                                                            \
+    else                                                                                                              \
         hipLaunchKernelGGL((gemm_nt_bf16_dma_kernel<BI, RE>), grid, dim3(256), 0, st, (const bf16_t*)a, lda,           \
                            (const bf16_t*)b, ldb, (const bf16_t*)bias, (const bf16_t*)resid, ldr, (bf16_t*)y, ldy, M, N, K)
     if (bias && resid) ACR_GEMM_LAUNCH(true, true);
@@ -927,19 +724,20 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// 256x256 output tile variant of the weight-gradient GEMM: 4 waves (2 x 2), each a 128x128 accumulator.  The weight
-// gradient is the ideal case for the big tile: few output tiles, a 25 120-long contraction split over ~256 workgroups
-// (one per CU, ~45 steps each), so prologue/epilogue amortise and there is no tile quantisation.  Per 16-row slice a wave
-// reads 8 fragments for 16 MFMAs (the 128x128-tile kernel above: 4 for 4), which takes the LDS off the critical path.
-// LDS per stage: dY tile [2 halves][64 m][128 n] + X tile [2 halves][64 m][128 k] = 64 KiB, two stages; each half has
-// exactly the layout of the kernel above, so wg_stage / wg_frag are shared.
+// 256x256 output tile weight-gradient GEMM, EIGHT waves (2 x 4, each a 128x64 accumulator: 8 MFMA tiles = 128
+// registers), TWO waves per SIMD so that one wave's barrier / wait / slab store overlaps the other's MFMAs (what made the
+// 320x256 NT kernel reach 1 PF).  The weight gradient is the ideal case for the big tile: few output tiles, a 25 120-long
+// contraction split over ~256 workgroups (one per CU, ~45 steps each), so prologue/epilogue amortise and there is no
+// tile quantisation.  Per stage: dY tile [2 halves][32 m][128 n] + X tile [2 halves][32 m][128 k]; each half has
+// exactly the layout of the 128x128-tile kernel above.  4 DMA instructions per stage and thread, 12 transpose reads per
+// 16-row slice and wave for 8 MFMAs.
 // ---------------------------------------------------------------------------------------------------------------
 #define WB_ROWS 32                         // contraction rows per ring stage
 #define WB_HALF (WB_ROWS * 128)            // elements of one [32 m][128 cols] half tile
 #define WB_STAGE (4 * WB_HALF)             // [dY half0 | dY half1 | X half0 | X half1] = 32 KiB
 
-// Ring of FOUR 32-row stages (32 KiB each) filled three stages ahead, 8 DMA instructions per stage and thread, spread
-// one per 4 MFMAs.  Three findings shaped this kernel (fc1's dW, 25120 x 3072 x 768, same launch geometry):
+// Ring of FOUR 32-row stages (32 KiB each) filled three stages ahead, the DMA instructions of a stage spread one per 2
+// MFMAs.  Three findings shaped the ring (measured on its 4-wave predecessor, fc1's dW, 25120 x 3072 x 768):
 //  * the compiler puts s_waitcnt vmcnt(0) in front of ds_read_b64_tr_b16 *builtins* that follow an LDS-DMA in the same
 //    block (it cannot disambiguate the DMA's LDS write from the read), which serialises DMA and compute: MFMA+reads
 //    alone 116 us, DMA alone 61 us, together 181 us.  Fragment reads here are inline asm with counted lgkmcnt waits;
@@ -947,152 +745,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 //    over the step's MFMAs (1 KiB per 128 cycles per wave = the consumption rate);
 //  * split-major tile order: the ~32 consecutive ids on one XCD are the tiles of ONE token range (L2 reuse).
 // The barrier that publishes stage it+1 sits between the two 16-row slices of stage it, so the barrier and the first
-// fragment reads of the next stage hide behind 16 MFMAs.  vmcnt bookkeeping at that barrier: stage it+2 (8) and the
-// first half of stage it+3 (4) may stay in flight -> s_waitcnt vmcnt(12).
-__global__ __launch_bounds__(256) void gemm_tn_bf16_big_kernel(const bf16_t* __restrict__ dY, int64_t ldy,
-                                                               const bf16_t* __restrict__ X, int64_t ldx,
-                                                               float* __restrict__ slabs, int M, int N, int K, int nsplit,
-                                                               int steps_per_split) {
-    __shared__ __attribute__((aligned(1024))) bf16_t smem[4 * WB_STAGE];
-    typedef __attribute__((address_space(3))) void* lds_vp;
-    typedef const __attribute__((address_space(1))) void* glb_vp;
-    const int ntk = K >> 8, ntiles = (N >> 8) * ntk;
-    int id = acr_xcd_remap(blockIdx.x, gridDim.x);
-    const int split = id / ntiles; id -= split * ntiles;
-    const int tk = id % ntk, tn = id / ntk;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = wave >> 1, wj = wave & 1;
-    const int r = lane & 31, hh = lane >> 5;
-    const int total_steps = (M + WB_ROWS - 1) / WB_ROWS;
-    const int st0 = split * steps_per_split, st1 = min(st0 + steps_per_split, total_steps);
-    const int n = st1 - st0;
-    f32x16 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    float* slab = slabs + (int64_t)split * N * K;
-    if (n > 0) {
-        // DMA sources: instruction q (0..7) of a stage: operand q>>2 (dY, X), 128-column half (q>>1)&1, row group q&1
-        uint32_t doff[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int row = (wave * 2 + (q & 1)) * 4 + (lane >> 4);
-            const int lc = (lane & 15) ^ ((row & 3) << 2);
-            const int col = ((q >> 2) ? tk : tn) * 256 + ((q >> 1) & 1) * 128 + lc * 8;
-            doff[q] = (uint32_t)(((int64_t)row * ((q >> 2) ? ldx : ldy) + col) * 2);
-        }
-        auto dma = [&](int it, int q) {                      // one DMA instruction of stage `it` (all rows < M: see host)
-            const int64_t m0 = (int64_t)(st0 + it) * WB_ROWS;
-            const char* base = (q >> 2) ? reinterpret_cast<const char*>(X + m0 * ldx) : reinterpret_cast<const char*>(dY + m0 * ldy);
-            bf16_t* dst = smem + (it & 3) * WB_STAGE + (q >> 1) * WB_HALF + (wave * 2 + (q & 1)) * 4 * 128;
-            __builtin_amdgcn_global_load_lds((glb_vp)(base + doff[q]), (lds_vp)dst, 16, 0, 0);
-        };
-        // fragment addresses (bytes): row 16 s + 4 h + (i >> 2) of the wave's half tile, 32-column block t at
-        // chunk (4 t ^ 4 x) with x = row & 3 -- see wg_frag; slice and +8-row offsets are immediates
-        const int li = lane & 15, x = (li >> 2) & 3;
-        const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) bf16_t*)smem;
-        const uint32_t lowb = (uint32_t)((4 * hh + (li >> 2)) * 256 + ((2 * ((lane >> 4) & 1) + ((li & 3) >> 1)) << 4) + ((li & 1) << 3));
-        uint32_t fa[4], fb[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            fa[t] = lds0 + wi * (WB_HALF * 2) + lowb + ((t ^ x) << 6);
-            fb[t] = lds0 + (2 + wj) * (WB_HALF * 2) + lowb + ((t ^ x) << 6);
-        }
-        bf16x4 x0l[8], x0h[8], x1l[8], x1h[8];              // [0..3] = dY fragments, [4..7] = X fragments
-#define WB_RD(lo, hi, addr, OFF)                                                                                     \
-    asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"                         \
-                 : "=&v"(lo), "=&v"(hi) : "v"(addr), "i"(OFF), "i"((OFF) + 2048))
-#define WB_READ8(L, H, so, OFF)                                                                                      \
-    _Pragma("unroll") for (int t_ = 0; t_ < 4; ++t_) {                                                               \
-        WB_RD(L[t_], H[t_], fa[t_] + (so), OFF);                                                                     \
-        WB_RD(L[4 + t_], H[4 + t_], fb[t_] + (so), OFF);                                                             \
-    }
-#define WB_WAIT(cnt, L, H)                                                                                           \
-    asm volatile("s_waitcnt lgkmcnt(" #cnt ")"                                                                       \
-                 : "+v"(L[0]), "+v"(L[1]), "+v"(L[2]), "+v"(L[3]), "+v"(L[4]), "+v"(L[5]), "+v"(L[6]), "+v"(L[7]),   \
-                   "+v"(H[0]), "+v"(H[1]), "+v"(H[2]), "+v"(H[3]), "+v"(H[4]), "+v"(H[5]), "+v"(H[6]), "+v"(H[7]))
-#define WB_MFMA16(L, H)                                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                 \
-        acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                                                       \
-            __builtin_shufflevector(L[i_], H[i_], 0, 1, 2, 3, 4, 5, 6, 7),                                           \
-            __builtin_shufflevector(L[4 + j_], H[4 + j_], 0, 1, 2, 3, 4, 5, 6, 7), acc[i_][j_], 0, 0, 0)
-#define WB_SPREAD4                                                                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                                               \
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                           \
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                           \
-    }
-        // MODE 0: steady state (issues stage it+3); 1: a later stage exists but nothing left to issue; 2: last stage
-        auto body = [&](int it, auto mode_tag) {
-            constexpr int MODE = decltype(mode_tag)::value;
-            const uint32_t so = (uint32_t)(it & 3) * (WB_STAGE * 2), so2 = (uint32_t)((it + 1) & 3) * (WB_STAGE * 2);
-            WB_READ8(x1l, x1h, so, 4096);                   // slice 1 of stage it
-            WB_WAIT(15, x0l, x0h);                          // <= 15 outstanding: the 16 older reads (slice 0) are done
-            if (MODE == 0) {
-                dma(it + 3, 0); dma(it + 3, 1); dma(it + 3, 2); dma(it + 3, 3);
-            }
-            WB_MFMA16(x0l, x0h);
-            if (MODE == 0) { WB_SPREAD4 }
-            WB_WAIT(0, x1l, x1h);                           // this wave holds every fragment of stage it
-            if (MODE <= 1) {
-                if (MODE == 0) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");     // stage it+1 landed (see header)
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                asm volatile("s_barrier" ::: "memory");
-                WB_READ8(x0l, x0h, so2, 0);                 // slice 0 of stage it+1
-            }
-            if (MODE == 0) {
-                dma(it + 3, 4); dma(it + 3, 5); dma(it + 3, 6); dma(it + 3, 7);
-            }
-            WB_MFMA16(x1l, x1h);
-            if (MODE == 0) { WB_SPREAD4 }
-        };
-#pragma unroll
-        for (int q = 0; q < 8; ++q) dma(0, q);
-        if (n > 1) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) dma(1, q);
-        }
-        if (n > 2) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) dma(2, q);
-        }
-        if (n > 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (n > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_barrier" ::: "memory");
-        WB_READ8(x0l, x0h, 0u, 0);
-        int it = 0;
-        for (; it + 3 < n; ++it) body(it, std::integral_constant<int, 0>{});
-        for (; it + 1 < n; ++it) body(it, std::integral_constant<int, 1>{});
-        body(it, std::integral_constant<int, 2>{});
-#undef WB_RD
-#undef WB_READ8
-#undef WB_WAIT
-#undef WB_MFMA16
-#undef WB_SPREAD4
-    }
-    // acc[i][j][reg] = dW[tn*256 + 128 wi + 32 i + krow(reg,hh)][tk*256 + 128 wj + 32 j + r]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int nn = tn * 256 + 128 * wi + 32 * i + acr_krow(reg, hh);
-                const int kk = tk * 256 + 128 * wj + 32 * j + r;
-                slab[(int64_t)nn * K + kk] = acc[i][j][reg];
-            }
-}
+// fragment reads of the next stage hide behind that slice's MFMAs.  vmcnt bookkeeping at that barrier: stage it+2 (4) and the
+// first half of stage it+3 (2) may stay in flight -> s_waitcnt vmcnt(6).
 
-// ---------------------------------------------------------------------------------------------------------------
-// Eight-wave flavour of the 256x256 weight-gradient kernel: waves 2 x 4, each a 128x64 accumulator (8 MFMA tiles = 128
-// registers), TWO waves per SIMD so that one wave's barrier / wait / slab store overlaps the other's MFMAs (what made the
-// 320x256 NT kernel reach 1 PF).  Same ring, same LDS image, same split-major order; 4 DMA instructions per stage and
-// thread, 12 transpose reads per 16-row slice and wave for 8 MFMAs.
-// ---------------------------------------------------------------------------------------------------------------
 // Bias gradient for free: the dY fragments a wave reads ARE the columns whose sums the bias gradient needs (fragment t of
 // a wave = 32 columns x 16 token rows, 8 rows per lane half).  Wave (wi, wj) sums fragment t = wj -- the 8 waves then
 // cover the tile's 256 columns once -- ~16 VALU per 8 MFMAs, hidden behind the matrix pipe.  Every workgroup of a row
@@ -1260,12 +915,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_bf16_wide_kernel(const bf16_t*
 }
 
 static bool wgrad_big_ok(int M, int N, int K) {
-    const int env = acr_opt(ACR_OPT_WGRAD_VARIANT);      // 1: 128x128 tiles, 2: 256x256
     // small problems (that would not fill the chip) and widths that are not multiples of 256 stay on the 128x128 kernel
-    return env == 2 && (N % 256) == 0 && (K % 256) == 0 && M >= 4096;
+    return (N % 256) == 0 && (K % 256) == 0 && M >= 4096;
 }
 
-// The 256x256 kernels have no ragged-row path: they take the first M_main = floor(M / 32) * 32 token rows; the remaining
+// The 256x256 kernel has no ragged-row path: it takes the first M_main = floor(M / 32) * 32 token rows; the remaining
 // (< 32) rows go through the 128x128 kernel (which masks ragged rows) into ONE extra slab, summed with the others.
 struct WgradPlan { bool big; int m_main, tail, nsplit, sps, nslab; };
 static WgradPlan wgrad_plan(int M, int N, int K) {
@@ -1293,17 +947,13 @@ extern "C" size_t acr_wgrad_ws_floats(int32_t M, int32_t N, int32_t K) {
 // slabs of the main part (and of the ragged tail) into ws; cs (nullable): per-slab column sums of dy for the fused bias path
 static void wgrad_launch(const WgradPlan& p, const bf16_t* dy, int64_t ldy, const bf16_t* x, int64_t ldx, int M, int N, int K, float* ws,
                          float* cs, hipStream_t st) {
-    const int tn_waves = acr_opt(ACR_OPT_WGRAD_WAVES);     // 4 or 8 waves per workgroup
-    if (p.big && (tn_waves == 8 || cs)) {
+    if (p.big) {
         if (cs)
             hipLaunchKernelGGL(gemm_tn_bf16_wide_kernel<true>, dim3((N / 256) * (K / 256) * p.nsplit), dim3(512), 0, st, dy, ldy, x, ldx,
                                ws, p.m_main, N, K, p.nsplit, p.sps, cs);
         else
             hipLaunchKernelGGL(gemm_tn_bf16_wide_kernel<false>, dim3((N / 256) * (K / 256) * p.nsplit), dim3(512), 0, st, dy, ldy, x,
                                ldx, ws, p.m_main, N, K, p.nsplit, p.sps, (float*)nullptr);
-    } else if (p.big) {
-        hipLaunchKernelGGL(gemm_tn_bf16_big_kernel, dim3((N / 256) * (K / 256) * p.nsplit), dim3(256), 0, st, dy, ldy, x, ldx, ws,
-                           p.m_main, N, K, p.nsplit, p.sps);
     } else {
         hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3((N / 128) * (K / 128) * p.nsplit), dim3(256), 0, st, dy, ldy, x, ldx, ws, M, N, K,
                            p.nsplit, p.sps);

@@ -1551,7 +1551,7 @@ struct TailPlan { int ntail, nsplit, kps; };
 // MFMA chains and nothing to cover its LDS reads, so launches of up to 256 tiles are split two ways as well.
 static TailPlan gemm_tail_plan(int M, int N, int K, bool x3 = false) {
     TailPlan p = {0, 1, 0};
-    if (acr_opt(ACR_OPT_GEMM_F32_NOTAIL) != 0 || (K % F_BK) != 0 || (N % 4) != 0) return p;
+    if ((K % F_BK) != 0 || (N % 4) != 0) return p;
     const int tiles = ((M + F_BM - 1) / F_BM) * ((N + F_BN - 1) / F_BN);
     // A product of at most a third of the chip's 512 workgroup slots (CAM generation at batch 2: 18-170 tiles) is all tail:
     // every tile is K-split, up to 16 ways, so that the launch fills the CUs instead of running 24-96 chunks on a few of them.
@@ -1614,7 +1614,7 @@ static size_t gemm_ws_base_floats(int mode, int M, int N, int K, bool x3 = false
 struct PlanesPlan { bool on; int nkb; size_t a_fl, b_fl, cs_fl; };
 static PlanesPlan planes_plan(int mode, int math, int M, int N, int K) {
     PlanesPlan p = {false, 0, 0, 0, 0};
-    if (math != ACR_MATH_BF16X3 || acr_opt(ACR_OPT_GEMM_X3_INKERNEL) != 0) return p;
+    if (math != ACR_MATH_BF16X3) return p;
     p.on = true; p.nkb = (K + P_BK - 1) / P_BK;
     if (mode == ACR_GEMM_TN) {                              // images of a[K][M] and b[K][N] as stored: rows = the K tokens
         const size_t nrb = (size_t)(K + 127) / 128;
@@ -1871,9 +1871,9 @@ extern "C" int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float
             if (rc == ACR_OK) rc = acr_gemm_x3(ACR_GEMM_TN, 0, pa, pb, nullptr, nullptr, 0, c, ldc, nullptr, nullptr, M, N, K, ws, stream);
             return rc;
         }
-        if ((K % F_BK) == 0 && off32_ok(M, N, K, lda, ldb, mode) && acr_opt(ACR_OPT_GEMM_F32_REGSTAGE) == 0 && math == ACR_MATH_BF16X3)
+        if ((K % F_BK) == 0 && off32_ok(M, N, K, lda, ldb, mode) && math == ACR_MATH_BF16X3)
             hipLaunchKernelGGL((gemm_f32_split_kernel<false, false, 3>), dim3((unsigned)(g.tiles_m * g.tiles_n * p.nsplit)), dim3(256), 0, st, g);
-        else if ((K % F_BK) == 0 && off32_ok(M, N, K, lda, ldb, mode) && acr_opt(ACR_OPT_GEMM_F32_REGSTAGE) == 0)
+        else if ((K % F_BK) == 0 && off32_ok(M, N, K, lda, ldb, mode))
             hipLaunchKernelGGL((gemm_f32_dma_kernel<false, false, 3>), dim3((unsigned)(g.tiles_m * g.tiles_n * p.nsplit)), dim3(256), 0, st, g);
         else
             hipLaunchKernelGGL((gemm_f32_kernel<false, false, 3>), dim3((unsigned)(g.tiles_m * g.tiles_n * p.nsplit)), dim3(256), 0, st, g);
@@ -1894,7 +1894,7 @@ extern "C" int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float
         else hipLaunchKernelGGL((gemm_f32_kernel<AK, BK_, ACTV>), grid, dim3(256), 0, st, g);                      \
     } while (0)
     const bool split = math == ACR_MATH_BF16X3;                   // products as six bf16 MFMA terms of a three-way split
-    const bool dma = (K % F_BK) == 0 && acr_opt(ACR_OPT_GEMM_F32_REGSTAGE) == 0 && off32_ok(M, N, K, lda, ldb, mode);
+    const bool dma = (K % F_BK) == 0 && off32_ok(M, N, K, lda, ldb, mode);
     TailPlan tp = gemm_tail_plan(M, N, K);
     const bool vec_ok = al16(c) && (ldc % 4) == 0 && (!bias || al16(bias)) && (!aux || (al16(aux) && (ldaux % 4) == 0)) &&
                         (!c2 || al16(c2));
@@ -2013,7 +2013,7 @@ extern "C" int acr_conv1x1_f32(int32_t math, const float* w, int32_t w_transpose
     g.aux = addend; g.ldaux = hw; g.aux_zs = (int64_t)cout * hw;
     g.nsplit = nsamp;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n * nsamp));
-    const bool dma = (cin % F_BK) == 0 && acr_opt(ACR_OPT_GEMM_F32_REGSTAGE) == 0;
+    const bool dma = (cin % F_BK) == 0;
     ACR_CHECK_ARG(math == ACR_MATH_F32 || math == ACR_MATH_BF16X3, "acr_conv1x1_f32: bad math %d", math);
     const bool split = dma && math == ACR_MATH_BF16X3;
     int kps = 0;
@@ -2115,9 +2115,9 @@ extern "C" int acr_conv1x1_wgrad_f32(int32_t math, const float* dy, const float*
     ACR_CHECK_ARG(math == ACR_MATH_F32 || math == ACR_MATH_BF16X3, "acr_conv1x1_wgrad_f32: bad math %d", math);
     // the split-product kernel advances in 16-deep stages: pixel counts that are multiples of 16 suffice (28 x 28 = 784 = 49 x 16
     // took the register-staged exact kernel before: 2.6 ms of the f32_split step)
-    if ((hw % S_BK) == 0 && acr_opt(ACR_OPT_GEMM_F32_REGSTAGE) == 0 && math == ACR_MATH_BF16X3)
+    if ((hw % S_BK) == 0 && math == ACR_MATH_BF16X3)
         hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, 3>), grid, dim3(256), 0, st, g);
-    else if ((hw % F_BK) == 0 && acr_opt(ACR_OPT_GEMM_F32_REGSTAGE) == 0)
+    else if ((hw % F_BK) == 0)
         hipLaunchKernelGGL((gemm_f32_dma_kernel<true, true, 3>), grid, dim3(256), 0, st, g);
     else
         hipLaunchKernelGGL((gemm_f32_kernel<true, true, 3>), grid, dim3(256), 0, st, g);

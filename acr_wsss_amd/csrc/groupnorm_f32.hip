@@ -637,24 +637,21 @@ static GnfRegPlan gnf_reg_plan_nt(int cg, int HW, int nt) {
     p.ok = p.un.units <= GNF_MAXU;
     return p;
 }
-// Workgroup size of the register-resident kernels (ACR_OPT_GN_PLAN).  The register footprint of a group on a CU is the same
-// whatever the workgroup size; what changes is how many INDEPENDENT workgroups share the CU -- a lone 1024-thread workgroup
-// cannot overlap its load phase with another one's store phase.
+// Workgroup size of the register-resident kernels.  The register footprint of a group on a CU is the same whatever the
+// workgroup size; what changes is how many INDEPENDENT workgroups share the CU -- a lone 1024-thread workgroup cannot
+// overlap its load phase with another one's store phase.  Measured fastest (profiles/r06_gn_plans.txt): the forward takes
+// 1024 threads for groups of more than 2048 vectors and 256 threads otherwise, the backward the smallest of 256 / 512 /
+// 1024 threads whose lanes can hold the group.
 static GnfRegPlan gnf_reg_plan(int cg, int HW, int max_slots, bool backward) {
-    const int nvec = cg * (HW >> 2);
-    int pref = acr_opt(ACR_OPT_GN_PLAN);
-    if (pref == 3) pref = backward ? 2 : 0;
-    static const int order[3] = {256, 512, 1024};
     GnfRegPlan p;
-    if (pref == 0) {
-        p = gnf_reg_plan_nt(cg, HW, nvec > 2048 ? 1024 : 256);
+    if (!backward) {
+        p = gnf_reg_plan_nt(cg, HW, cg * (HW >> 2) > 2048 ? 1024 : 256);
         p.ok = p.ok && p.slots <= max_slots && (p.slots <= GNF_RV || p.nt == 1024);
         return p;
     }
-    for (int i = 0; i < 3; ++i) {
-        p = gnf_reg_plan_nt(cg, HW, order[i]);
-        const int cap = (pref == 1 && order[i] == 256) ? GNF_RV : max_slots;      // 1: small workgroups only for small groups
-        if (p.ok && p.slots <= cap) return p;
+    for (int nt = 256; nt <= 1024; nt *= 2) {
+        p = gnf_reg_plan_nt(cg, HW, nt);
+        if (p.ok && p.slots <= max_slots) return p;
     }
     p.ok = false;
     return p;
@@ -669,10 +666,12 @@ static GnfRegPlan gnf_reg_plan(int cg, int HW, int max_slots, bool backward) {
     if ((P).nt == 256) GNF_LAUNCH_REG(KERNEL, 256, RV_, P, __VA_ARGS__)                            \
     else if ((P).nt == 512) GNF_LAUNCH_REG(KERNEL, 512, RV_, P, __VA_ARGS__)                       \
     else GNF_LAUNCH_REG(KERNEL, 1024, RV_, P, __VA_ARGS__)
+// the forward plan launches 256 threads with GNF_RV slots or 1024 threads with any slot count
 #define GNF_DISPATCH_REG_FWD(KERNEL, P, ...)                                                       \
-    if ((P).slots <= GNF_RV) { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV, P, __VA_ARGS__) }                 \
-    else if ((P).slots <= GNF_RV_BWD_MAX) { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV_BWD_MAX, P, __VA_ARGS__) } \
-    else { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV_FWD_MAX, P, __VA_ARGS__) }
+    if ((P).nt == 256) GNF_LAUNCH_REG(KERNEL, 256, GNF_RV, P, __VA_ARGS__)                         \
+    else if ((P).slots <= GNF_RV) GNF_LAUNCH_REG(KERNEL, 1024, GNF_RV, P, __VA_ARGS__)             \
+    else if ((P).slots <= GNF_RV_BWD_MAX) GNF_LAUNCH_REG(KERNEL, 1024, GNF_RV_BWD_MAX, P, __VA_ARGS__) \
+    else GNF_LAUNCH_REG(KERNEL, 1024, GNF_RV_FWD_MAX, P, __VA_ARGS__)
 #define GNF_DISPATCH_REG_BWD(KERNEL, P, ...)                                                       \
     if ((P).slots <= GNF_RV) { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV, P, __VA_ARGS__) }                 \
     else { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV_BWD_MAX, P, __VA_ARGS__) }

@@ -10,8 +10,8 @@ from torch.autograd import Function
 from . import _lib as L
 
 HEAD_DIM = 64
-# fp32 attention with a backward keeps its logits resident in HBM (csrc/attn_f32_sres.hip); ACR_ATTN_F32_SCORES=0 selects the
-# recompute generation (csrc/attn_f32_dma.hip) for A/B runs
+# fp32 attention with a backward keeps its logits resident in HBM (csrc/attn_f32_sres.hip); False selects the recompute
+# generation (csrc/attn_f32_dma.hip)
 ATTN_F32_SCORES = True
 
 
@@ -235,9 +235,6 @@ def attention_core(qkv, heads, stack=None, layer=0, owner=None, math=0):
     return AttnCoreFn.apply(qkv, heads, stack, layer, owner, math)
 
 
-ATTN_O_IMAGE = True      # A/B: the attention output's image from the forward's epilogue
-
-
 def attention_core_oimg(qkv, heads, stack=None, layer=0, owner=None, math=0):
     """attention_core that also returns o's split-product image (or None where the forward cannot write it): (o, pmean, o_image)."""
     return AttnCoreFn.apply(qkv, heads, stack, layer, owner, math, True)
@@ -331,16 +328,13 @@ def wgrad_bf16(dy2, x2):
     return dw
 
 
-FUSED_BIAS_GRAD = True      # A/B switch
-
-
 def wgrad_bias_bf16(dy2, x2):
     """(dW, db) = (dy2^T @ x2, column sums of dy2) in ONE sweep over dy2 (acr_wgrad_bias_bf16: the bias gradient is
     accumulated from the dY fragments inside the weight-gradient kernel); unsupported shapes take the two separate ops."""
     M, N = dy2.shape
     K = x2.shape[1]
     lib = L.load()
-    nws = lib.acr_wgrad_bias_ws_floats(M, N, K) if FUSED_BIAS_GRAD else 0
+    nws = lib.acr_wgrad_bias_ws_floats(M, N, K)
     if (nws == 0 or N % 8 or dy2.stride(1) != 1 or x2.stride(1) != 1 or dy2.stride(0) % 8 or x2.stride(0) % 8
             or dy2.data_ptr() % 16 or x2.data_ptr() % 16):
         return wgrad_bf16(dy2, x2), colsum_bf16(dy2)
@@ -432,21 +426,16 @@ def _dx_f32(dy2, weight, owner, out, aux=None, act=0, math=0):
 
 class LinearBf16Fn(Function):
     """y = x W^T + b (+ resid) for the attention block's qkv / proj Linears in the bf16 mode, on the hand-written
-    MFMA GEMM for forward and input gradient; the weight gradient (a reduction over all tokens) stays on
-    hipBLASLt through torch.mm."""
+    MFMA GEMMs: forward, input gradient and the weight gradient (a reduction over all tokens; the bias gradient rides along
+    where the shape allows)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, resid, hip_dx=True, hip_dw=True, hip_fwd=True, owner=None):
-        ctx.hip_dx, ctx.hip_dw, ctx.owner = hip_dx, hip_dw, owner
+    def forward(ctx, x, weight, bias, resid, owner=None):
+        ctx.owner = owner
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         r2 = resid.reshape(-1, weight.shape[0]) if resid is not None else None
-        if hip_fwd:
-            y = linear_bf16(x2, weight, bias, r2)
-        else:                                               # library GEMM forward, hand-written backward pieces
-            y = torch.nn.functional.linear(x2, weight, bias)
-            if r2 is not None:
-                y.add_(r2)
+        y = linear_bf16(x2, weight, bias, r2)
         ctx.save_for_backward(x2, weight)
         ctx.has_bias, ctx.has_resid = bias is not None, resid is not None
         return y.reshape(*shp[:-1], weight.shape[0])
@@ -459,20 +448,20 @@ class LinearBf16Fn(Function):
             dy2 = dy2.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if ctx.hip_dx and weight.shape[0] % 64 == 0:
+            if weight.shape[0] % 64 == 0:
                 dx = linear_bf16(dy2, weight_t(weight, ctx.owner))
             else:                                           # contraction length not a multiple of the K tile
                 dx = torch.mm(dy2, weight)
             dx = dx.reshape(*dy.shape[:-1], weight.shape[1])
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] and ctx.hip_dw and want_db:
+        if ctx.needs_input_grad[1] and want_db:
             dw, db = wgrad_bias_bf16(dy2, x2)               # one sweep over dy for both
         else:
             if ctx.needs_input_grad[1]:
-                dw = wgrad_bf16(dy2, x2) if ctx.hip_dw else torch.mm(dy2.t(), x2)
+                dw = wgrad_bf16(dy2, x2)
             if want_db:
                 db = colsum_bf16(dy2)
-        return dx, dw, db, (dy if ctx.has_resid else None), None, None, None, None
+        return dx, dw, db, (dy if ctx.has_resid else None), None
 
 
 def mlp_fusable(x, fc1, fc2):
@@ -716,11 +705,8 @@ def _f32_ok(*ts):
 def linear_f32_usable(x, weight):
     K = x.shape[-1]
     N = weight.shape[0]
-    return (F32_HIP_LINEAR and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_contiguous()
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_contiguous()
             and weight.is_contiguous() and K % 4 == 0 and N % 4 == 0 and K >= 32 and N >= 32 and x.numel() // K >= 1)
-
-
-F32_HIP_LINEAR = True      # A/B switch: fp32 Linears on acr_gemm_f32 vs hipBLASLt
 
 
 class LinearF32Fn(Function):
@@ -893,15 +879,14 @@ def mlp_f32(x, fc1, fc2, resid=None, math=0, x_image=None):
     return MlpF32Fn.apply(x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, resid, fc1, fc2, math, x_image)
 
 
-def linear_or_hip(x, lin, resid=None, use_hip=True, hip_dx=True, hip_dw=True, hip_fwd=True, math=0, x_image=None):
+def linear_or_hip(x, lin, resid=None, use_hip=True, math=0, x_image=None):
     """nn.Linear forward; bf16 CUDA tensors with K % 64 == 0 take the hand-written GEMM (resid fused).
-    ``hip_dx`` = False leaves the input gradient on hipBLASLt (shapes where the library kernel is faster).
     ``x_image``: x came out of layer_norm_image -- it exists only as that split-product image."""
     if x_image is not None:
         return LinearF32Fn.apply(x, lin.weight, lin.bias, resid, lin, math, x_image)
     if (use_hip and x.is_cuda and x.dtype == torch.bfloat16 and lin.weight.dtype == torch.bfloat16
             and lin.weight.shape[1] % 64 == 0 and x.is_contiguous()):
-        return LinearBf16Fn.apply(x, lin.weight, lin.bias, resid, hip_dx, hip_dw, hip_fwd, lin)
+        return LinearBf16Fn.apply(x, lin.weight, lin.bias, resid, lin)
     if use_hip and linear_f32_usable(x, lin.weight) and not torch.is_autocast_enabled():
         return LinearF32Fn.apply(x, lin.weight, lin.bias, resid, lin, math)
     y = torch.nn.functional.linear(x, lin.weight, lin.bias)
@@ -966,21 +951,15 @@ def subsample2(x):
     return x[:, :, ::2, ::2].contiguous()
 
 
-F32_HIP_CONV1X1 = True      # A/B switch: fp32 1x1 convolutions on acr_conv1x1_f32 vs MIOpen
-
-
 def conv1x1_fusable(x, weight, stride):
     if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and weight.dtype == x.dtype and x.dim() == 4 and x.is_contiguous()):
         return False
     N, C, H, W = x.shape
     co, ci = weight.shape[0], weight.shape[1]
-    if x.dtype == torch.float32 and (not F32_HIP_CONV1X1 or torch.is_autocast_enabled()):
+    if x.dtype == torch.float32 and torch.is_autocast_enabled():
         return False
     return (stride == 1 and weight.shape[2] == 1 and weight.shape[3] == 1 and ci % 64 == 0 and co % 64 == 0
             and (H * W) % 8 == 0)
-
-
-CONV1X1_WIMG = True      # A/B: split-product 1x1 convolutions with the weight as an image
 
 
 def _conv1x1_f32_launch(math, w2, w_transposed, x, addend, y, N, co, ci, hw, img=None):
@@ -989,7 +968,7 @@ def _conv1x1_f32_launch(math, w2, w_transposed, x, addend, y, N, co, ci, hw, img
     lib = L.load()
     nws = lib.acr_conv1x1_ws_floats(math, N, co, ci, hw)
     ws = torch.empty(nws, dtype=torch.float32, device=x.device) if nws else None
-    if math == 1 and CONV1X1_WIMG and ci % 32 == 0:
+    if math == 1 and ci % 32 == 0:
         wi = img if img is not None else (x3_image_t(w2) if w_transposed else x3_image(w2))
         L.check(lib.acr_conv1x1_x3(L.ptr(wi), L.ptr(x), L.ptr(addend), L.ptr(y), N, co, ci, hw, L.ptr(ws), L.stream_ptr()), "acr_conv1x1_x3")
         return
@@ -1127,9 +1106,6 @@ def conv3x3(x, weight, imgs=None):
 
 
 # ---- stride-2 SAME convolutions (7x7 stem convolution, the two stride-2 3x3s) on the tap-table kernels -------------------------
-CONV_S2_HIP = True      # A/B: strided convolutions under f32_split on csrc/conv3x3.hip vs MIOpen
-
-
 class _S2Plan:
     """Everything a k x k stride-2 TF-SAME convolution of a C-channel H x W input needs on the space-to-depth grid
     (include/acr_hip.h, acr_conv_taps_x3): input row u = 2*o + ky - pb (pb = the SAME padding in front) is row o + dy of pixel
@@ -1225,7 +1201,7 @@ def conv_s2_plan(k, C, H, W, device):
 def conv_s2_fusable(x, weight, stride, math):
     """fp32 NCHW k x k stride-2 SAME convolution with split products that the tap-table kernels cover (k = 3 on C % 16 == 0 channels,
     k = 7 on <= 4): forward always; with gradients only on the shapes the weight-gradient kernel and the depth-to-space pass take."""
-    if not (CONV_S2_HIP and math == 1 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and stride == 2
+    if not (math == 1 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and stride == 2
             and x.is_contiguous() and not torch.is_autocast_enabled() and weight.shape[2] == weight.shape[3]):
         return False
     k, C, (H, W) = weight.shape[2], x.shape[1], x.shape[2:]
@@ -1306,8 +1282,6 @@ def conv1x1(x, weight, wt=None, math=0, imgs=None):
 def conv1x1_skip(x, weight, wt=None, math=0, imgs=None):
     """(conv(x), x_skip): see Conv1x1Fn.  ``wt``: the (cin, cout) copy of the weight when the caller already has one; ``imgs``:
     its split-product images (W, W^T) likewise."""
-    if not SKIP_FUSION:
-        return Conv1x1Fn.apply(x, weight, wt, math, imgs)[0], x
     return Conv1x1Fn.apply(x, weight, wt, math, imgs)
 
 
@@ -1372,26 +1346,18 @@ def layer_norm_fusable(x, ln):
             and C % 256 == 0 and C <= 1024 and not (x.dtype == torch.float32 and torch.is_autocast_enabled()))
 
 
-def layer_norm(x, ln, use_hip=True):
+def layer_norm(x, ln):
     """nn.LayerNorm forward; contiguous bf16 CUDA rows with C % 256 == 0 (<= 1024) take the HIP kernels."""
-    if use_hip and layer_norm_fusable(x, ln):
+    if layer_norm_fusable(x, ln):
         return LayerNormFn.apply(x, ln.weight, ln.bias, ln.eps, False)[0]
     return torch.nn.functional.layer_norm(x, (x.shape[-1],), ln.weight, ln.bias, ln.eps)
 
 
-SKIP_FUSION = True      # A/B switch for the fused skip-gradient adds
-
-
-def layer_norm_skip(x, ln, use_hip=True):
+def layer_norm_skip(x, ln):
     """(LN(x), x_skip) -- see LayerNormFn; on the stock path x_skip is x itself."""
-    if use_hip and layer_norm_fusable(x, ln):
-        if not SKIP_FUSION:
-            return LayerNormFn.apply(x, ln.weight, ln.bias, ln.eps, False)[0], x
+    if layer_norm_fusable(x, ln):
         return LayerNormFn.apply(x, ln.weight, ln.bias, ln.eps, False)
     return torch.nn.functional.layer_norm(x, (x.shape[-1],), ln.weight, ln.bias, ln.eps), x
-
-
-TOKENS_HIP = True      # A/B: the hybrid ViT's token assembly as one kernel each way
 
 
 class TokensFn(Function):
@@ -1421,7 +1387,7 @@ class TokensFn(Function):
 
 
 def tokens_fusable(y, bias, prefix, pos):
-    return (TOKENS_HIP and y.is_cuda and y.dim() == 4 and all(t.dtype == torch.float32 and t.is_contiguous() for t in (y, bias, prefix, pos))
+    return (y.is_cuda and y.dim() == 4 and all(t.dtype == torch.float32 and t.is_contiguous() for t in (y, bias, prefix, pos))
             and prefix.shape[0] <= 8 and pos.shape[1] == prefix.shape[0] + y.shape[2] * y.shape[3] and not torch.is_autocast_enabled())
 
 
@@ -1429,14 +1395,11 @@ def tokens(y, bias, prefix, pos):
     return TokensFn.apply(y, bias, prefix, pos)
 
 
-LN_IMAGE = True      # A/B: the blocks' LayerNorms write their consumer's operand image directly
-
-
-def ln_image_usable(x, ln, lin, math, use_hip=True):
+def ln_image_usable(x, ln, lin, math):
     """norm -> Linear pairs of a block under split products where LN(x) can leave as the Linear's operand image (LayerNormFn with
     image=True + LinearF32Fn / MlpF32Fn with x_image): exactly the conditions under which that Linear takes its image path."""
     C = x.shape[-1]
-    return (LN_IMAGE and use_hip and math == 1 and X3_IMAGES and F32_HIP_LINEAR and SKIP_FUSION and x.is_cuda and x.dtype == torch.float32
+    return (math == 1 and X3_IMAGES and x.is_cuda and x.dtype == torch.float32
             and x.is_contiguous() and ln.weight.dtype == torch.float32 and ln.bias is not None and C % 256 == 0 and C <= 1024
             and not torch.is_autocast_enabled() and lin.weight.dtype == torch.float32 and lin.weight.is_contiguous() and lin.weight.shape[1] == C
             and lin.weight.shape[0] % 4 == 0 and lin.weight.shape[0] >= 32 and _f32_ok(x, ln.weight, ln.bias, lin.weight, lin.bias))
@@ -1448,7 +1411,6 @@ def layer_norm_image(x, ln):
 
 
 GN_ACT = {"none": 0, "relu": 1, "add_relu": 2}
-F32_HIP_NORMS = True      # A/B switch: fp32 GroupNorm on the HIP kernels vs torch
 
 
 def groupnorm_fusable(x, resid=None):
@@ -1457,7 +1419,7 @@ def groupnorm_fusable(x, resid=None):
         return False
     N, C, H, W = x.shape
     if x.dtype == torch.float32:                            # streaming fp32 kernels: any group size, HW % 4 == 0
-        if C % 32 or (H * W) % 4 or torch.is_autocast_enabled() or not F32_HIP_NORMS:
+        if C % 32 or (H * W) % 4 or torch.is_autocast_enabled():
             return False
     elif C % 32 or (H * W) % 8 or (C // 32) * H * W // 8 > 1024 * 13:
         return False
@@ -1541,9 +1503,6 @@ def _wstd_desc(p0s, p1s, p2s, device, p3s=None):
     return host.to(device, non_blocking=True), ch
 
 
-WSTD_TRANSPOSED = True      # A/B: transposed 1x1 weights from the weight-std launch
-
-
 class WeightStdAllFn(Function):
     """w_hat_i = (w_i - mean) / (std + eps) for ALL conv weights of the stem at once (one launch forward, one
     backward) on acr_weight_std_bf16.  Inputs and outputs are tuples of (cout, cin, k, k) bf16 tensors."""
@@ -1555,7 +1514,7 @@ class WeightStdAllFn(Function):
         # bf16 1x1 convolutions: the standardised weight is also written transposed, (cin, cout), for Conv1x1Fn's input
         # gradient (the fp32 kernels read W as stored and need no copy)
         outs_t = [torch.empty((w.shape[1], w.shape[0]), dtype=w.dtype, device=w.device)
-                  if (WSTD_TRANSPOSED and w.dtype == torch.bfloat16 and w.shape[2] == 1 and w.shape[3] == 1) else None for w in ws]
+                  if (w.dtype == torch.bfloat16 and w.shape[2] == 1 and w.shape[3] == 1) else None for w in ws]
         desc, total = _wstd_desc(ws, outs, None, ws[0].device, outs_t)
         ctx.transposed = outs_t
         fn = L.load().acr_weight_std_f32 if ws[0].dtype == torch.float32 else L.load().acr_weight_std_bf16

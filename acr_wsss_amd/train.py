@@ -127,9 +127,6 @@ class PolyOptimizer(torch.optim.SGD):
         _set_versions(ps, [p._version + 1 for p in ps])
 
 
-TABLE_CHECK = True      # A/B (timing only): per-step refresh of the pointer table
-
-
 class MasterWeights:
     """bf16 model, fp32 master weights: the MI355X training precision of this build.
 
@@ -248,17 +245,16 @@ class MasterWeights:
         hn[:, 3] = [p.data_ptr() for p in self.model_params]
         # masters / momentum buffers may have been replaced since the table was built (optimizer.load_state_dict on
         # resume does exactly that): every column is refreshed from the live tensors, so a stale pointer cannot survive
-        if TABLE_CHECK:
-            # one pass over the state dict's items (no tensor hashing): ~0.1 ms for 315 tensors
-            mom_of = {id(p): st.get("momentum_buffer") for p, st in opt.state.items()}
-            moms = []
-            for m in self.masters:
-                buf = mom_of.get(id(m))
-                if buf is None:
-                    buf = opt.state[m]["momentum_buffer"] = torch.zeros_like(m)
-                moms.append(buf)
-            hn[:, 1] = [m.data_ptr() for m in self.masters]
-            hn[:, 2] = [b.data_ptr() for b in moms]
+        # one pass over the state dict's items (no tensor hashing): ~0.1 ms for 315 tensors
+        mom_of = {id(p): st.get("momentum_buffer") for p, st in opt.state.items()}
+        moms = []
+        for m in self.masters:
+            buf = mom_of.get(id(m))
+            if buf is None:
+                buf = opt.state[m]["momentum_buffer"] = torch.zeros_like(m)
+            moms.append(buf)
+        hn[:, 1] = [m.data_ptr() for m in self.masters]
+        hn[:, 2] = [b.data_ptr() for b in moms]
         self._sgd_tab.copy_(host, non_blocking=True)
         self._sgd_evt = torch.cuda.Event()
         self._sgd_evt.record()
@@ -323,7 +319,7 @@ def refresh_weight_transposes(model):
     wt = getattr(model, "_acr_wt_f32", None)
     if wt is None:
         p0 = next(model.parameters(), None)
-        if p0 is None or not p0.is_cuda or p0.dtype != torch.float32 or not _ops.F32_WT or not _ops.F32_HIP_LINEAR:
+        if p0 is None or not p0.is_cuda or p0.dtype != torch.float32 or not _ops.F32_WT:
             return
         wt = _ops.WeightTransposes(model.modules(), dtype=torch.float32)
         object.__setattr__(model, "_acr_wt_f32", wt)       # not a submodule / parameter: plain attribute

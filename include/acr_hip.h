@@ -10,7 +10,7 @@
  *   - plain C, no torch types; device pointers are raw `void*` / `float*` owned by the caller
  *   - work is enqueued on `stream` (a hipStream_t passed as void*); no hidden synchronisation,
  *     no allocation -> safe to capture into a hipGraph, re-entrant.  The ONLY process-wide state is
- *     the explicit option table below (acr_set_option): kernel-variant selectors for A/B measurements,
+ *     the explicit option table below (acr_set_option): a kernel-variant selector for an A/B measurement,
  *     atomically readable, never read from the environment by the library itself
  *   - returns 0 on success, a negative acr_status on failure; acr_last_error() gives a
  *     thread-local message for the last failure on the calling thread
@@ -73,25 +73,12 @@ typedef struct acr_attn_desc {
 int         acr_version(void);
 const char* acr_last_error(void);
 
-/* Kernel-variant selectors (A/B measurement switches; defaults = the measured-fastest settings).
- * Process-wide, set explicitly by the host (acr_wsss_amd/_lib.py maps the documented ACR_* environment variables
- * onto these calls at load time); results are identical under every setting up to the documented tolerances.
+/* Kernel-variant selector (A/B measurement switch; the default = the measured-fastest setting).
+ * Process-wide, set explicitly by the host (acr_wsss_amd/_lib.py set_option); results are identical under every setting.
+ * Codes 0-6 and 8-12 named variants that were retired once their A/B was settled; they are unknown options now.
  * acr_set_option returns ACR_ERR_INVALID for an unknown option; acr_get_option returns INT32_MIN for one. */
 typedef enum acr_option {
-    ACR_OPT_GEMM_VARIANT = 0,   /* acr_linear_bf16: 2 = by size (128x128 LDS-DMA / 320x256 8-wave), 3 = 256x256 4-wave, 4 = always 320x256 */
-    ACR_OPT_GEMM_NOWIDE = 1,    /* 1: never take the 320x256 8-wave kernel */
-    ACR_OPT_GEMM_REGSTAGE = 2,  /* 1: register-staged 128x128 kernel (oldest variant) */
-    ACR_OPT_WGRAD_VARIANT = 3,  /* acr_wgrad_bf16: 1 = 128x128 tiles, 2 = 256x256 */
-    ACR_OPT_WGRAD_WAVES = 4,    /* 4 or 8 waves per 256x256 workgroup */
-    ACR_OPT_DQ_VARIANT = 5,     /* acr_attn_bwd (bf16) dQ sweep: 0 = by presence of G, 2 = 2-wave, 4 = 4-wave */
-    ACR_OPT_GEMM_F32_REGSTAGE = 6, /* 1: acr_gemm_f32 always takes the register-staged kernel (A/B of the LDS-DMA kernel) */
     ACR_OPT_ATTN_DELTA_1HEAD = 7, /* 1: the delta pass of the resident-score backward keeps one wave per (query block, head) reading the gradient block from HBM itself (A/B of the 4-head LDS-staged kernel) */
-    ACR_OPT_RESERVED_8 = 8,      /* was ACR_OPT_ATTN_F32_NW (five-wave forward workgroups: measured slower, out of the library since round 5) */
-    ACR_OPT_GEMM_F32_NOTAIL = 9, /* 1: acr_gemm_f32 NT / NN never K-splits the tiles beyond the last whole half-round (A/B) */
-    ACR_OPT_ATTN_F32_NOSPLITTAIL = 10, /* 1: resident-score attention keeps the leftover 32-row block as an ordinary (1 live wave) workgroup (A/B) */
-    ACR_OPT_GEMM_X3_INKERNEL = 11, /* 1: split-product acr_gemm_f32 splits operand tiles inside the GEMM kernel instead of once per product into bf16 planes (A/B) */
-    ACR_OPT_GN_PLAN = 12,        /* fp32 GroupNorm, register-resident kernels: workgroup size preference -- 0 = 1024 threads for groups of more than 2048 vectors, 1 = 512 threads where the slots allow, 2 = the smallest of 256 / 512 / 1024 threads whose lanes can hold the group, 3 (default) = 0 in the forward and 2 in the backward: measured fastest, profiles/r06_gn_plans.txt (A/B) */
-    ACR_OPT_COUNT_
 } acr_option;
 int     acr_set_option(int32_t option, int32_t value);
 int32_t acr_get_option(int32_t option);

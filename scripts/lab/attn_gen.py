@@ -19,9 +19,8 @@ gst = torch.zeros(B, T, ops.pad4(T), device=dev)
 gst[:, :, :T] = torch.randn(B, T, T, device=dev) * 1e-3
 gpm = gst[:, :, :T]
 res = {}
-for gen in ("recompute", "scores nw4", "split x3 notail", "split x3"):
+for gen in ("recompute", "scores nw4", "split x3"):
     ops.ATTN_F32_SCORES = gen != "recompute"
-    _lib.set_option("attn_f32_nosplittail", 1 if gen.endswith("notail") else 0)
     stack = ops.MeanStack(B, 1, T, dev)
     def run():
         qkv.grad = None

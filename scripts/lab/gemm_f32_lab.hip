@@ -14,7 +14,6 @@ unsigned long long* g_lab_stamp = nullptr;
 static thread_local char g_err[512] = "";
 void acr_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap); }
 int acr_check_launch(const char* what) { hipError_t e = hipGetLastError(); if (e != hipSuccess) { printf("%s: %s\n", what, hipGetErrorString(e)); return -2; } return 0; }
-int32_t acr_opt(int) { return getenv("LAB_REG") ? 1 : 0; }
 
 // bare MFMA loop: peak of this box
 __global__ __launch_bounds__(256) void mfma_peak(float* out, int iters) {

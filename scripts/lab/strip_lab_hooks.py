@@ -7,7 +7,7 @@
 
 The hooks compiled to nothing in product builds; the device ISA before and after the transform is compared with
 `scripts/lab/strip_lab_hooks.py --check` (hipcc --cuda-device-only -S on both trees).  The phase-timer builds the lab scripts
-used (`attn_x3_phases.py`, `attn_bwd_phases.py`, `gemm_timeline.py`, ...) now build from the tree at the last commit that carried
+used (`attn_x3_phases.py`, `attn_bwd_phases.py`, `gemm_timeline.py` (removed; at `101ac4b`), ...) now build from the tree at the last commit that carried
 the hooks: `git archive <that commit> acr_wsss_amd/csrc | tar -x -C scripts/lab/_build/hooks` (build_variant.sh -H).
 
 usage: strip_lab_hooks.py file.hip [...]        (rewrites in place)
