@@ -131,7 +131,8 @@ class DPT(BaseModel):
 class ACR(DPT):
     def __init__(self, num_classes, backbone_name, path=None, math="f32", **kwargs):
         """Reference signature (DPT/ACR.py:148) plus ``math``: how this model's fp32 matrix products are evaluated
-        ("f32" exact-fp32 MFMA = the reference's arithmetic, "f32_split" = bf16x3 split products; backbone.set_math)."""
+        ("f32" exact-fp32 MFMA = the reference's arithmetic, "f32_split" = bf16x3 split products, "f32_fp16x2" = opt-in,
+        narrower fp16x2 products for the block Linears only; backbone.set_math)."""
         self.num_class = num_classes
         kwargs["use_bn"] = True
         backbone_dict = {"vitb_hybrid": "vitb_rn50_384", "vitb": "vitb16_384", "deit": "deitb16_384",
@@ -145,7 +146,8 @@ class ACR(DPT):
             self.load(path)
 
     def set_math(self, math):
-        """"f32" | "f32_split" for every fp32 product of this model (a per-model property carried into each C-ABI call)."""
+        """"f32" | "f32_split" | "f32_fp16x2" for the fp32 products of this model (a per-model property carried into each C-ABI
+        call; "f32_fp16x2" changes the block Linears only and is never the default: backbone.set_math)."""
         from ..backbone import set_math
         from .._lib import MATH
         if math not in MATH:

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("ACR_LIB_PATH") or os.path.join(_HERE, "libacr_hip.so"
 ACR_F32, ACR_BF16, ACR_BF16_F32MATH, ACR_F32_BF16X3 = 0, 1, 2, 3
 # acr_math (include/acr_hip.h): how an fp32 entry point multiplies -- a per-call argument.  "f32": exact-fp32 MFMA;
 # "f32_split": six bf16-MFMA terms of a three-way operand split (fp32 tensors, fp32 accumulate, fp32-accurate)
-MATH = {"f32": 0, "f32_split": 1}
+MATH = {"f32": 0, "f32_split": 1, "f32_fp16x2": 2}
 BF16_F32MATH = False      # True: bf16 tensors take the exact-fp32 MFMA kernels (reference for the bf16-MFMA ones)
 GETAM_FUNCS = {"grad": 0, "cam_grad": 1, "grad_s": 2, "cam_grad_s": 3}
 
@@ -69,6 +69,14 @@ SIGNATURES = {
     "acr_x3_image_t": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_gemm_x3_ws_floats": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "acr_gemm_x3": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32,
+                              c_int32, c_int32, c_void_p, c_void_p]),
+    "acr_h2_image_floats": (c_size_t, [c_int32, c_int32]),
+    "acr_h2_ws_floats": (c_size_t, [c_int32, c_int32]),
+    "acr_h2_image": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_h2_image_cols": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_h2_image_t": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "acr_gemm_h2_ws_floats": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "acr_gemm_h2": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32,
                               c_int32, c_int32, c_void_p, c_void_p]),
     "acr_gemm_f32": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

@@ -29,13 +29,18 @@ def set_math(module, math):
       "f32"        exact-fp32 MFMA, the reference's arithmetic (default; what CAM inference and the parity fixtures run);
       "f32_split"  the same fp32 tensors with every product of the block Linears, the stem's 1x1 convolutions and the
                    attention as six bf16-MFMA terms of a three-way operand split (include/acr_hip.h: acr_math) --
-                   fp32-accurate, 24 mantissa bits per operand, fp32 accumulate.
+                   fp32-accurate, 24 mantissa bits per operand, fp32 accumulate;
+      "f32_fp16x2" opt-in and NARROWER: the block Linears (qkv, proj, fc1, fc2: forward, input and weight gradient) as three
+                   fp16-MFMA terms of a two-piece split with a power-of-two scale per row / column (22 significand bits per
+                   operand, include/acr_hip.h ACR_MATH_FP16X2); the attention core, the stem and the patch-embedding
+                   projection run exactly what "f32_split" runs.
     Has no effect on a bf16 model.  Returns the module."""
     from . import _lib
     code = _lib.MATH[math] if isinstance(math, str) else int(math)
     for m in module.modules():
         if hasattr(type(m), "acr_math"):
-            m.acr_math = code
+            # fp16x2 is built for the block Linears only (Mlp, Attention's qkv / proj); everything else keeps the split products
+            m.acr_math = code if code != _lib.MATH["f32_fp16x2"] or isinstance(m, (Mlp, Attention)) else _lib.MATH["f32_split"]
     return module
 
 
@@ -391,7 +396,7 @@ class Attention(nn.Module):
         self.last_pm = None         # (B,T,T) head-mean map of the last forward (slice of the MeanStack)
 
     hip_linear = True       # qkv / proj on the hand-written MFMA GEMMs (acr_linear_bf16 / acr_gemm_f32)
-    acr_math = 0            # _lib.MATH code of the fp32 products: Linears and, in training, the attention core (set_math)
+    acr_math = 0            # _lib.MATH code of the fp32 products: Linears and, in training, the attention core (set_math; fp16x2: Linears only)
     keep_state_in_training = False      # True: get_attn() / get_attn_gradients() also work after a train()-mode forward
 
     def forward(self, x, stack=None, layer=0, resid=None, x_image=None):
@@ -399,12 +404,13 @@ class Attention(nn.Module):
         proj GEMM epilogue on the bf16 path).  ``x_image``: x is the output of ops.layer_norm_image (it exists only as that image)."""
         self._override = {}
         qkv = ops.linear_or_hip(x, self.qkv, None, self.hip_linear, math=self.acr_math, x_image=x_image)  # packed (B, T, 3*H*64): no permute copy
+        core_math = 1 if self.acr_math == 2 else self.acr_math          # fp16x2 changes the Linears only: the core runs the split products
         if (self.acr_math == 1 and self.hip_linear and ops.X3_IMAGES and ops.linear_f32_usable(qkv, self.proj.weight)
                 and not torch.is_autocast_enabled() and ops._f32_ok(self.proj.weight, self.proj.bias, resid)):
             # split products: o leaves the attention forward as proj's operand image (no image pass over o)
             o, self.last_pm, oimg = ops.attention_core_oimg(qkv, self.num_heads, stack, layer, self, self.acr_math)
             return ops.linear_or_hip(o, self.proj, resid, self.hip_linear, math=self.acr_math, x_image=oimg)
-        o, self.last_pm = ops.attention_core(qkv, self.num_heads, stack, layer, self, self.acr_math)
+        o, self.last_pm = ops.attention_core(qkv, self.num_heads, stack, layer, self, core_math)
         return ops.linear_or_hip(o, self.proj, resid, self.hip_linear, math=self.acr_math)
 
     # -- reference state API (vision_transformer.py:186-196) --

@@ -22,7 +22,9 @@
 // step (q, s), which is what makes one 16-byte read feed four MFMAs.
 #include <math.h>
 
+#include <mutex>
 #include <type_traits>
+#include <unordered_map>
 
 #include "acr_common.h"
 
@@ -48,6 +50,7 @@ struct GemmF32Args {
     int tile0, tiles_launch;             // this launch covers tiles tile0 .. tile0 + tiles_launch - 1 (each nsplit times)
     int nkb_a, nkb_b;                    // gemm_f32_planes_tn_kernel: stages (16 features) per token block of the a / b image
     int img_nkb;                         // image epilogues (ACT 5, 6): stages per row block of the OUTPUT image c2 points at (ceil(N / 16))
+    const int* ea; const int* eb;        // fp16x2 images: scale exponents per output row (of a) / column (of b)
     // z-slices: workgroup slice z = split index.  K-split (weight gradient of a Linear): operands shared, k range z*k_zs..;
     // batch (1x1 convolutions per sample): operands / outputs advance by *_zs per slice, k range the whole contraction
     int64_t a_zs, b_zs, c_zs, aux_zs;
@@ -681,6 +684,55 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const GemmF32Arg
 #define P_STAGE_B (6 * P_TILE_B)
 #define PL_RD(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
 
+// Image formats of the planes kernels (template parameter FMT):
+//   0  bf16x3: three bf16 planes, six MFMA terms per tile and stage (v_mfma_f32_32x32x16_bf16);
+//   1  fp16x2: two fp16 planes of x * 2^e, e an exact power-of-two scale per NON-contracted index (row of an NT operand, column of
+//      a TN operand, acr_h2_image*), three terms (v_mfma_f32_32x32x16_f16, same lane maps and rate), ldexp(acc, -(e_a + e_b))
+//      before the epilogue.  A stage carries 2 planes instead of 3: 16 KiB instead of 24, 4 DMA pieces per wave instead of 6.
+// Terms are issued smallest first: (0,2) (2,0) (1,1) (0,1) (1,0) (0,0) resp. (0,1) (1,0) (0,0).
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <int FMT> struct PlanesFmt { static constexpr int NP = FMT == 0 ? 3 : 2, NT = FMT == 0 ? 6 : 3; };
+__host__ __device__ constexpr int pl_ta(int fmt, int t) { return fmt == 0 ? (t == 1 ? 2 : (t == 2 || t == 4) ? 1 : 0) : (t == 1 ? 1 : 0); }
+__host__ __device__ constexpr int pl_tb(int fmt, int t) { return fmt == 0 ? (t == 0 ? 2 : (t == 2 || t == 3) ? 1 : 0) : (t == 0 ? 1 : 0); }
+template <int FMT>
+__device__ __forceinline__ f32x16 pl_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
+    if constexpr (FMT == 0) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// MFMAs M0 .. M1 - 1 of a stage (m = tile * NT + term, tile = 2 I + J) on register sets a[block][plane], b[block][plane]
+template <int FMT, int M0, int M1>
+__device__ __forceinline__ void pl_mfmas(f32x16 (&acc)[2][2], const bf16x8 (&a)[2][PlanesFmt<FMT>::NP], const bf16x8 (&b)[2][PlanesFmt<FMT>::NP]) {
+    if constexpr (M0 < M1) {
+        constexpr int NT = PlanesFmt<FMT>::NT, t = M0 / NT, k = M0 % NT;
+        acc[t >> 1][t & 1] = pl_mfma<FMT>(a[t >> 1][pl_ta(FMT, k)], b[t & 1][pl_tb(FMT, k)], acc[t >> 1][t & 1]);
+        pl_mfmas<FMT, M0 + 1, M1>(acc, a, b);
+    }
+}
+// the same on the transposed reads of gemm_f32_planes_tn_kernel (fragment = lo tokens | hi tokens)
+template <int FMT, int M0, int M1>
+__device__ __forceinline__ void pt_mfmas(f32x16 (&acc)[2][2], const bf16x4 (&al)[2][PlanesFmt<FMT>::NP], const bf16x4 (&ah)[2][PlanesFmt<FMT>::NP],
+                                         const bf16x4 (&bl)[2][PlanesFmt<FMT>::NP], const bf16x4 (&bh)[2][PlanesFmt<FMT>::NP]) {
+    if constexpr (M0 < M1) {
+        constexpr int NT = PlanesFmt<FMT>::NT, t = M0 / NT, k = M0 % NT;
+        constexpr int I = t >> 1, J = t & 1, PA = pl_ta(FMT, k), PB = pl_tb(FMT, k);
+        acc[I][J] = pl_mfma<FMT>(__builtin_shufflevector(al[I][PA], ah[I][PA], 0, 1, 2, 3, 4, 5, 6, 7),
+                                 __builtin_shufflevector(bl[J][PB], bh[J][PB], 0, 1, 2, 3, 4, 5, 6, 7), acc[I][J]);
+        pt_mfmas<FMT, M0 + 1, M1>(acc, al, ah, bl, bh);
+    }
+}
+// fp16x2: acc *= 2^-(e_a[row] + e_b[col]) for one wave's 64 x 64 block (rows mb.., columns nb..); exact unless the result is subnormal
+__device__ __forceinline__ void h2_unscale(const GemmF32Args& g, f32x16 (&acc)[2][2], int mb, int nb, int r, int h) {
+    const int eb0 = g.eb[min(nb + r, g.N - 1)], eb1 = g.eb[min(nb + 32 + r, g.N - 1)];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ea = g.ea[min(mb + i * 32 + acr_krow(e, h), g.M - 1)];
+            acc[i][0][e] = ldexpf(acc[i][0][e], -(ea + eb0));
+            acc[i][1][e] = ldexpf(acc[i][1][e], -(ea + eb1));
+        }
+}
+
 // ---- image epilogues: the product's output leaves the kernel AS the image the next product reads -----------------------------
 // ACT 5 (fc1 forward): h = acc + bias; c = GELU'(h) in fp32 (all the backward needs of h), c2 = IMAGE of GELU(h) -- fc2's operand
 //        in the forward and in its weight gradient; the fp32 activation is never written.
@@ -842,9 +894,11 @@ __global__ __launch_bounds__(256) void gemm_x3_tail_image_kernel(const GemmF32Ar
     if (ACT == 6 && g.cs) x3_tile_colsum(csum, red, tid, g.cs + (int64_t)tm * g.N, n0, g.N);
 }
 
-template <int ACT>
+template <int ACT, int FMT = 0>
 __global__ __launch_bounds__(256, 2) void gemm_f32_planes_kernel(const GemmF32Args g) {
-    __shared__ __attribute__((aligned(1024))) float smem[P_SLOTS * P_STAGE_B / 4];      // 72 KiB
+    constexpr int NP = PlanesFmt<FMT>::NP, NG = 4 * NP, NM = 4 * PlanesFmt<FMT>::NT;     // reads (= groups) and MFMAs per stage
+    constexpr int STAGE_B = 2 * NP * P_TILE_B;
+    __shared__ __attribute__((aligned(1024))) float smem[P_SLOTS * STAGE_B / 4];          // 72 KiB (bf16x3), 48 KiB (fp16x2)
     typedef __attribute__((address_space(3))) void* lds_vp;
     typedef const __attribute__((address_space(1))) void* glb_vp;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -860,10 +914,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_kernel(const GemmF32Ar
     const int zs = split / g.ksplit;
     const int kbeg = (split - zs * g.ksplit) * g.k_zs, kend = min(g.K, kbeg + g.kps);      // host: K, kps multiples of 16
     const int nkb = g.K / P_BK;                             // stages per row block in the tiled image
-    // this wave's six KiB of every stage: waves 0, 1 the two halves of A's 12 KiB, waves 2, 3 of B's
-    const char* __restrict__ pw = (wave < 2 ? reinterpret_cast<const char*>(g.a) + ((int64_t)tm * nkb + kbeg / P_BK) * (3 * P_TILE_B)
-                                            : reinterpret_cast<const char*>(g.b) + ((int64_t)tn * nkb + kbeg / P_BK) * (3 * P_TILE_B)) +
-                                  (wave & 1) * (6 * 1024) + lane * 16;
+    // this wave's 2 NP KiB of every stage: waves 0, 1 the two halves of A's NP * 4 KiB, waves 2, 3 of B's
+    const char* __restrict__ pw = (wave < 2 ? reinterpret_cast<const char*>(g.a) + ((int64_t)tm * nkb + kbeg / P_BK) * (NP * P_TILE_B)
+                                            : reinterpret_cast<const char*>(g.b) + ((int64_t)tn * nkb + kbeg / P_BK) * (NP * P_TILE_B)) +
+                                  (wave & 1) * (2 * NP * 1024) + lane * 16;
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -874,44 +928,47 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_kernel(const GemmF32Ar
     const int nst = (kend - kbeg) / P_BK;
     char* sm = reinterpret_cast<char*>(smem);
     auto dma1 = [&](int st, int slot, int i) {
-        __builtin_amdgcn_global_load_lds((glb_vp)(pw + (int64_t)st * (3 * P_TILE_B) + i * 1024), (lds_vp)(sm + slot * P_STAGE_B + (wave * 6 + i) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_vp)(pw + (int64_t)st * (NP * P_TILE_B) + i * 1024), (lds_vp)(sm + slot * STAGE_B + (wave * 2 * NP + i) * 1024), 16, 0, 0);
     };
     const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)sm;
     const uint32_t hx = (h ^ ((r >> 3) & 1)) * 16;
-    const uint32_t fa = lbase + (wm * 64 + r) * 32 + hx, fb = lbase + 3 * P_TILE_B + (wn * 64 + r) * 32 + hx;
+    const uint32_t fa = lbase + (wm * 64 + r) * 32 + hx, fb = lbase + NP * P_TILE_B + (wn * 64 + r) * 32 + hx;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) dma1(0, 0, i);
+    for (int i = 0; i < 2 * NP; ++i) dma1(0, 0, i);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) dma1(min(1, nst - 1), 1, i);
-    bf16x8 ap[2][2][3], bp[2][2][3];                        // [register set][block][plane]
-#define PL_MFMA(SET, I, J, PA, PB) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][PA], bp[SET][J][PB], acc[I][J], 0, 0, 0);
-#define PL_PAIR(SET, I, J, T)                                                       \
-    if (T == 0) { PL_MFMA(SET, I, J, 0, 2) PL_MFMA(SET, I, J, 2, 0) }              \
-    else if (T == 1) { PL_MFMA(SET, I, J, 1, 1) PL_MFMA(SET, I, J, 0, 1) }         \
-    else { PL_MFMA(SET, I, J, 1, 0) PL_MFMA(SET, I, J, 0, 0) }
+    for (int i = 0; i < 2 * NP; ++i) dma1(min(1, nst - 1), 1, i);
+    bf16x8 ap[2][2][NP], bp[2][2][NP];                      // [register set][block][plane]
     // step st (slot = st % 3): stage st has landed for everyone -> refill the slot stage st - 1 was read from with stage st + 2
     // (past the end: the last stage again, into a slot nobody reads -- keeps the DMA count per step, hence the vmcnt, constant),
     // read stage st into register set SET while the MFMAs of stage st - 1 (set SET ^ 1) run
     auto step = [&](int st, int slot, auto set_tag, auto first_tag) {
         constexpr int SET = decltype(set_tag)::value;
         constexpr bool FIRST = decltype(first_tag)::value;
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // younger: the 6 pieces of stage st + 1
+        if constexpr (NP == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // younger: the 2 NP pieces of stage st + 1
+        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         acr_barrier_nofence();
         const int rslot = slot == 0 ? 2 : slot - 1;         // (st + 2) % 3
         const int rst = min(st + 2, nst - 1);
-        const uint32_t fas = fa + slot * P_STAGE_B, fbs = fb + slot * P_STAGE_B;
+        const uint32_t fas = fa + slot * STAGE_B, fbs = fb + slot * STAGE_B;
 #define PL_GROUP(K12)                                                                                                   \
-        if (!FIRST) { PL_PAIR(SET ^ 1, ((K12) / 6), (((K12) / 3) & 1), ((K12) % 3)) }                                   \
-        if ((K12) < 6) PL_RD(ap[SET][(K12) / 3][(K12) % 3], fas, ((K12) % 3) * P_TILE_B + ((K12) / 3) * 1024);          \
-        else PL_RD(bp[SET][((K12) - 6) / 3][(K12) % 3], fbs, ((K12) % 3) * P_TILE_B + (((K12) - 6) / 3) * 1024);        \
-        if ((K12) & 1) dma1(rst, rslot, (K12) >> 1);                                                                   \
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr ((K12) < NG) {                                                                                     \
+            if constexpr (!FIRST) pl_mfmas<FMT, (K12) * NM / NG, ((K12) + 1) * NM / NG>(acc, ap[SET ^ 1], bp[SET ^ 1]);  \
+            if constexpr ((K12) < 2 * NP) PL_RD(ap[SET][(K12) / NP][(K12) % NP], fas, ((K12) % NP) * P_TILE_B + ((K12) / NP) * 1024); \
+            else PL_RD(bp[SET][((K12) - 2 * NP) / NP][(K12) % NP], fbs, ((K12) % NP) * P_TILE_B + (((K12) - 2 * NP) / NP) * 1024); \
+            if ((K12) & 1) dma1(rst, rslot, (K12) >> 1);                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                          \
+        }
         PL_GROUP(0) PL_GROUP(1) PL_GROUP(2) PL_GROUP(3) PL_GROUP(4) PL_GROUP(5)
         PL_GROUP(6) PL_GROUP(7) PL_GROUP(8) PL_GROUP(9) PL_GROUP(10) PL_GROUP(11)
 #undef PL_GROUP
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(ap[SET][0][0]), "+v"(ap[SET][0][1]), "+v"(ap[SET][0][2]), "+v"(ap[SET][1][0]), "+v"(ap[SET][1][1]), "+v"(ap[SET][1][2]),
-                       "+v"(bp[SET][0][0]), "+v"(bp[SET][0][1]), "+v"(bp[SET][0][2]), "+v"(bp[SET][1][0]), "+v"(bp[SET][1][1]), "+v"(bp[SET][1][2]));
+        if constexpr (NP == 3)
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(ap[SET][0][0]), "+v"(ap[SET][0][1]), "+v"(ap[SET][0][2]), "+v"(ap[SET][1][0]), "+v"(ap[SET][1][1]), "+v"(ap[SET][1][2]),
+                           "+v"(bp[SET][0][0]), "+v"(bp[SET][0][1]), "+v"(bp[SET][0][2]), "+v"(bp[SET][1][0]), "+v"(bp[SET][1][1]), "+v"(bp[SET][1][2]));
+        else
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(ap[SET][0][0]), "+v"(ap[SET][0][1]), "+v"(ap[SET][1][0]), "+v"(ap[SET][1][1]),
+                           "+v"(bp[SET][0][0]), "+v"(bp[SET][0][1]), "+v"(bp[SET][1][0]), "+v"(bp[SET][1][1]));
     };
     step(0, 0, std::integral_constant<int, 0>{}, std::true_type{});
     int slot = 1;
@@ -923,17 +980,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_kernel(const GemmF32Ar
             slot = slot == 2 ? 0 : slot + 1;
         }
     }
-#define PL_ALL(SET)                                                                                      \
-    PL_PAIR(SET, 0, 0, 0) PL_PAIR(SET, 0, 0, 1) PL_PAIR(SET, 0, 0, 2) PL_PAIR(SET, 0, 1, 0) PL_PAIR(SET, 0, 1, 1) PL_PAIR(SET, 0, 1, 2) \
-    PL_PAIR(SET, 1, 0, 0) PL_PAIR(SET, 1, 0, 1) PL_PAIR(SET, 1, 0, 2) PL_PAIR(SET, 1, 1, 0) PL_PAIR(SET, 1, 1, 1) PL_PAIR(SET, 1, 1, 2)
-    if (nst & 1) { PL_ALL(0) } else { PL_ALL(1) }
-#undef PL_ALL
-#undef PL_PAIR
-#undef PL_MFMA
+    if (nst & 1) pl_mfmas<FMT, 0, NM>(acc, ap[0], bp[0]);
+    else pl_mfmas<FMT, 0, NM>(acc, ap[1], bp[1]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the refills past the end
     __syncthreads();                                        // every wave is done with the ring: the finish may reuse it
-    if (ACT == 5 || ACT == 6) x3_finish_image<ACT>(g, acc, smem, tm, tn, m0, n0, wm, wn, r, h, tid);
-    else gemm_f32_finish<true, ACT == 5 || ACT == 6 ? 0 : ACT>(g, acc, smem, split, tt, tn, m0, n0, zs, wm, wn, r, h, tid, 0.f, false);
+    if constexpr (FMT == 1) h2_unscale(g, acc, m0 + wm * 64, n0 + wn * 64, r, h);
+    if constexpr (ACT == 5 || ACT == 6) x3_finish_image<ACT>(g, acc, smem, tm, tn, m0, n0, wm, wn, r, h, tid);
+    else gemm_f32_finish<true, ACT>(g, acc, smem, split, tt, tn, m0, n0, zs, wm, wn, r, h, tid, 0.f, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -949,8 +1002,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_kernel(const GemmF32Ar
 #define PL_RDTR(lo, hi, alo, ahi, OFF)                                                                  \
     asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"          \
                  : "=&v"(lo), "=&v"(hi) : "v"(alo), "v"(ahi), "i"(OFF))
+template <int FMT = 0>
 __global__ __launch_bounds__(256, 2) void gemm_f32_planes_tn_kernel(const GemmF32Args g) {
-    __shared__ __attribute__((aligned(1024))) float smem[P_SLOTS * P_STAGE_B / 4];      // 72 KiB
+    constexpr int NP = PlanesFmt<FMT>::NP, NG = 4 * NP, NM = 4 * PlanesFmt<FMT>::NT;
+    constexpr int STAGE_B = 2 * NP * P_TILE_B;
+    __shared__ __attribute__((aligned(1024))) float smem[P_SLOTS * STAGE_B / 4];          // 72 KiB (bf16x3), 48 KiB (fp16x2)
     typedef __attribute__((address_space(3))) void* lds_vp;
     typedef const __attribute__((address_space(1))) void* glb_vp;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -965,13 +1021,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_tn_kernel(const GemmF3
     const int nkb = wave < 2 ? g.nkb_a : g.nkb_b;          // feature stages per token block of this wave's operand
     const int f0 = (wave < 2 ? tm : tn) * 8;               // first feature stage of the tile
     const char* __restrict__ pw = reinterpret_cast<const char*>(wave < 2 ? g.a : g.b);
-    // piece q = 6 (wave & 1) + i of the operand's 12: plane q >> 2, chunk pair q & 3 (feature stages f0 + 2 (q & 3) + (lane >> 5));
+    // piece q = 2 NP (wave & 1) + i of the operand's 4 NP: plane q >> 2, chunk pair q & 3 (feature stages f0 + 2 (q & 3) + (lane >> 5));
     // feature stages past the operand's end (M or N not a multiple of 128) alias the last one: rows the finish never stores
-    int offd[6];
+    int offd[2 * NP];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int q = (wave & 1) * 6 + i, pl = q >> 2, fs = min(f0 + 2 * (q & 3) + (lane >> 5), nkb - 1);
-        offd[i] = (fs * 3 + pl) * P_TILE_B + (lane & 31) * 16;
+    for (int i = 0; i < 2 * NP; ++i) {
+        const int q = (wave & 1) * 2 * NP + i, pl = q >> 2, fs = min(f0 + 2 * (q & 3) + (lane >> 5), nkb - 1);
+        offd[i] = (fs * NP + pl) * P_TILE_B + (lane & 31) * 16;
     }
     f32x16 acc[2][2];
 #pragma unroll
@@ -984,9 +1040,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_tn_kernel(const GemmF3
     char* sm = reinterpret_cast<char*>(smem);
     auto dma1 = [&](int st, int slot, int i) {
         const int tk = kbeg + st * P_BK;                    // uniform
-        const char* src = pw + ((int64_t)(tk >> 7) * nkb) * (3 * P_TILE_B) + (tk & 127) * 32;
-        const int q = (wave & 1) * 6 + i;
-        __builtin_amdgcn_global_load_lds((glb_vp)(src + offd[i]), (lds_vp)(sm + slot * P_STAGE_B + (wave >> 1) * (3 * P_TILE_B) + (q >> 2) * P_TILE_B + (q & 3) * 1024),
+        const char* src = pw + ((int64_t)(tk >> 7) * nkb) * (NP * P_TILE_B) + (tk & 127) * 32;
+        const int q = (wave & 1) * 2 * NP + i;
+        __builtin_amdgcn_global_load_lds((glb_vp)(src + offd[i]), (lds_vp)(sm + slot * STAGE_B + (wave >> 1) * (NP * P_TILE_B) + (q >> 2) * P_TILE_B + (q & 3) * 1024),
                                          16, 0, 0);
     };
     const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)sm;
@@ -994,42 +1050,45 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_tn_kernel(const GemmF3
     // lo: token row 4 h + qq (< 8: halves as stored), hi: row 8 + 4 h + qq (halves swapped)
     const uint32_t tlo = (4 * h + qq) * 32 + ((pp >> 1) << 4) + 8 * (pp & 1), thi = (8 + 4 * h + qq) * 32 + (((pp >> 1) ^ 1) << 4) + 8 * (pp & 1);
     const uint32_t fa_lo = lbase + (wm * 4 + g1) * 512 + tlo, fa_hi = lbase + (wm * 4 + g1) * 512 + thi;
-    const uint32_t fb_lo = lbase + 3 * P_TILE_B + (wn * 4 + g1) * 512 + tlo, fb_hi = lbase + 3 * P_TILE_B + (wn * 4 + g1) * 512 + thi;
+    const uint32_t fb_lo = lbase + NP * P_TILE_B + (wn * 4 + g1) * 512 + tlo, fb_hi = lbase + NP * P_TILE_B + (wn * 4 + g1) * 512 + thi;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) dma1(0, 0, i);
+    for (int i = 0; i < 2 * NP; ++i) dma1(0, 0, i);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) dma1(min(1, nst - 1), 1, i);
-    bf16x4 al[2][2][3], ah[2][2][3], bl[2][2][3], bh[2][2][3];      // [register set][block][plane], tokens lo / hi
-#define PT_MFMA(SET, I, J, PA, PB)                                                                                                        \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_shufflevector(al[SET][I][PA], ah[SET][I][PA], 0, 1, 2, 3, 4, 5, 6, 7), \
-                                                        __builtin_shufflevector(bl[SET][J][PB], bh[SET][J][PB], 0, 1, 2, 3, 4, 5, 6, 7), acc[I][J], 0, 0, 0);
-#define PT_PAIR(SET, I, J, T)                                                       \
-    if (T == 0) { PT_MFMA(SET, I, J, 0, 2) PT_MFMA(SET, I, J, 2, 0) }              \
-    else if (T == 1) { PT_MFMA(SET, I, J, 1, 1) PT_MFMA(SET, I, J, 0, 1) }         \
-    else { PT_MFMA(SET, I, J, 1, 0) PT_MFMA(SET, I, J, 0, 0) }
+    for (int i = 0; i < 2 * NP; ++i) dma1(min(1, nst - 1), 1, i);
+    bf16x4 al[2][2][NP], ah[2][2][NP], bl[2][2][NP], bh[2][2][NP];      // [register set][block][plane], tokens lo / hi
     auto step = [&](int st, int slot, auto set_tag, auto first_tag) {
         constexpr int SET = decltype(set_tag)::value;
         constexpr bool FIRST = decltype(first_tag)::value;
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // younger: the 6 pieces of stage st + 1
+        if constexpr (NP == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // younger: the 2 NP pieces of stage st + 1
+        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         acr_barrier_nofence();
         const int rslot = slot == 0 ? 2 : slot - 1;         // (st + 2) % 3
         const int rst = min(st + 2, nst - 1);
-        const uint32_t so = slot * P_STAGE_B;
+        const uint32_t so = slot * STAGE_B;
         const uint32_t a_lo = fa_lo + so, a_hi = fa_hi + so, b_lo = fb_lo + so, b_hi = fb_hi + so;
 #define PT_GROUP(K12)                                                                                                                   \
-        if (!FIRST) { PT_PAIR(SET ^ 1, ((K12) / 6), (((K12) / 3) & 1), ((K12) % 3)) }                                                   \
-        if ((K12) < 6) PL_RDTR(al[SET][(K12) / 3][(K12) % 3], ah[SET][(K12) / 3][(K12) % 3], a_lo, a_hi, ((K12) % 3) * P_TILE_B + ((K12) / 3) * 1024); \
-        else PL_RDTR(bl[SET][((K12) - 6) / 3][(K12) % 3], bh[SET][((K12) - 6) / 3][(K12) % 3], b_lo, b_hi, ((K12) % 3) * P_TILE_B + (((K12) - 6) / 3) * 1024); \
-        if ((K12) & 1) dma1(rst, rslot, (K12) >> 1);                                                                                   \
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr ((K12) < NG) {                                                                                                     \
+            if constexpr (!FIRST) pt_mfmas<FMT, (K12) * NM / NG, ((K12) + 1) * NM / NG>(acc, al[SET ^ 1], ah[SET ^ 1], bl[SET ^ 1], bh[SET ^ 1]); \
+            if constexpr ((K12) < 2 * NP) PL_RDTR(al[SET][(K12) / NP][(K12) % NP], ah[SET][(K12) / NP][(K12) % NP], a_lo, a_hi, ((K12) % NP) * P_TILE_B + ((K12) / NP) * 1024); \
+            else PL_RDTR(bl[SET][((K12) - 2 * NP) / NP][(K12) % NP], bh[SET][((K12) - 2 * NP) / NP][(K12) % NP], b_lo, b_hi, ((K12) % NP) * P_TILE_B + (((K12) - 2 * NP) / NP) * 1024); \
+            if ((K12) & 1) dma1(rst, rslot, (K12) >> 1);                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                                          \
+        }
         PT_GROUP(0) PT_GROUP(1) PT_GROUP(2) PT_GROUP(3) PT_GROUP(4) PT_GROUP(5)
         PT_GROUP(6) PT_GROUP(7) PT_GROUP(8) PT_GROUP(9) PT_GROUP(10) PT_GROUP(11)
 #undef PT_GROUP
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(al[SET][0][0]), "+v"(al[SET][0][1]), "+v"(al[SET][0][2]), "+v"(al[SET][1][0]), "+v"(al[SET][1][1]), "+v"(al[SET][1][2]),
-                       "+v"(ah[SET][0][0]), "+v"(ah[SET][0][1]), "+v"(ah[SET][0][2]), "+v"(ah[SET][1][0]), "+v"(ah[SET][1][1]), "+v"(ah[SET][1][2]),
-                       "+v"(bl[SET][0][0]), "+v"(bl[SET][0][1]), "+v"(bl[SET][0][2]), "+v"(bl[SET][1][0]), "+v"(bl[SET][1][1]), "+v"(bl[SET][1][2]),
-                       "+v"(bh[SET][0][0]), "+v"(bh[SET][0][1]), "+v"(bh[SET][0][2]), "+v"(bh[SET][1][0]), "+v"(bh[SET][1][1]), "+v"(bh[SET][1][2]));
+        if constexpr (NP == 3)
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(al[SET][0][0]), "+v"(al[SET][0][1]), "+v"(al[SET][0][2]), "+v"(al[SET][1][0]), "+v"(al[SET][1][1]), "+v"(al[SET][1][2]),
+                           "+v"(ah[SET][0][0]), "+v"(ah[SET][0][1]), "+v"(ah[SET][0][2]), "+v"(ah[SET][1][0]), "+v"(ah[SET][1][1]), "+v"(ah[SET][1][2]),
+                           "+v"(bl[SET][0][0]), "+v"(bl[SET][0][1]), "+v"(bl[SET][0][2]), "+v"(bl[SET][1][0]), "+v"(bl[SET][1][1]), "+v"(bl[SET][1][2]),
+                           "+v"(bh[SET][0][0]), "+v"(bh[SET][0][1]), "+v"(bh[SET][0][2]), "+v"(bh[SET][1][0]), "+v"(bh[SET][1][1]), "+v"(bh[SET][1][2]));
+        else
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(al[SET][0][0]), "+v"(al[SET][0][1]), "+v"(al[SET][1][0]), "+v"(al[SET][1][1]),
+                           "+v"(ah[SET][0][0]), "+v"(ah[SET][0][1]), "+v"(ah[SET][1][0]), "+v"(ah[SET][1][1]),
+                           "+v"(bl[SET][0][0]), "+v"(bl[SET][0][1]), "+v"(bl[SET][1][0]), "+v"(bl[SET][1][1]),
+                           "+v"(bh[SET][0][0]), "+v"(bh[SET][0][1]), "+v"(bh[SET][1][0]), "+v"(bh[SET][1][1]));
     };
     step(0, 0, std::integral_constant<int, 0>{}, std::true_type{});
     int slot = 1;
@@ -1041,15 +1100,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_tn_kernel(const GemmF3
             slot = slot == 2 ? 0 : slot + 1;
         }
     }
-#define PT_ALL(SET)                                                                                      \
-    PT_PAIR(SET, 0, 0, 0) PT_PAIR(SET, 0, 0, 1) PT_PAIR(SET, 0, 0, 2) PT_PAIR(SET, 0, 1, 0) PT_PAIR(SET, 0, 1, 1) PT_PAIR(SET, 0, 1, 2) \
-    PT_PAIR(SET, 1, 0, 0) PT_PAIR(SET, 1, 0, 1) PT_PAIR(SET, 1, 0, 2) PT_PAIR(SET, 1, 1, 0) PT_PAIR(SET, 1, 1, 1) PT_PAIR(SET, 1, 1, 2)
-    if (nst & 1) { PT_ALL(0) } else { PT_ALL(1) }
-#undef PT_ALL
-#undef PT_PAIR
-#undef PT_MFMA
+    if (nst & 1) pt_mfmas<FMT, 0, NM>(acc, al[0], ah[0], bl[0], bh[0]);
+    else pt_mfmas<FMT, 0, NM>(acc, al[1], ah[1], bl[1], bh[1]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (FMT == 1) h2_unscale(g, acc, m0 + wm * 64, n0 + wn * 64, r, h);
     gemm_f32_finish<true, 3>(g, acc, smem, split, tt, tn, m0, n0, 0, wm, wn, r, h, tid, 0.f, false);
 }
 
@@ -1322,10 +1377,41 @@ __device__ __forceinline__ void planes_split8(const float (&x)[8], bf16x8& p0, b
 // byte offset of the 16-byte chunk (row rr of the tile, contraction half kh) inside a plane of the tiled image
 __device__ __forceinline__ int planes_chunk_off(int rr, int kh) { return rr * 32 + ((kh ^ ((rr >> 3) & 1)) << 4); }
 
+// fp16x2 split of 8 elements with scale exponents e: xs = x 2^e (exact), p0 = fp16(xs), p1 = fp16(xs - p0) (the difference is exact)
+__device__ __forceinline__ void h2_split8(const float (&x)[8], const int (&e)[8], bf16x8& p0, bf16x8& p1) {
+    f16x8 q0, q1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float xs = ldexpf(x[i], e[i]);
+        const _Float16 h0 = (_Float16)xs;
+        q0[i] = h0; q1[i] = (_Float16)(xs - (float)h0);
+    }
+    p0 = __builtin_bit_cast(bf16x8, q0); p1 = __builtin_bit_cast(bf16x8, q1);
+}
+// the planes of one 16-byte chunk in image format FMT (planes P_TILE_B apart): bf16x3, or fp16x2 with exponents e
+template <int FMT>
+__device__ __forceinline__ void planes_write8(char* dst, const float (&v)[8], const int (&e)[8]) {
+    if constexpr (FMT == 0) {
+        bf16x8 p0, p1, p2;
+        planes_split8(v, p0, p1, p2);
+        *reinterpret_cast<bf16x8*>(dst) = p0;
+        *reinterpret_cast<bf16x8*>(dst + P_TILE_B) = p1;
+        *reinterpret_cast<bf16x8*>(dst + 2 * P_TILE_B) = p2;
+    } else {
+        bf16x8 p0, p1;
+        h2_split8(v, e, p0, p1);
+        *reinterpret_cast<bf16x8*>(dst) = p0;
+        *reinterpret_cast<bf16x8*>(dst + P_TILE_B) = p1;
+    }
+}
+
 // tiled image of x[row][k] (pitch ld floats; the operand's rows are x's rows).  Workgroup = row block rb x 4 stages (64 k);
 // thread -> 4 chunks of 8 k: a row's 256 bytes are read by 8 neighbouring threads, a stage's 8 rows x 32 bytes written by 16.
+// FMT 0: bf16x3 image.  FMT 1: fp16x2, exponent ex[row] (row-scaled).  FMT 2: fp16x2, exponent ex[k] (column-scaled).
+template <int FMT>
 __global__ __launch_bounds__(256) void planes_tile_kernel(const float* __restrict__ x, int64_t ld, int rows, int K, int nkb, char* __restrict__ img,
-                                                          float* __restrict__ colpart) {
+                                                          float* __restrict__ colpart, const int* __restrict__ ex) {
+    constexpr int NP = PlanesFmt<FMT == 0 ? 0 : 1>::NP;
     __shared__ float red[32 * 64];
     const int kq = (nkb + 3) >> 2;
     const int rb = blockIdx.x / kq, k0 = (blockIdx.x - rb * kq) << 6;
@@ -1347,12 +1433,10 @@ __global__ __launch_bounds__(256) void planes_tile_kernel(const float* __restric
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) cs[e] += v[e];
-        bf16x8 p0, p1, p2;
-        planes_split8(v, p0, p1, p2);
-        char* dst = img + ((int64_t)rb * nkb + (k >> 4)) * (3 * P_TILE_B) + planes_chunk_off(rr, k8 & 1);
-        *reinterpret_cast<bf16x8*>(dst) = p0;
-        *reinterpret_cast<bf16x8*>(dst + P_TILE_B) = p1;
-        *reinterpret_cast<bf16x8*>(dst + 2 * P_TILE_B) = p2;
+        int ev[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ev[e] = FMT == 1 ? ex[row] : FMT == 2 ? ex[k + e] : 0;
+        planes_write8<FMT == 0 ? 0 : 1>(img + ((int64_t)rb * nkb + (k >> 4)) * (NP * P_TILE_B) + planes_chunk_off(rr, k8 & 1), v, ev);
     }
     if (colpart) {                                          // column sums of this row block (bias gradient part): thread = rows
         const int tid = threadIdx.x;                        // (tid >> 3) + 32 j of the 8 columns 8 (tid & 7) ..; fixed summation order
@@ -1370,9 +1454,11 @@ __global__ __launch_bounds__(256) void planes_tile_kernel(const float* __restric
 // blocks through an fp32 LDS tile (pitch 65: the column reads are conflict-free); thread (c = tid & 63, q = tid >> 6) then
 // holds the 16 contraction elements 16 q .. 16 q + 15 of operand row c0 + c = one whole stage row (32 bytes per plane).
 // colpart (or null): per 64-row block of x the column sums of the block (bias gradient parts, summed in block order by
-// gemm_f32_reduce1_kernel: deterministic).
+// gemm_f32_reduce1_kernel: deterministic).  FMT 0: bf16x3.  FMT 1: fp16x2 with exponent ex[operand row] (row-scaled).
+template <int FMT>
 __global__ __launch_bounds__(256) void planes_tile_t_kernel(const float* __restrict__ x, int64_t ld, int R, int C, int nkb, char* __restrict__ img,
-                                                            float* __restrict__ colpart) {
+                                                            float* __restrict__ colpart, const int* __restrict__ ex) {
+    constexpr int NP = PlanesFmt<FMT>::NP;
     __shared__ float tile[64 * 65];
     __shared__ float red[256];
     const int tid = threadIdx.x;
@@ -1411,15 +1497,90 @@ __global__ __launch_bounds__(256) void planes_tile_t_kernel(const float* __restr
     const int kb = (r0 >> 4) + gq;                          // stage of these 16 contraction elements
     if (kb >= nkb) return;
     const int orow = c0 + c;                                // operand row (rows past C inside the last 128-row block: zeros from the loads above)
-    bf16x8 p0, p1, p2;
-    char* dst = img + ((int64_t)(orow >> 7) * nkb + kb) * (3 * P_TILE_B);
+    char* dst = img + ((int64_t)(orow >> 7) * nkb + kb) * (NP * P_TILE_B);
     const int rr = orow & 127;
-    planes_split8(v0, p0, p1, p2);
-    char* d0 = dst + planes_chunk_off(rr, 0);
-    *reinterpret_cast<bf16x8*>(d0) = p0; *reinterpret_cast<bf16x8*>(d0 + P_TILE_B) = p1; *reinterpret_cast<bf16x8*>(d0 + 2 * P_TILE_B) = p2;
-    planes_split8(v1, p0, p1, p2);
-    char* d1 = dst + planes_chunk_off(rr, 1);
-    *reinterpret_cast<bf16x8*>(d1) = p0; *reinterpret_cast<bf16x8*>(d1 + P_TILE_B) = p1; *reinterpret_cast<bf16x8*>(d1 + 2 * P_TILE_B) = p2;
+    int ev[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ev[e] = FMT == 1 ? ex[orow] : 0;
+    planes_write8<FMT>(dst + planes_chunk_off(rr, 0), v0, ev);
+    planes_write8<FMT>(dst + planes_chunk_off(rr, 1), v1, ev);
+}
+
+// ---- fp16x2 scale exponents (include/acr_hip.h "fp16x2 images") ------------------------------------------------------------------
+// e with max|x| 2^e in [2^14, 2^15) for the largest FINITE |x| of a group; 0 for a group without a finite non-zero value
+__device__ __forceinline__ float h2_absmax(float m, float v) { const float a = fabsf(v); return a <= 3.402823466e38f ? fmaxf(m, a) : m; }
+__device__ __forceinline__ int h2_exp(float m) {
+    if (!(m > 0.f)) return 0;
+    int ex;
+    frexpf(m, &ex);                                         // m = f 2^ex, f in [0.5, 1): m 2^(15 - ex) = f 2^15
+    return 15 - ex;
+}
+// row-scaled: one wave per row of x (rows x K, pitch ld); ex[row] for row < nexp (0 past rows); writes the direction flag
+__global__ __launch_bounds__(256) void h2_rowexp_kernel(const float* __restrict__ x, int64_t ld, int rows, int K, int nexp, int* __restrict__ ex,
+                                                        int* __restrict__ flag, int dir) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x < 4) flag[threadIdx.x] = threadIdx.x == 0 ? dir : 0;
+    if (row >= nexp) return;
+    float m = 0.f;
+    if (row < rows) {
+        const float* p = x + (int64_t)row * ld;
+        const int k4 = K >> 2;
+#pragma unroll 4
+        for (int i = lane; i < k4; i += 64) {
+            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
+            m = h2_absmax(h2_absmax(m, v[0]), v[1]); m = h2_absmax(h2_absmax(m, v[2]), v[3]);
+        }
+        for (int k = 4 * k4 + lane; k < K; k += 64) m = h2_absmax(m, p[k]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0) ex[row] = h2_exp(m);
+}
+// column-scaled, pass 1: per 128-row block rb of x (R x C, pitch ld % 4 == 0, 16-byte aligned) the column maxima part[rb][c].
+// Workgroup = (rb, 256 columns); thread = 4 columns (4 (tid & 63)) x every 4th row from (tid >> 6), float4 loads; the four row
+// quarters are combined through LDS (a maximum: the result does not depend on the order)
+__global__ __launch_bounds__(256) void h2_colmax_kernel(const float* __restrict__ x, int64_t ld, int R, int C, float* __restrict__ part) {
+    __shared__ f32x4 red[256];
+    const int tid = threadIdx.x, rb = blockIdx.x, q = tid >> 6;
+    const int c0 = blockIdx.y * 256 + (tid & 63) * 4, r1 = min(R, rb * 128 + 128);
+    f32x4 m = {0.f, 0.f, 0.f, 0.f};
+    if (c0 + 4 <= C) {
+#pragma unroll 8
+        for (int r = rb * 128 + q; r < r1; r += 4) {
+            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + (int64_t)r * ld + c0));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = h2_absmax(m[e], v[e]);
+        }
+    } else if (c0 < C) {
+        for (int r = rb * 128 + q; r < r1; r += 4)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c0 + e < C) m[e] = h2_absmax(m[e], x[(int64_t)r * ld + c0 + e]);
+    }
+    red[tid] = m;
+    __syncthreads();
+    if (tid < 64) {
+        const f32x4 u = red[tid], v = red[tid + 64], w = red[tid + 128], z = red[tid + 192];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c0 + e < C) part[(int64_t)rb * C + c0 + e] = fmaxf(fmaxf(u[e], v[e]), fmaxf(w[e], z[e]));
+    }
+}
+// pass 2: ex[c] from the nparts row-block maxima (0 for c in [C, nexp)); workgroup = 64 columns, thread (c, q = tid >> 6) takes
+// every 4th part from q, quarters combined through LDS; writes the direction flag
+__global__ __launch_bounds__(256) void h2_colexp_kernel(const float* __restrict__ part, int nparts, int C, int nexp, int* __restrict__ ex,
+                                                        int* __restrict__ flag, int dir) {
+    __shared__ float red[256];
+    const int tid = threadIdx.x, c = blockIdx.x * 64 + (tid & 63), q = tid >> 6;
+    if (blockIdx.x == 0 && tid < 4) flag[tid] = tid == 0 ? dir : 0;
+    float m = 0.f;
+    if (c < C) {
+#pragma unroll 4
+        for (int k = q; k < nparts; k += 4) m = fmaxf(m, part[(int64_t)k * C + c]);
+    }
+    red[tid] = m;
+    __syncthreads();
+    if (tid < 64 && c < nexp) ex[c] = h2_exp(fmaxf(fmaxf(red[tid], red[tid + 64]), fmaxf(red[tid + 128], red[tid + 192])));
 }
 
 // MANY small images in one launch (round 5): the stem's 52 standardised convolution weights need up to two images each per step
@@ -1609,13 +1770,25 @@ static size_t gemm_ws_base_floats(int mode, int M, int N, int K, bool x3 = false
     const TnPlan p = tn_plan(M, N, K);
     return (size_t)p.nsplit * ((size_t)M * N + (size_t)M);
 }
-// Workspace of the pre-split operands (gemm_f32_planes_kernel): behind the slabs, [A planes | B planes | column-sum parts],
-// every region a multiple of 16 bytes.  Off when the plane offsets would not fit 32 bits (the kernel's DMA offsets are ints).
+// fp16x2 images (include/acr_hip.h "fp16x2 images"): [2 tiled fp16 planes][int32 exponents, nexp][int32 flag, 4]
+static int h2_nexp(int rows, int cols) { return max((rows + F_BM - 1) / F_BM, (cols + F_BM - 1) / F_BM) * F_BM; }
+static size_t h2_plane_floats(int rows, int cols) { return (size_t)((rows + F_BM - 1) / F_BM) * ((cols + P_BK - 1) / P_BK) * (2 * P_TILE_B / 4); }
+static size_t h2_floats(int rows, int cols) { return h2_plane_floats(rows, cols) + h2_nexp(rows, cols) + 4; }
+static int* h2_exps(const float* img, int rows, int cols) { return (int*)(img + h2_plane_floats(rows, cols)); }
+// Workspace of the pre-split operands (gemm_f32_planes_kernel): behind the slabs, [A image | B image | column-sum / column-max parts],
+// every region a multiple of 16 bytes.
 struct PlanesPlan { bool on; int nkb; size_t a_fl, b_fl, cs_fl; };
 static PlanesPlan planes_plan(int mode, int math, int M, int N, int K) {
     PlanesPlan p = {false, 0, 0, 0, 0};
-    if (math != ACR_MATH_BF16X3) return p;
+    if (math != ACR_MATH_BF16X3 && math != ACR_MATH_FP16X2) return p;
     p.on = true; p.nkb = (K + P_BK - 1) / P_BK;
+    if (math == ACR_MATH_FP16X2) {                          // TN: column-scaled images of a[K][M], b[K][N]; NT / NN: row-scaled of a, b (resp. b^T)
+        const size_t nrb = (size_t)(K + 127) / 128;
+        p.a_fl = mode == ACR_GEMM_TN ? h2_floats(K, M) : h2_floats(M, K);
+        p.b_fl = mode == ACR_GEMM_TN ? h2_floats(K, N) : h2_floats(N, K);
+        p.cs_fl = mode == ACR_GEMM_NT ? 0 : (nrb * (mode == ACR_GEMM_TN ? max(M, N) : N) + 3) / 4 * 4;
+        return p;
+    }
     if (mode == ACR_GEMM_TN) {                              // images of a[K][M] and b[K][N] as stored: rows = the K tokens
         const size_t nrb = (size_t)(K + 127) / 128;
         p.a_fl = nrb * ((M + P_BK - 1) / P_BK) * (3 * P_TILE_B / 4);
@@ -1651,15 +1824,17 @@ __global__ __launch_bounds__(256) void planes_colsum_kernel(const float* __restr
     }
 }
 // operand rows = x's rows
-static void launch_planes_tile(const float* x, int64_t ld, int rows, int K, int nkb, float* img, float* colpart, hipStream_t st) {
+template <int FMT = 0>
+static void launch_planes_tile(const float* x, int64_t ld, int rows, int K, int nkb, float* img, float* colpart, hipStream_t st, const int* ex = nullptr) {
     const int64_t nb = (int64_t)((rows + F_BM - 1) / F_BM) * ((nkb + 3) / 4);
-    hipLaunchKernelGGL(planes_tile_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, ld, rows, K, nkb, reinterpret_cast<char*>(img), colpart);
+    hipLaunchKernelGGL(planes_tile_kernel<FMT>, dim3((unsigned)nb), dim3(256), 0, st, x, ld, rows, K, nkb, reinterpret_cast<char*>(img), colpart, ex);
 }
 // operand rows = x's C columns, contraction = x's R rows; the row blocks of x cover whole stages up to nkb * 16
-static void launch_planes_tile_t(const float* x, int64_t ld, int R, int C, int nkb, float* img, float* colpart, hipStream_t st) {
+template <int FMT = 0>
+static void launch_planes_tile_t(const float* x, int64_t ld, int R, int C, int nkb, float* img, float* colpart, hipStream_t st, const int* ex = nullptr) {
     const int cpad = (C + F_BM - 1) / F_BM * F_BM;            // all 128 rows of the last row block are written (zeros past C)
     const int64_t nb = (int64_t)((nkb * P_BK + 63) / 64) * (cpad / 64);
-    hipLaunchKernelGGL(planes_tile_t_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, ld, R, C, nkb, reinterpret_cast<char*>(img), colpart);
+    hipLaunchKernelGGL(planes_tile_t_kernel<FMT>, dim3((unsigned)nb), dim3(256), 0, st, x, ld, R, C, nkb, reinterpret_cast<char*>(img), colpart, ex);
 }
 
 // ---- the image API: split-product operands made once, used by several products (include/acr_hip.h "split-product images") ------
@@ -1772,40 +1947,28 @@ extern "C" size_t acr_gemm_x3_ws_floats(int32_t mode, int32_t act, int32_t M, in
     const size_t base = (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4;
     return base + (act == 4 ? ((size_t)((M + F_BM - 1) / F_BM) * N + 3) / 4 * 4 : 0);        // act 4: column-sum parts per tile row
 }
-extern "C" int acr_gemm_x3(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux,
-                           float* c, int64_t ldc, float* c2, float* colsum, int32_t M, int32_t N, int32_t K, float* ws, void* stream) {
-    ACR_CHECK_ARG(a_img && b_img && (c || act == 4), "acr_gemm_x3: null pointer");
-    ACR_CHECK_ARG(M > 0 && N > 0 && K > 0, "acr_gemm_x3: empty problem (M=%d N=%d K=%d)", M, N, K);
-    ACR_CHECK_ARG((mode == ACR_GEMM_NT || mode == ACR_GEMM_TN) && act >= 0 && act <= 4, "acr_gemm_x3: mode must be ACR_GEMM_NT or ACR_GEMM_TN (got %d), act 0..4 (got %d)", mode, act);
-    ACR_CHECK_ARG(!colsum || act == 4, "acr_gemm_x3: colsum comes with act 4 only (the image passes give it otherwise)");
-    ACR_CHECK_ARG(al16(a_img) && al16(b_img) && al16(c) && (ldc % 4) == 0 && (!bias || al16(bias)) && (!aux || (al16(aux) && (ldaux % 4) == 0)) && (!c2 || al16(c2)),
-                  "acr_gemm_x3: pointers must be 16-byte aligned, pitches %% 4 == 0");
-    ACR_CHECK_ARG(!ws || al16(ws), "acr_gemm_x3: ws must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+// the products on images of format FMT (acr_gemm_x3: FMT 0; acr_gemm_h2: FMT 1, exponents ea / eb); arguments checked by the callers
+template <int FMT>
+static int gemm_planes(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux,
+                       float* c, int64_t ldc, float* c2, float* colsum, int32_t M, int32_t N, int32_t K, float* ws, const int* ea, const int* eb,
+                       hipStream_t st) {
     GemmF32Args g;
     g.a = a_img; g.lda = 0; g.b = b_img; g.ldb = 0; g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.c = c; g.ldc = ldc; g.c2 = c2;
-    g.cs = nullptr; g.M = M; g.N = N;
+    g.cs = nullptr; g.M = M; g.N = N; g.ea = ea; g.eb = eb;
     g.K = (K + P_BK - 1) / P_BK * P_BK;                     // the images are zero past K
     g.tiles_m = (M + F_BM - 1) / F_BM; g.tiles_n = (N + F_BN - 1) / F_BN; g.nsplit = 1; g.kps = g.K;
     g.a_zs = g.b_zs = g.c_zs = g.aux_zs = 0; g.k_zs = g.kps; g.ksplit = 1 << 30;
     g.tile0 = 0; g.tiles_launch = g.tiles_m * g.tiles_n;
     g.nkb_a = (M + P_BK - 1) / P_BK; g.nkb_b = (N + P_BK - 1) / P_BK;
     if (mode == ACR_GEMM_TN) {                              // a_img = image of a[K][M], b_img = image of b[K][N] (rows = the K tokens)
-        ACR_CHECK_ARG(act == 0 && !bias && !aux, "acr_gemm_x3: TN takes no epilogue");
-        ACR_CHECK_ARG(ws, "acr_gemm_x3: TN needs the acr_gemm_x3_ws_floats workspace");
-        ACR_CHECK_ARG((M % 4) == 0 && (N % 4) == 0 && ldc == N, "acr_gemm_x3: TN needs M, N %% 4 == 0 and a dense output (ldc == N)");
         const TnPlan p = tn_plan(M, N, K);
         g.nsplit = p.nsplit; g.kps = p.kps; g.k_zs = p.kps;
         g.c = ws; g.ldc = N;
-        hipLaunchKernelGGL(gemm_f32_planes_tn_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n * p.nsplit)), dim3(256), 0, st, g);
+        hipLaunchKernelGGL(gemm_f32_planes_tn_kernel<FMT>, dim3((unsigned)(g.tiles_m * g.tiles_n * p.nsplit)), dim3(256), 0, st, g);
         const int64_t n4 = (int64_t)M * N / 4;
         hipLaunchKernelGGL(gemm_f32_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float*)ws, p.nsplit, n4, c);
-        return acr_check_launch("acr_gemm_x3(TN)");
+        return acr_check_launch(FMT == 0 ? "acr_gemm_x3(TN)" : "acr_gemm_h2(TN)");
     }
-    ACR_CHECK_ARG((act != 1 && act != 3 && act != 4) || c2, "acr_gemm_x3: act 1 / 3 / 4 need c2");
-    ACR_CHECK_ARG((act != 2 && act != 4) || aux, "acr_gemm_x3: act 2 / 4 (GELU') need the saved derivative in aux");
-    ACR_CHECK_ARG(act < 3 || ((N % 8) == 0 && (!aux || (ldaux % 4) == 0)), "acr_gemm_x3: image epilogues need N %% 8 == 0");
-    ACR_CHECK_ARG(act != 4 || !colsum || ws, "acr_gemm_x3: act 4 with colsum needs ws");
     TailPlan tp = gemm_tail_plan(M, N, K, true);
     if (!ws) tp.ntail = 0;
     float* parts = (act == 4 && colsum) ? ws + (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4 : nullptr;
@@ -1813,16 +1976,18 @@ extern "C" int acr_gemm_x3(int32_t mode, int32_t act, const float* a_img, const 
     g.tiles_launch -= tp.ntail;
     if (g.tiles_launch > 0) {
         const dim3 grid((unsigned)g.tiles_launch);
-        if (act == 0) hipLaunchKernelGGL((gemm_f32_planes_kernel<0>), grid, dim3(256), 0, st, g);
-        else if (act == 1) hipLaunchKernelGGL((gemm_f32_planes_kernel<1>), grid, dim3(256), 0, st, g);
-        else if (act == 2) hipLaunchKernelGGL((gemm_f32_planes_kernel<2>), grid, dim3(256), 0, st, g);
-        else if (act == 3) hipLaunchKernelGGL((gemm_f32_planes_kernel<5>), grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((gemm_f32_planes_kernel<6>), grid, dim3(256), 0, st, g);
+        if (act == 0) hipLaunchKernelGGL((gemm_f32_planes_kernel<0, FMT>), grid, dim3(256), 0, st, g);
+        else if (act == 1) hipLaunchKernelGGL((gemm_f32_planes_kernel<1, FMT>), grid, dim3(256), 0, st, g);
+        else if (act == 2) hipLaunchKernelGGL((gemm_f32_planes_kernel<2, FMT>), grid, dim3(256), 0, st, g);
+        else if constexpr (FMT == 0) {
+            if (act == 3) hipLaunchKernelGGL((gemm_f32_planes_kernel<5>), grid, dim3(256), 0, st, g);
+            else hipLaunchKernelGGL((gemm_f32_planes_kernel<6>), grid, dim3(256), 0, st, g);
+        }
     }
     if (tp.ntail) {                                         // the tail tiles, K-split into slabs, and their epilogue (gemm_tail_plan)
         GemmF32Args gt = g;
         gt.tile0 = g.tiles_launch; gt.tiles_launch = tp.ntail; gt.nsplit = tp.nsplit; gt.kps = tp.kps; gt.k_zs = tp.kps; gt.c = ws;
-        hipLaunchKernelGGL((gemm_f32_planes_kernel<4>), dim3((unsigned)(tp.ntail * tp.nsplit)), dim3(256), 0, st, gt);
+        hipLaunchKernelGGL((gemm_f32_planes_kernel<4, FMT>), dim3((unsigned)(tp.ntail * tp.nsplit)), dim3(256), 0, st, gt);
         GemmF32Args ge = g;
         ge.tile0 = gt.tile0;
         const dim3 egrid((unsigned)(tp.ntail * 16));
@@ -1833,7 +1998,135 @@ extern "C" int acr_gemm_x3(int32_t mode, int32_t act, const float* a_img, const 
         else hipLaunchKernelGGL((gemm_x3_tail_image_kernel<6>), dim3((unsigned)tp.ntail), dim3(256), 0, st, ge, (const float*)ws, tp.ntail, tp.nsplit);
     }
     if (parts) hipLaunchKernelGGL(planes_colsum_kernel, dim3((N + 15) / 16), dim3(256), 0, st, (const float*)parts, g.tiles_m, N, colsum);
-    return acr_check_launch("acr_gemm_x3");
+    return acr_check_launch(FMT == 0 ? "acr_gemm_x3" : "acr_gemm_h2");
+}
+extern "C" int acr_gemm_x3(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux,
+                           float* c, int64_t ldc, float* c2, float* colsum, int32_t M, int32_t N, int32_t K, float* ws, void* stream) {
+    ACR_CHECK_ARG(a_img && b_img && (c || act == 4), "acr_gemm_x3: null pointer");
+    ACR_CHECK_ARG(M > 0 && N > 0 && K > 0, "acr_gemm_x3: empty problem (M=%d N=%d K=%d)", M, N, K);
+    ACR_CHECK_ARG((mode == ACR_GEMM_NT || mode == ACR_GEMM_TN) && act >= 0 && act <= 4, "acr_gemm_x3: mode must be ACR_GEMM_NT or ACR_GEMM_TN (got %d), act 0..4 (got %d)", mode, act);
+    ACR_CHECK_ARG(!colsum || act == 4, "acr_gemm_x3: colsum comes with act 4 only (the image passes give it otherwise)");
+    ACR_CHECK_ARG(al16(a_img) && al16(b_img) && al16(c) && (ldc % 4) == 0 && (!bias || al16(bias)) && (!aux || (al16(aux) && (ldaux % 4) == 0)) && (!c2 || al16(c2)),
+                  "acr_gemm_x3: pointers must be 16-byte aligned, pitches %% 4 == 0");
+    ACR_CHECK_ARG(!ws || al16(ws), "acr_gemm_x3: ws must be 16-byte aligned");
+    if (mode == ACR_GEMM_TN) {
+        ACR_CHECK_ARG(act == 0 && !bias && !aux, "acr_gemm_x3: TN takes no epilogue");
+        ACR_CHECK_ARG(ws, "acr_gemm_x3: TN needs the acr_gemm_x3_ws_floats workspace");
+        ACR_CHECK_ARG((M % 4) == 0 && (N % 4) == 0 && ldc == N, "acr_gemm_x3: TN needs M, N %% 4 == 0 and a dense output (ldc == N)");
+    } else {
+        ACR_CHECK_ARG((act != 1 && act != 3 && act != 4) || c2, "acr_gemm_x3: act 1 / 3 / 4 need c2");
+        ACR_CHECK_ARG((act != 2 && act != 4) || aux, "acr_gemm_x3: act 2 / 4 (GELU') need the saved derivative in aux");
+        ACR_CHECK_ARG(act < 3 || ((N % 8) == 0 && (!aux || (ldaux % 4) == 0)), "acr_gemm_x3: image epilogues need N %% 8 == 0");
+        ACR_CHECK_ARG(act != 4 || !colsum || ws, "acr_gemm_x3: act 4 with colsum needs ws");
+    }
+    return gemm_planes<0>(mode, act, a_img, b_img, bias, aux, ldaux, c, ldc, c2, colsum, M, N, K, ws, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// ---- fp16x2 images ------------------------------------------------------------------------------------------------------------------
+extern "C" size_t acr_h2_image_floats(int32_t rows, int32_t cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    return h2_floats(rows, cols);
+}
+extern "C" size_t acr_h2_ws_floats(int32_t rows, int32_t cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    return (size_t)((rows + F_BM - 1) / F_BM) * cols;
+}
+// image -> scale direction (ACR_H2_ROWS / ACR_H2_COLS) of the last acr_h2_image* call that wrote it: acr_gemm_h2 checks an image's
+// direction against its mode without reading the device-side flag (no host synchronisation)
+static std::mutex h2_reg_mu;
+static std::unordered_map<const void*, int> h2_reg;
+static void h2_record(const void* img, int dir) {
+    std::lock_guard<std::mutex> lk(h2_reg_mu);
+    h2_reg[img] = dir;
+}
+static int h2_recorded(const void* img) {
+    std::lock_guard<std::mutex> lk(h2_reg_mu);
+    const auto it = h2_reg.find(img);
+    return it == h2_reg.end() ? -1 : it->second;
+}
+// row-scaled image of x (rows x cols): one exponent per row; colsum (or null) = x's column sums, parts in ws
+static void h2_image_rows(const float* x, int64_t ld, int rows, int cols, float* img, float* colsum, float* ws, hipStream_t st) {
+    const int nexp = h2_nexp(rows, cols);
+    int* ex = h2_exps(img, rows, cols);
+    hipLaunchKernelGGL(h2_rowexp_kernel, dim3((unsigned)((nexp + 3) / 4)), dim3(256), 0, st, x, ld, rows, cols, nexp, ex, ex + nexp, (int)ACR_H2_ROWS);
+    launch_planes_tile<1>(x, ld, rows, cols, (cols + P_BK - 1) / P_BK, img, colsum ? ws : nullptr, st, ex);
+    if (colsum)
+        hipLaunchKernelGGL(planes_colsum_kernel, dim3((cols + 15) / 16), dim3(256), 0, st, (const float*)ws, (rows + F_BM - 1) / F_BM, cols, colsum);
+}
+// column-scaled image of x (rows x cols, the contraction over rows: a TN operand): one exponent per column.  ws holds the
+// per-row-block column maxima, then (colsum) the column-sum parts
+static void h2_image_cols(const float* x, int64_t ld, int rows, int cols, float* img, float* colsum, float* ws, hipStream_t st) {
+    const int nexp = h2_nexp(rows, cols), nrb = (rows + F_BM - 1) / F_BM;
+    int* ex = h2_exps(img, rows, cols);
+    hipLaunchKernelGGL(h2_colmax_kernel, dim3((unsigned)nrb, (unsigned)((cols + 255) / 256)), dim3(256), 0, st, x, ld, rows, cols, ws);
+    hipLaunchKernelGGL(h2_colexp_kernel, dim3((unsigned)((nexp + 63) / 64)), dim3(256), 0, st, (const float*)ws, nrb, cols, nexp, ex, ex + nexp,
+                       (int)ACR_H2_COLS);
+    launch_planes_tile<2>(x, ld, rows, cols, (cols + P_BK - 1) / P_BK, img, colsum ? ws : nullptr, st, ex);
+    if (colsum)
+        hipLaunchKernelGGL(planes_colsum_kernel, dim3((cols + 15) / 16), dim3(256), 0, st, (const float*)ws, nrb, cols, colsum);
+}
+// row-scaled image of x^T (x: rows x cols; operand rows = x's columns): one exponent per column of x; ws: the column maxima parts
+static void h2_image_t(const float* x, int64_t ld, int rows, int cols, float* img, float* ws, hipStream_t st) {
+    const int nexp = h2_nexp(cols, rows), nrb = (rows + F_BM - 1) / F_BM;
+    int* ex = h2_exps(img, cols, rows);
+    hipLaunchKernelGGL(h2_colmax_kernel, dim3((unsigned)nrb, (unsigned)((cols + 255) / 256)), dim3(256), 0, st, x, ld, rows, cols, ws);
+    hipLaunchKernelGGL(h2_colexp_kernel, dim3((unsigned)((nexp + 63) / 64)), dim3(256), 0, st, (const float*)ws, nrb, cols, nexp, ex, ex + nexp,
+                       (int)ACR_H2_ROWS);
+    launch_planes_tile_t<1>(x, ld, rows, cols, (rows + P_BK - 1) / P_BK, img, nullptr, st, ex);
+}
+#define H2_IMAGE_ARGS(what)                                                                                                                  \
+    ACR_CHECK_ARG(x && image, what ": null pointer");                                                                                        \
+    ACR_CHECK_ARG(rows > 0 && cols > 0 && ld >= cols, what ": bad shape (rows=%d cols=%d ld=%lld)", rows, cols, (long long)ld);               \
+    ACR_CHECK_ARG(al16(x) && al16(image) && (ld % 4) == 0 && (!ws || al16(ws)), what ": x, image and ws must be 16-byte aligned, ld %% 4 == 0")
+extern "C" int acr_h2_image(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, float* colsum, float* ws, void* stream) {
+    H2_IMAGE_ARGS("acr_h2_image");
+    ACR_CHECK_ARG(!colsum || ws, "acr_h2_image: colsum needs ws (acr_h2_ws_floats)");
+    h2_image_rows(x, ld, rows, cols, image, colsum, ws, (hipStream_t)stream);
+    h2_record(image, ACR_H2_ROWS);
+    return acr_check_launch("acr_h2_image");
+}
+extern "C" int acr_h2_image_cols(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, float* colsum, float* ws, void* stream) {
+    H2_IMAGE_ARGS("acr_h2_image_cols");
+    ACR_CHECK_ARG(ws, "acr_h2_image_cols: needs ws (acr_h2_ws_floats)");
+    h2_image_cols(x, ld, rows, cols, image, colsum, ws, (hipStream_t)stream);
+    h2_record(image, ACR_H2_COLS);
+    return acr_check_launch("acr_h2_image_cols");
+}
+extern "C" int acr_h2_image_t(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, float* ws, void* stream) {
+    H2_IMAGE_ARGS("acr_h2_image_t");
+    ACR_CHECK_ARG(ws, "acr_h2_image_t: needs ws (acr_h2_ws_floats)");
+    h2_image_t(x, ld, rows, cols, image, ws, (hipStream_t)stream);
+    h2_record(image, ACR_H2_ROWS);
+    return acr_check_launch("acr_h2_image_t");
+}
+#undef H2_IMAGE_ARGS
+extern "C" size_t acr_gemm_h2_ws_floats(int32_t mode, int32_t act, int32_t M, int32_t N, int32_t K) {
+    (void)act;
+    if (mode != ACR_GEMM_NT && mode != ACR_GEMM_TN) return 0;
+    return (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4;
+}
+extern "C" int acr_gemm_h2(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux,
+                           float* c, int64_t ldc, float* c2, int32_t M, int32_t N, int32_t K, float* ws, void* stream) {
+    ACR_CHECK_ARG(a_img && b_img && c, "acr_gemm_h2: null pointer");
+    ACR_CHECK_ARG(M > 0 && N > 0 && K > 0, "acr_gemm_h2: empty problem (M=%d N=%d K=%d)", M, N, K);
+    ACR_CHECK_ARG((mode == ACR_GEMM_NT || mode == ACR_GEMM_TN) && act >= 0 && act <= 2, "acr_gemm_h2: mode must be ACR_GEMM_NT or ACR_GEMM_TN (got %d), act 0..2 (got %d)", mode, act);
+    ACR_CHECK_ARG(al16(a_img) && al16(b_img) && al16(c) && (ldc % 4) == 0 && (!bias || al16(bias)) && (!aux || (al16(aux) && (ldaux % 4) == 0)) && (!c2 || al16(c2)) && (!ws || al16(ws)),
+                  "acr_gemm_h2: pointers must be 16-byte aligned, pitches %% 4 == 0");
+    const int want = mode == ACR_GEMM_NT ? ACR_H2_ROWS : ACR_H2_COLS;
+    ACR_CHECK_ARG(h2_recorded(a_img) == want && h2_recorded(b_img) == want,
+                  "acr_gemm_h2: %s needs %s-scaled images (acr_h2_image%s)", mode == ACR_GEMM_NT ? "NT" : "TN", want == ACR_H2_ROWS ? "row" : "column",
+                  want == ACR_H2_ROWS ? " / acr_h2_image_t" : "_cols");
+    if (mode == ACR_GEMM_TN) {
+        ACR_CHECK_ARG(act == 0 && !bias && !aux && !c2, "acr_gemm_h2: TN takes no epilogue");
+        ACR_CHECK_ARG(ws, "acr_gemm_h2: TN needs the acr_gemm_h2_ws_floats workspace");
+        ACR_CHECK_ARG((M % 4) == 0 && (N % 4) == 0 && ldc == N, "acr_gemm_h2: TN needs M, N %% 4 == 0 and a dense output (ldc == N)");
+        return gemm_planes<1>(mode, 0, a_img, b_img, nullptr, nullptr, 0, c, ldc, nullptr, nullptr, M, N, K, ws, h2_exps(a_img, K, M), h2_exps(b_img, K, N),
+                              (hipStream_t)stream);
+    }
+    ACR_CHECK_ARG(act != 1 || c2, "acr_gemm_h2: act 1 needs c2");
+    ACR_CHECK_ARG(act != 2 || aux, "acr_gemm_h2: act 2 (GELU') needs the saved derivative in aux");
+    return gemm_planes<1>(mode, act, a_img, b_img, bias, aux, ldaux, c, ldc, c2, nullptr, M, N, K, ws, h2_exps(a_img, M, K), h2_exps(b_img, N, K),
+                          (hipStream_t)stream);
 }
 
 extern "C" int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float* a, int64_t lda, const float* b, int64_t ldb, const float* bias,
@@ -1842,7 +2135,7 @@ extern "C" int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float
     ACR_CHECK_ARG(a && b && c, "acr_gemm_f32: null pointer");
     ACR_CHECK_ARG(M > 0 && N > 0 && K > 0, "acr_gemm_f32: empty problem (M=%d N=%d K=%d)", M, N, K);
     ACR_CHECK_ARG(mode >= ACR_GEMM_NT && mode <= ACR_GEMM_TN && act >= 0 && act <= 2, "acr_gemm_f32: bad mode %d / act %d", mode, act);
-    ACR_CHECK_ARG(math == ACR_MATH_F32 || math == ACR_MATH_BF16X3, "acr_gemm_f32: bad math %d", math);
+    ACR_CHECK_ARG(math == ACR_MATH_F32 || math == ACR_MATH_BF16X3 || math == ACR_MATH_FP16X2, "acr_gemm_f32: bad math %d", math);
     ACR_CHECK_ARG(al16(a) && al16(b) && (lda % 4) == 0 && (ldb % 4) == 0, "acr_gemm_f32: operands must be 16-byte aligned with pitches %% 4 == 0");
     hipStream_t st = (hipStream_t)stream;
     GemmF32Args g;
@@ -1862,6 +2155,15 @@ extern "C" int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float
         g.c = ws; g.ldc = N;
         g.cs = colsum ? ws + (size_t)p.nsplit * M * N : nullptr;
         const PlanesPlan pl = planes_plan(mode, math, M, N, K);
+        if (pl.on && math == ACR_MATH_FP16X2) {             // column-scaled images of both operands (+ a's column sums), then the product
+            ACR_CHECK_ARG(al16(ws), "acr_gemm_f32: ws must be 16-byte aligned");
+            float* pa = ws + (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4;
+            float* pb = pa + pl.a_fl;
+            float* cw = pb + pl.b_fl;
+            h2_image_cols(a, lda, K, M, pa, colsum, cw, st);
+            h2_image_cols(b, ldb, K, N, pb, nullptr, cw, st);
+            return gemm_planes<1>(ACR_GEMM_TN, 0, pa, pb, nullptr, nullptr, 0, c, ldc, nullptr, nullptr, M, N, K, ws, h2_exps(pa, K, M), h2_exps(pb, K, N), st);
+        }
         if (pl.on) {                                        // both operands split once into images, then the product on the images
             float* wp = ws + (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4;
             float* pa = wp;
@@ -1904,6 +2206,15 @@ extern "C" int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float
         grid = dim3((unsigned)g.tiles_launch);
     }
     const PlanesPlan pl = planes_plan(mode, math, M, N, K);
+    if (math == ACR_MATH_FP16X2) {                          // row-scaled images of a and b (NN: of b^T), then the product; no other way
+        ACR_CHECK_ARG(ws && al16(ws) && vec_ok, "acr_gemm_f32: fp16x2 needs the acr_gemm_f32_ws_floats workspace (16-byte aligned) and 16-byte aligned c / bias / aux / c2");
+        float* pa = ws + (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4;
+        float* pb = pa + pl.a_fl;
+        h2_image_rows(a, lda, M, K, pa, nullptr, nullptr, st);
+        if (mode == ACR_GEMM_NT) h2_image_rows(b, ldb, N, K, pb, nullptr, nullptr, st);
+        else h2_image_t(b, ldb, K, N, pb, pb + pl.b_fl, st);
+        return gemm_planes<1>(ACR_GEMM_NT, act, pa, pb, bias, aux, ldaux, c, ldc, c2, nullptr, M, N, K, ws, h2_exps(pa, M, K), h2_exps(pb, N, K), st);
+    }
     if (pl.on && ws && al16(ws) && vec_ok) {                // both operands split once into images, then the product on the images
         float* wp = ws + (gemm_ws_base_floats(mode, M, N, K, true) + 3) / 4 * 4;
         float* pa = wp;
@@ -2014,6 +2325,10 @@ extern "C" int acr_conv1x1_f32(int32_t math, const float* w, int32_t w_transpose
     g.nsplit = nsamp;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n * nsamp));
     const bool dma = (cin % F_BK) == 0;
+    if (math == ACR_MATH_FP16X2) {
+        acr_set_error("acr_conv1x1_f32: ACR_MATH_FP16X2 is built for the block Linears only (acr_gemm_f32)");
+        return ACR_ERR_UNSUPPORTED;
+    }
     ACR_CHECK_ARG(math == ACR_MATH_F32 || math == ACR_MATH_BF16X3, "acr_conv1x1_f32: bad math %d", math);
     const bool split = dma && math == ACR_MATH_BF16X3;
     int kps = 0;
@@ -2112,6 +2427,10 @@ extern "C" int acr_conv1x1_wgrad_f32(int32_t math, const float* dy, const float*
     g.k_zs = g.kps;
     g.nsplit = nsamp * ks;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n * g.nsplit));
+    if (math == ACR_MATH_FP16X2) {
+        acr_set_error("acr_conv1x1_wgrad_f32: ACR_MATH_FP16X2 is built for the block Linears only (acr_gemm_f32)");
+        return ACR_ERR_UNSUPPORTED;
+    }
     ACR_CHECK_ARG(math == ACR_MATH_F32 || math == ACR_MATH_BF16X3, "acr_conv1x1_wgrad_f32: bad math %d", math);
     // the split-product kernel advances in 16-deep stages: pixel counts that are multiples of 16 suffice (28 x 28 = 784 = 49 x 16
     // took the register-staged exact kernel before: 2.6 ms of the f32_split step)

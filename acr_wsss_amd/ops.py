@@ -540,7 +540,8 @@ GEMM_MODES = {"nt": 0, "nn": 1, "tn": 2}
 def gemm_f32_raw(mode, a, b, c, bias=None, aux=None, act=0, c2=None, colsum=None, math=0):
     """c = op(a) op(b) through acr_gemm_f32 (see include/acr_hip.h): 'nt' c[M,N] = a[M,K] b[N,K]^T, 'nn' c = a[M,K] b[K,N],
     'tn' c = a[K,M]^T b[K,N] (+ colsum[M] = column sums of a).  fp32, unit inner strides.  ``math``: _lib.MATH code (0 = exact-fp32
-    MFMA, 1 = six bf16-MFMA terms of a three-way operand split), a per-call argument."""
+    MFMA, 1 = six bf16-MFMA terms of a three-way operand split, 2 = three fp16-MFMA terms of a scaled two-piece split made in
+    the call's workspace -- the fp16x2 Linears of LinearF32Fn / MlpF32Fn), a per-call argument."""
     lib = L.load()
     md = GEMM_MODES[mode]
     M, N = c.shape
@@ -711,7 +712,9 @@ def linear_f32_usable(x, weight):
 
 class LinearF32Fn(Function):
     """y = x W^T + b (+ resid) in fp32 on acr_gemm_f32: forward NT, input gradient NN (W as stored), weight + bias gradient
-    in one TN sweep over dy (models/vision_transformer.py:200,212 and their autograd backward)."""
+    in one TN sweep over dy (models/vision_transformer.py:200,212 and their autograd backward).  math 2 (fp16x2) takes the
+    per-call path: every product splits its operands in its own workspace (row images of x / dy and of W resp. W^T, column
+    images of dy and x for dW; db from the dy split pass), so no image is cached across calls or shared with math 1."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, resid, owner=None, math=0, x_image=None):

@@ -49,8 +49,20 @@ typedef enum acr_dtype { ACR_F32 = 0, ACR_BF16 = 1, ACR_BF16_F32MATH = 2, ACR_F3
  *   bits = all of an fp32 mantissa), a.b ~ a0b0 + a0b1 + a1b0 + a1b1 + a0b2 + a2b0 on v_mfma_f32_32x32x16_bf16 (the dropped
  *   terms are <= 2^-24 |a.b|); every bf16 x bf16 product is exact in fp32 and the sums accumulate in fp32.  Same tensors,
  *   layouts, epilogues and determinism as ACR_MATH_F32; as accurate against float64 as the fp32 FMA chain
- *   (tests/test_kernels_gpu.py::test_split_math_adversarial_operands).  Peak: bf16 MFMA peak / 6 = 417 TF-equivalent. */
-typedef enum acr_math { ACR_MATH_F32 = 0, ACR_MATH_BF16X3 = 1 } acr_math;
+ *   (tests/test_kernels_gpu.py::test_split_math_adversarial_operands).  Peak: bf16 MFMA peak / 6 = 417 TF-equivalent.
+ * ACR_MATH_FP16X2 (opt-in, narrower: 22 significand bits per operand instead of 24): every operand group -- a row of an NT / NN
+ *   operand, a column of a TN operand, i.e. one NON-contracted index -- gets an exact power-of-two scale 2^e with
+ *   max|finite x| 2^e in [2^14, 2^15) (e = 0 for an all-zero group), and x 2^e = p0 + p1 with p0 = fp16(x 2^e),
+ *   p1 = fp16(x 2^e - p0) (ldexp scaling, never a float factor); a.b = ldexp(sum(a0b0 + a0b1 + a1b0), -(e_a + e_b)) on
+ *   v_mfma_f32_32x32x16_f16 (same rate and lane maps as the bf16 form), products exact in fp32, fp32 accumulate.  Per element
+ *   |x - (p0 + p1) 2^-e| <= ACR_FP16X2_REL |x| + ACR_FP16X2_FLOOR max|group| (the floor: half of fp16's smallest subnormal
+ *   2^-24 in units where the group maximum is >= 2^14).  A NaN operand element stays NaN; an inf element becomes NaN (its
+ *   second piece is inf - inf) -- never a finite result; groups without a non-finite element are unaffected.  No atomics,
+ *   fixed-order reductions, no host synchronisation.  Accepted by acr_gemm_f32 only (and the fp16x2 image calls below); the
+ *   1x1 / 3x3 convolution entries return ACR_ERR_UNSUPPORTED for it, and attention has no fp16x2 dtype. */
+typedef enum acr_math { ACR_MATH_F32 = 0, ACR_MATH_BF16X3 = 1, ACR_MATH_FP16X2 = 2 } acr_math;
+#define ACR_FP16X2_REL 2.384185791015625e-07      /* 2^-22 */
+#define ACR_FP16X2_FLOOR 1.8189894035458565e-12   /* 2^-39 */
 
 typedef enum acr_getam_func {   /* DPT/ACR.py:189-205 */
     ACR_GETAM_GRAD = 0, ACR_GETAM_CAM_GRAD = 1, ACR_GETAM_GRAD_S = 2, ACR_GETAM_CAM_GRAD_S = 3
@@ -188,7 +200,9 @@ int acr_linear_dgelu_bf16(const void* a, int64_t lda, const void* w, int64_t ldw
  * ws: caller-owned scratch of acr_gemm_f32_ws_floats(mode, math, M, N, K) floats (TN: the split slabs; NT / NN: slabs for the
  * K-split tail tiles, 0 when the tile count needs none -- ws may then be NULL; without ws the product runs unsplit.
  * math = ACR_MATH_BF16X3 adds the bf16 planes both operands are split into once per call (csrc/gemm_f32.hip
- * gemm_f32_planes_kernel); with ws == NULL the operand tiles are split inside the GEMM kernel instead, same results). */
+ * gemm_f32_planes_kernel); with ws == NULL the operand tiles are split inside the GEMM kernel instead, same results).
+ * math = ACR_MATH_FP16X2 adds the fp16x2 images of both operands (row-scaled for NT / NN, column-scaled for TN) and requires ws;
+ * it has no other way to run (ACR_ERR_INVALID without ws). */
 typedef enum acr_gemm_mode { ACR_GEMM_NT = 0, ACR_GEMM_NN = 1, ACR_GEMM_TN = 2 } acr_gemm_mode;
 size_t acr_gemm_f32_ws_floats(int32_t mode, int32_t math, int32_t M, int32_t N, int32_t K);
 int acr_gemm_f32(int32_t mode, int32_t math, int32_t act, const float* a, int64_t lda, const float* b, int64_t ldb, const float* bias,
@@ -276,6 +290,31 @@ size_t acr_gemm_x3_ws_floats(int32_t mode, int32_t act, int32_t M, int32_t N, in
 int acr_x3_image_many(const void* descs, const int32_t* blk, int32_t nwg, void* stream);
 int acr_gemm_x3(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux, float* c,
                 int64_t ldc, float* c2, float* colsum, int32_t M, int32_t N, int32_t K, float* ws, void* stream);
+
+/* ---- fp16x2 images: operands of acr_math ACR_MATH_FP16X2 products, made once and used by several products ---------------------
+ * Layout, in floats: the two fp16 planes of x[rows][cols] (x 2^e), tiled [128 rows][16 cols] as the split-product images above
+ * (zero outside the matrix); then nexp = 128 max(ceil(rows / 128), ceil(cols / 128)) int32 exponents e along the scaled
+ * dimension (0 past its end); then 4 int32, the first of which is the scale direction (acr_h2_dir).
+ *   acr_h2_image_floats(rows, cols): size of an image in floats.
+ *   acr_h2_ws_floats(rows, cols): scratch of the calls below (per-128-row-block column maxima / column-sum parts).
+ *   acr_h2_image: ROW-scaled image of x (pitch ld): the operand of ACR_GEMM_NT.  colsum (nullable, (cols)) = x's column sums
+ *                 (through ws, required with colsum).
+ *   acr_h2_image_cols: COLUMN-scaled image of x (rows = the contraction): the operand of ACR_GEMM_TN.  ws required; colsum as above.
+ *   acr_h2_image_t: ROW-scaled image of x^T (a (cols) x (rows) matrix, one exponent per column of x): a weight's image for dx.
+ *                 ws required.
+ *   acr_gemm_h2: c[M,N] from images as acr_gemm_x3 (NT: act 0, 1 (c2 = GELU(h)), 2; TN: act 0), K-split tails and workspace
+ *                (acr_gemm_h2_ws_floats) as there.  An image whose scale direction does not match the mode (NT: rows, TN:
+ *                columns) -- as recorded on the host when an acr_h2_image* call last wrote that address -- is refused with
+ *                ACR_ERR_INVALID. */
+typedef enum acr_h2_dir { ACR_H2_ROWS = 0, ACR_H2_COLS = 1 } acr_h2_dir;
+size_t acr_h2_image_floats(int32_t rows, int32_t cols);
+size_t acr_h2_ws_floats(int32_t rows, int32_t cols);
+int acr_h2_image(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, float* colsum, float* ws, void* stream);
+int acr_h2_image_cols(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, float* colsum, float* ws, void* stream);
+int acr_h2_image_t(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, float* ws, void* stream);
+size_t acr_gemm_h2_ws_floats(int32_t mode, int32_t act, int32_t M, int32_t N, int32_t K);
+int acr_gemm_h2(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux, float* c,
+                int64_t ldc, float* c2, int32_t M, int32_t N, int32_t K, float* ws, void* stream);
 
 /* ---- 3x3 stride-1 SAME convolutions of the stem's bottlenecks (models/resnetv2.py:171-216 `conv2`; std_conv.py:40-65) in NCHW fp32
  * as implicit GEMMs with split products on the bf16 MFMA (math = ACR_MATH_BF16X3 only: ACR_ERR_UNSUPPORTED otherwise -- the
