@@ -65,9 +65,18 @@ def test_consistency_full_size_is_a_mean_over_samples():
     """The loss at BASELINE size (16 images x 2 views, 12 layers, T = 785: a 946 MB stack) through a size-independent property:
     both terms are means over equally sized per-sample blocks, so they equal the mean of the 16 one-sample results, and sample
     i's gradient is 1/16 of its one-sample gradient (checked on the first and the last sample)."""
+    _consistency_full_size_case(16, 28)
+
+
+def test_consistency_full_size_coco_is_a_mean_over_samples():
+    """The same property at COCO 512^2 (BASELINE configs[4]): 8 images x 2 views, T = 1025, p = 32."""
+    _consistency_full_size_case(8, 32)
+
+
+def _consistency_full_size_case(B, p):
     from acr_wsss_amd import ops
     dev = _dev()
-    B, L, p = 16, 12, 28
+    L = 12
     T = p * p + 1
     g = torch.Generator(device="cpu").manual_seed(5)
     a = torch.rand(2 * B, L, T, T, generator=g).to(dev).requires_grad_(True)
@@ -186,7 +195,8 @@ def test_attention_bf16(B, T, H, with_g, f32math):
 
 
 @pytest.mark.parametrize("B,T,dtype,math", [(32, 785, torch.float32, 0), (32, 785, torch.float32, 1), (32, 785, torch.bfloat16, 0),
-                                             (16, 2305, torch.float32, 0), (16, 2305, torch.float32, 1)])
+                                             (16, 2305, torch.float32, 0), (16, 2305, torch.float32, 1),
+                                             (16, 1025, torch.float32, 0), (16, 1025, torch.float32, 1)])      # COCO 512^2
 def test_attention_full_size_is_per_sample(B, T, dtype, math):
     """BASELINE-size launches (32 views x 12 heads x 785 tokens: one training step; 16 samples x 2305 tokens: eight images at scale 2,
     a 4 GB score buffer, byte offsets beyond 2^32) checked through a size-independent property: attention is per sample, so the
