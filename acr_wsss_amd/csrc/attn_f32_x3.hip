@@ -24,7 +24,7 @@
 // One image serves rowop (contraction over the 64 columns) and accop (contraction over the 32 rows).
 #include <type_traits>
 
-#include "acr_common.h"
+#include "acr_split.h"
 #include "attn_f32.h"
 #include "attn_f32_sres_tails.h"
 
@@ -32,7 +32,7 @@ typedef __bf16 bf16_t;
 typedef __attribute__((address_space(3))) void* x3_lds_vp;
 typedef const __attribute__((address_space(1))) void* x3_glb_vp;
 
-#define X3_PLANE_B 4096                    // bytes of one plane image of a 32-row tile
+#define X3_PLANE_B (32 * 64 * 2)           // bytes of one plane image of a 32-row x 64-column tile
 #define X3_TILE_B (3 * X3_PLANE_B)         // one operand tile: three planes
 #define X3_SLOT_B (2 * X3_TILE_B)          // one ring slot: two operand tiles
 #define X3_SB_FLOATS 1024                  // one 32 x 32 score block (layout: attn_f32_sres.hip)
@@ -80,34 +80,6 @@ __device__ __forceinline__ int x3_swz(int row) {
     return x ^ ((x & 1) << 2);
 }
 
-// ---- a = a0 + a1 + a2 --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void x3_split1(float x, bf16_t& h0, bf16_t& h1, bf16_t& h2) {
-    h0 = (bf16_t)x;
-    const float r1 = x - (float)h0;
-    h1 = (bf16_t)r1;
-    const float r2 = r1 - (float)h1;
-    h2 = (bf16_t)r2;
-}
-// accumulator registers 8S .. 8S+7 -> the three fragments of k-step S
-template <int S>
-__device__ __forceinline__ void x3_split_acc(const f32x16& z, bf16x8 (&p)[3]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        bf16_t h0, h1, h2;
-        x3_split1(z[8 * S + e], h0, h1, h2);
-        p[0][e] = h0; p[1][e] = h1; p[2][e] = h2;
-    }
-}
-#define X3_MFMA6(ACC, A, Bv)                                                         \
-    do {                                                                             \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], Bv[2], ACC, 0, 0, 0);    \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], Bv[0], ACC, 0, 0, 0);    \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], Bv[1], ACC, 0, 0, 0);    \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], Bv[1], ACC, 0, 0, 0);    \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], Bv[0], ACC, 0, 0, 0);    \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], Bv[0], ACC, 0, 0, 0);    \
-    } while (0)
-
 // ---- split kernel: up to three fp32 (B, T, H, 64) operands -> 3 bf16 planes each, dense (B, T, D) ------------------------------
 struct X3SplitArgs {
     const float* src[3];
@@ -129,12 +101,7 @@ __global__ __launch_bounds__(256) void x3_split_kernel(const X3SplitArgs a) {
     const float* s = a.src[w] + (int64_t)b * a.sb + (int64_t)tok * a.st + (int64_t)h * a.sh + c8 * 8;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(s), hi = *reinterpret_cast<const f32x4*>(s + 4);
     bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        bf16_t h0, h1, h2;
-        x3_split1(e < 4 ? lo[e] : hi[e - 4], h0, h1, h2);
-        p0[e] = h0; p1[e] = h1; p2[e] = h2;
-    }
+    split3_bf16(lo, hi, p0, p1, p2);
     bf16_t* d = a.dst + (int64_t)(3 * w) * a.plane + i * 8;
     *reinterpret_cast<bf16x8*>(d) = p0;
     *reinterpret_cast<bf16x8*>(d + a.plane) = p1;
@@ -151,12 +118,7 @@ __global__ __launch_bounds__(256) void x3_split2d_kernel(const float* __restrict
     const float* s = x + row * ld + c8 * 8;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(s), hi = *reinterpret_cast<const f32x4*>(s + 4);
     bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        bf16_t h0, h1, h2;
-        x3_split1(e < 4 ? lo[e] : hi[e - 4], h0, h1, h2);
-        p0[e] = h0; p1[e] = h1; p2[e] = h2;
-    }
+    split3_bf16(lo, hi, p0, p1, p2);
     bf16_t* d = dst + row * cols + c8 * 8;
     *reinterpret_cast<bf16x8*>(d) = p0;
     *reinterpret_cast<bf16x8*>(d + plane) = p1;
@@ -213,8 +175,6 @@ __device__ __forceinline__ X3Lane x3_lane(int lane, const char* smem) {
 // finding as gemm_bf16.hip).  LDS operations of a wave return in order, so "at most n outstanding" = "all but my n newest
 // reads have landed"; operations the compiler adds around them only make a wait stricter.  Outputs are early-clobber and the
 // waits name the registers that must have landed.
-#define X3_RD128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
-#define X3_RD32(dst, addr, OFF) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
 #define X3_RDTR(lo, hi, alo, ahi, OFF)                                                                  \
     asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"          \
                  : "=&v"(lo), "=&v"(hi) : "v"(alo), "v"(ahi), "i"(OFF))
@@ -223,7 +183,7 @@ __device__ __forceinline__ X3Lane x3_lane(int lane, const char* smem) {
     asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(h_[0]), "+v"(h_[1]), "+v"(h_[2]))
 // rows of the tile as an MFMA operand: element j of lane (r, h) = tile[r][16 S + 8 h + j], planes 0..2
 #define X3_ROWFRAG(a, lb, TOFF, S) \
-    { X3_RD128(a[0], lb.rowb[S], TOFF); X3_RD128(a[1], lb.rowb[S], (TOFF) + X3_PLANE_B); X3_RD128(a[2], lb.rowb[S], (TOFF) + 2 * X3_PLANE_B); }
+    { IMG_RD128(a[0], lb.rowb[S], TOFF); IMG_RD128(a[1], lb.rowb[S], (TOFF) + X3_PLANE_B); IMG_RD128(a[2], lb.rowb[S], (TOFF) + 2 * X3_PLANE_B); }
 // the tile transposed: element j of lane (r, h) = tile[16 S + 8 (j >> 2) + 4 h + (j & 3)][32 BLK + r] (lo: j < 4, hi: j >= 4)
 #define X3_TRFRAG(l, h_, lb, TOFF, S, BLK)                                                      \
     { X3_RDTR(l[0], h_[0], lb.trb[0][BLK], lb.trb[1][BLK], (TOFF) + (S) * 2048);                 \
@@ -250,18 +210,18 @@ __device__ __forceinline__ void x3_rowop(f32x16& acc, const X3Lane& lb, const bf
     X3_ROWFRAG(a0, lb, TILE_OFF, 0);
     X3_ROWFRAG(a1, lb, TILE_OFF, 1);
     X3_WAIT3(3, a0);
-    { const bf16x8 b_[3] = {y[0][0], y[1][0], y[2][0]}; X3_MFMA6(acc, a0, b_); }
+    { const bf16x8 b_[3] = {y[0][0], y[1][0], y[2][0]}; ACR_MFMA6(acc, a0, b_); }
     f0();
     X3_ROWFRAG(a0, lb, TILE_OFF, 2);
     X3_WAIT3(3, a1);
-    { const bf16x8 b_[3] = {y[0][1], y[1][1], y[2][1]}; X3_MFMA6(acc, a1, b_); }
+    { const bf16x8 b_[3] = {y[0][1], y[1][1], y[2][1]}; ACR_MFMA6(acc, a1, b_); }
     f1();
     X3_ROWFRAG(a1, lb, TILE_OFF, 3);
     X3_WAIT3(3, a0);
-    { const bf16x8 b_[3] = {y[0][2], y[1][2], y[2][2]}; X3_MFMA6(acc, a0, b_); }
+    { const bf16x8 b_[3] = {y[0][2], y[1][2], y[2][2]}; ACR_MFMA6(acc, a0, b_); }
     f2();
     X3_WAIT3(0, a1);
-    { const bf16x8 b_[3] = {y[0][3], y[1][3], y[2][3]}; X3_MFMA6(acc, a1, b_); }
+    { const bf16x8 b_[3] = {y[0][3], y[1][3], y[2][3]}; ACR_MFMA6(acc, a1, b_); }
 }
 // The accumulator tile z (pieces z0: rows 0-15, z1: rows 16-31) times the transposed tile, both 32-column blocks:
 //   ZA = true :  acc_blk[i = z-lane][j = tile column 32 blk + r]      (z is the A operand)
@@ -274,18 +234,18 @@ __device__ __forceinline__ void x3_accop(f32x16& acc0, f32x16& acc1, const bf16x
     X3_TRFRAG(l0, h0, lb, TILE_OFF, 0, 0);
     X3_TRFRAG(l1, h1, lb, TILE_OFF, 0, 1);
     X3_WAIT6(6, l0, h0);
-    { X3_JOIN(t, l0, h0); if (ZA) { X3_MFMA6(acc0, z0, t); } else { X3_MFMA6(acc0, t, z0); } }
+    { X3_JOIN(t, l0, h0); if (ZA) { ACR_MFMA6(acc0, z0, t); } else { ACR_MFMA6(acc0, t, z0); } }
     f0();
     X3_TRFRAG(l0, h0, lb, TILE_OFF, 1, 0);
     X3_WAIT6(6, l1, h1);
-    { X3_JOIN(t, l1, h1); if (ZA) { X3_MFMA6(acc1, z0, t); } else { X3_MFMA6(acc1, t, z0); } }
+    { X3_JOIN(t, l1, h1); if (ZA) { ACR_MFMA6(acc1, z0, t); } else { ACR_MFMA6(acc1, t, z0); } }
     f1();
     X3_TRFRAG(l1, h1, lb, TILE_OFF, 1, 1);
     X3_WAIT6(6, l0, h0);
-    { X3_JOIN(t, l0, h0); if (ZA) { X3_MFMA6(acc0, z1, t); } else { X3_MFMA6(acc0, t, z1); } }
+    { X3_JOIN(t, l0, h0); if (ZA) { ACR_MFMA6(acc0, z1, t); } else { ACR_MFMA6(acc0, t, z1); } }
     f2();
     X3_WAIT6(0, l1, h1);
-    { X3_JOIN(t, l1, h1); if (ZA) { X3_MFMA6(acc1, z1, t); } else { X3_MFMA6(acc1, t, z1); } }
+    { X3_JOIN(t, l1, h1); if (ZA) { ACR_MFMA6(acc1, z1, t); } else { ACR_MFMA6(acc1, t, z1); } }
 }
 // the same with ONE fragment set (12 registers less): a group's reads are issued behind the previous group's filler, their
 // latency is covered by the SIMD partner, not by this wave's own MFMAs (dK/dV body: 256 registers are all there is)
@@ -295,19 +255,19 @@ __device__ __forceinline__ void x3_accop1(f32x16& acc0, f32x16& acc1, const bf16
     bf16x4 l0[3], h0[3];
     X3_TRFRAG(l0, h0, lb, TILE_OFF, 0, 0);
     X3_WAIT6(0, l0, h0);
-    { X3_JOIN(t, l0, h0); if (ZA) { X3_MFMA6(acc0, z0, t); } else { X3_MFMA6(acc0, t, z0); } }
+    { X3_JOIN(t, l0, h0); if (ZA) { ACR_MFMA6(acc0, z0, t); } else { ACR_MFMA6(acc0, t, z0); } }
     X3_TRFRAG(l0, h0, lb, TILE_OFF, 0, 1);
     f0();
     X3_WAIT6(0, l0, h0);
-    { X3_JOIN(t, l0, h0); if (ZA) { X3_MFMA6(acc1, z0, t); } else { X3_MFMA6(acc1, t, z0); } }
+    { X3_JOIN(t, l0, h0); if (ZA) { ACR_MFMA6(acc1, z0, t); } else { ACR_MFMA6(acc1, t, z0); } }
     X3_TRFRAG(l0, h0, lb, TILE_OFF, 1, 0);
     f1();
     X3_WAIT6(0, l0, h0);
-    { X3_JOIN(t, l0, h0); if (ZA) { X3_MFMA6(acc0, z1, t); } else { X3_MFMA6(acc0, t, z1); } }
+    { X3_JOIN(t, l0, h0); if (ZA) { ACR_MFMA6(acc0, z1, t); } else { ACR_MFMA6(acc0, t, z1); } }
     X3_TRFRAG(l0, h0, lb, TILE_OFF, 1, 1);
     f2();
     X3_WAIT6(0, l0, h0);
-    { X3_JOIN(t, l0, h0); if (ZA) { X3_MFMA6(acc1, z1, t); } else { X3_MFMA6(acc1, t, z1); } }
+    { X3_JOIN(t, l0, h0); if (ZA) { ACR_MFMA6(acc1, z1, t); } else { ACR_MFMA6(acc1, t, z1); } }
 }
 // the lane's row (row0 + r, clamped) of an operand's planes as fragments y[plane][k-step]
 __device__ __forceinline__ void x3_rows_from_global(bf16x8 (&y)[3][4], const bf16_t* __restrict__ base, int64_t plane, int D, int row0,
@@ -414,8 +374,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
         rs += __shfl_xor(rs, 32);
         l += rs;
         bf16x8 p0[3], p1[3];
-        x3_split_acc<0>(p, p0);
-        x3_accop<VOFF, false>(o0, o1, p0, p1, lb, [&] { x3_split_acc<1>(p, p1); });      // o[reg] = O^T[d = 32*blk + krow][query = r]
+        split3_bf16_acc<0>(p, p0);
+        x3_accop<VOFF, false>(o0, o1, p0, p1, lb, [&] { split3_bf16_acc<1>(p, p1); });      // o[reg] = O^T[d = 32*blk + krow][query = r]
     };
     for (int k0 = 0; k0 < g.T; k0 += 64) {
         step(k0, std::integral_constant<int, 0>{});
@@ -435,12 +395,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
         // The output as the NEXT product's split-product image (proj reads o as [token][feature] rows; include/acr_hip.h "split-product
         // images"): row = b T + query of the (B T) x D matrix, this head's 64 features = 8 chunks of 8.  Lane (r, h) holds features
         // 8 grp + 4 h .. + 3 of each quad: the two halves of a chunk sit in lanes (r, 0) and (r, 1), so the pair swaps one quad per two
-        // chunks and lane h finishes the chunks of parity h.  Same split expression as the image pass (planes_split8): same bits.
+        // chunks and lane h finishes the chunks of parity h.  The split is the image pass's (split3_bf16, acr_split.h).
         if (oimg != nullptr) {
             const int64_t row = (int64_t)b * g.T + q0 + r;
             const int nkb = g.D >> 4;
-            char* ib = oimg + ((row >> 7) * nkb + hd * 4) * (int64_t)X3_TILE_B + (int)(row & 127) * 32;
-            const int sw = (int)((row >> 3) & 1);
+            char* ib = oimg + IMG_STAGE_OFF(row >> 7, nkb, hd * 4, 3) + (int)(row & 127) * IMG_ROW_B;
+            const int sw = (int)IMG_ROW_SWZ(row);               // planes_chunk_off, on the 64-bit row
 #pragma unroll
             for (int half = 0; half < 2; ++half)
 #pragma unroll
@@ -457,17 +417,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
                     const float v8[8] = {h ? rcv[0] : own[0], h ? rcv[1] : own[1], h ? rcv[2] : own[2], h ? rcv[3] : own[3],
                                          h ? own[0] : rcv[0], h ? own[1] : rcv[1], h ? own[2] : rcv[2], h ? own[3] : rcv[3]};
                     bf16x8 p0, p1, p2;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        bf16_t h0, h1, h2;
-                        x3_split1(v8[e], h0, h1, h2);
-                        p0[e] = h0; p1[e] = h1; p2[e] = h2;
-                    }
+                    split3_bf16(v8, p0, p1, p2);
                     const int c8 = half * 4 + 2 * j + h;        // chunk of 8 features inside the head: stage hd*4 + (c8 >> 1), half c8 & 1
-                    char* dst = ib + (c8 >> 1) * X3_TILE_B + (((c8 & 1) ^ sw) << 4);
+                    char* dst = ib + (c8 >> 1) * (3 * IMG_PLANE_B) + (((c8 & 1) ^ sw) << 4);
                     *reinterpret_cast<bf16x8*>(dst) = p0;
-                    *reinterpret_cast<bf16x8*>(dst + X3_PLANE_B) = p1;
-                    *reinterpret_cast<bf16x8*>(dst + 2 * X3_PLANE_B) = p2;
+                    *reinterpret_cast<bf16x8*>(dst + IMG_PLANE_B) = p1;
+                    *reinterpret_cast<bf16x8*>(dst + 2 * IMG_PLANE_B) = p2;
                 }
         }
     }
@@ -481,7 +436,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
         for (int i = lane; i < (int)(rend - rows) * 24; i += 64) {
             const int64_t row = rows + i / 24;
             const int rem = i % 24, stage = rem / 6, pl = (rem % 6) >> 1, half = rem & 1;
-            char* dst = oimg + ((row >> 7) * nkb + hd * 4 + stage) * (int64_t)X3_TILE_B + pl * X3_PLANE_B + (int)(row & 127) * 32 + half * 16;
+            char* dst = oimg + IMG_STAGE_OFF(row >> 7, nkb, (int64_t)(hd * 4) + stage, 3) + pl * IMG_PLANE_B + (int)(row & 127) * IMG_ROW_B + half * 16;
             *reinterpret_cast<bf16x8*>(dst) = z;
         }
     }
@@ -564,7 +519,7 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
     f32x16 dq0 = {0}, dq1 = {0};
     const X3Lane lb = x3_lane(lane, smem);
     const int doff = x3_dma_off(g.D, pc, lane);
-    const uint32_t saddr = x3_lds_addr(sw) + lane * 16;                                 // + slot * 4096 + gq * 1024
+    const uint32_t saddr = x3_lds_addr(sw) + lane * 16;                                 // + slot * X3_SB_FLOATS * 4 + gq * 1024
     uint32_t gaddr[4];                                                                  // quad gq = keys 8 gq + 4 h .. + 3 of row r
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) gaddr[gq] = x3_lds_addr(gw) + r * 128 + (((2 * gq + h) ^ ((r >> 1) & 7)) << 4);
@@ -586,10 +541,10 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
         // tile(t+1) [3].  The score block (t) is older than it.
         if (k0 > 0) x3_wait_vm(k0 + 32 < g.T ? 7 : 0);
         f32x4 s4[4], g4[4];
-        X3_RD128(s4[0], saddr, SLOT * 4096); X3_RD128(s4[1], saddr, SLOT * 4096 + 1024);
-        X3_RD128(s4[2], saddr, SLOT * 4096 + 2048); X3_RD128(s4[3], saddr, SLOT * 4096 + 3072);
+        IMG_RD128(s4[0], saddr, SLOT * X3_SB_FLOATS * 4); IMG_RD128(s4[1], saddr, SLOT * X3_SB_FLOATS * 4 + 1024);
+        IMG_RD128(s4[2], saddr, SLOT * X3_SB_FLOATS * 4 + 2048); IMG_RD128(s4[3], saddr, SLOT * X3_SB_FLOATS * 4 + 3072);
         if (gb0 != nullptr) {
-            X3_RD128(g4[0], gaddr[0], 0); X3_RD128(g4[1], gaddr[1], 0); X3_RD128(g4[2], gaddr[2], 0); X3_RD128(g4[3], gaddr[3], 0);
+            IMG_RD128(g4[0], gaddr[0], 0); IMG_RD128(g4[1], gaddr[1], 0); IMG_RD128(g4[2], gaddr[2], 0); IMG_RD128(g4[3], gaddr[3], 0);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(g4[0]), "+v"(g4[1]), "+v"(g4[2]), "+v"(g4[3]));
             if (k0 + 32 > g.T) {                           // keys beyond T: their columns hold whatever the row pitch holds
 #pragma unroll
@@ -610,9 +565,9 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
         // the private tiles have been read: G is refilled for the next step and the score slot for the step AFTER next -- between
         // the MFMA groups of the second product, like the second half of the split
         bf16x8 z0[3], z1[3];
-        x3_split_acc<0>(ds, z0);
+        split3_bf16_acc<0>(ds, z0);
         x3_accop<KOFF, true>(dq0, dq1, z0, z1, lb,          // dQ[query = krow][d = 32*blk + r]
-                             [&] { x3_split_acc<1>(ds, z1); },
+                             [&] { split3_bf16_acc<1>(ds, z1); },
                              [&] { if (k0 + 32 < g.T) dma_g(k0 + 32); X3_FENCE(); },
                              [&] { if (k0 + 64 < g.T) dma_scores((k0 >> 5) + 2, SLOT); X3_FENCE(); });
     };
@@ -707,7 +662,7 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
     f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
     const X3Lane lb = x3_lane(lane, smem);
     const int doff = x3_dma_off(g.D, pc, lane);
-    // transposed score reads: lane (kappa = r, h): LDS byte address = tb4[reg & 3] + slot*4096 + 128*(reg >> 2)
+    // transposed score reads: lane (kappa = r, h): LDS byte address = tb4[reg & 3] + slot * X3_SB_FLOATS * 4 + 128*(reg >> 2)
     uint32_t tb4[4];
     {
         const int gk = r >> 3, hk = (r >> 2) & 1, ek = r & 3, mm = 2 * gk + hk;
@@ -735,15 +690,15 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
         // lse2-delta(t) and G(t) (issued in the previous step) must have landed in this wave's private tiles: behind them are
         // scores(t+1) [4] and this step's tile(t+1) [3].  The score block (t) is older than both: it has landed with them.
         if (q0 > 0) x3_wait_vm(q0 + 32 < g.T ? 7 : 0);
-        // this wave's private tiles, read by inline asm (see X3_RD128): score block transposed, G block, lse2 | delta
+        // this wave's private tiles, read by inline asm (see IMG_RD128): score block transposed, G block, lse2 | delta
         float s[16], gv[16];
         f32x4 l4[4], d4[4];
-#define X3_RDS(REG) X3_RD32(s[REG], tb4[(REG) & 3], SLOT * X3_SB_FLOATS * 4 + 128 * ((REG) >> 2))
-#define X3_RDG(REG) X3_RD32(gv[REG], gaddr, 128 * (((REG) & 3) + 8 * ((REG) >> 2)))
+#define X3_RDS(REG) IMG_RD32(s[REG], tb4[(REG) & 3], SLOT * X3_SB_FLOATS * 4 + 128 * ((REG) >> 2))
+#define X3_RDG(REG) IMG_RD32(gv[REG], gaddr, 128 * (((REG) & 3) + 8 * ((REG) >> 2)))
         X3_RDS(0); X3_RDS(1); X3_RDS(2); X3_RDS(3); X3_RDS(4); X3_RDS(5); X3_RDS(6); X3_RDS(7);
         X3_RDS(8); X3_RDS(9); X3_RDS(10); X3_RDS(11); X3_RDS(12); X3_RDS(13); X3_RDS(14); X3_RDS(15);
-        X3_RD128(l4[0], rcaddr, 0); X3_RD128(l4[1], rcaddr, 32); X3_RD128(l4[2], rcaddr, 64); X3_RD128(l4[3], rcaddr, 96);
-        X3_RD128(d4[0], rcaddr, 128); X3_RD128(d4[1], rcaddr, 160); X3_RD128(d4[2], rcaddr, 192); X3_RD128(d4[3], rcaddr, 224);
+        IMG_RD128(l4[0], rcaddr, 0); IMG_RD128(l4[1], rcaddr, 32); IMG_RD128(l4[2], rcaddr, 64); IMG_RD128(l4[3], rcaddr, 96);
+        IMG_RD128(d4[0], rcaddr, 128); IMG_RD128(d4[1], rcaddr, 160); IMG_RD128(d4[2], rcaddr, 192); IMG_RD128(d4[3], rcaddr, 224);
         if (gb0 != nullptr) {
             X3_RDG(0); X3_RDG(1); X3_RDG(2); X3_RDG(3); X3_RDG(4); X3_RDG(5); X3_RDG(6); X3_RDG(7);
             X3_RDG(8); X3_RDG(9); X3_RDG(10); X3_RDG(11); X3_RDG(12); X3_RDG(13); X3_RDG(14); X3_RDG(15);
@@ -778,14 +733,14 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
         // the splits of P's second half and of dS; the DMAs land under the rest of the step and the next step's counted waits
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // every read of the private tiles has returned
         bf16x8 z0[3], z1[3];
-        x3_split_acc<0>(p, z0);
+        split3_bf16_acc<0>(p, z0);
         x3_accop<DOOFF, true>(dv0, dv1, z0, z1, lb,
-                              [&] { x3_split_acc<1>(p, z1); },
+                              [&] { split3_bf16_acc<1>(p, z1); },
                               [&] { if (q0 + 32 < g.T) dma_rc(q0 + 32); X3_FENCE(); },
                               [&] { if (q0 + 32 < g.T) dma_g(q0 + 32); X3_FENCE(); });
-        x3_split_acc<0>(ds, z0);
+        split3_bf16_acc<0>(ds, z0);
         x3_accop<QOFF, true>(dk0, dk1, z0, z1, lb,
-                             [&] { x3_split_acc<1>(ds, z1); },
+                             [&] { split3_bf16_acc<1>(ds, z1); },
                              [&] { if (q0 + 64 < g.T) dma_scores((q0 >> 5) + 2, SLOT); X3_FENCE(); });
     };
     for (int q0 = 0; q0 < g.T; q0 += 64) {

@@ -22,7 +22,7 @@
 // Arithmetic, tile structure, ring and counted waits are gemm_f32_split_kernel's.
 #include <type_traits>
 
-#include "acr_common.h"
+#include "acr_split.h"
 
 #define C3_BM 128
 #define C3_BN 128
@@ -56,24 +56,6 @@ struct Conv3Args {
     C3Tab t;
 };
 
-__device__ __forceinline__ void c3_split3(const f32x4& lo4, const f32x4& hi4, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = e < 4 ? lo4[e] : hi4[e - 4];
-        const __bf16 h0 = (__bf16)x;
-        const float r1 = x - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const float r2 = r1 - (float)h1;
-        p0[e] = h0; p1[e] = h1; p2[e] = (__bf16)r2;
-    }
-}
-#define C3_MFMA6(ACC, A, Bv)                                                         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], Bv[2], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], Bv[0], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], Bv[1], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], Bv[1], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], Bv[0], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], Bv[0], ACC, 0, 0, 0);
 
 // 9-bit validity mask of pixel p: bit t set iff tap t of p lies inside the image
 __device__ __forceinline__ int c3_valid9(int p, int H, int W, int HW) {
@@ -186,8 +168,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const Conv3Args g
     bf16x8 ap[2][2][3], bp[2][2][3];                        // [register set][block][piece]
     f32x4 ra[2][2], rb[2][2];
 #define C3_ALL(SET)                                                                                 \
-    C3_MFMA6(acc[0][0], ap[SET][0], bp[SET][0]) C3_MFMA6(acc[0][1], ap[SET][0], bp[SET][1])        \
-    C3_MFMA6(acc[1][0], ap[SET][1], bp[SET][0]) C3_MFMA6(acc[1][1], ap[SET][1], bp[SET][1])
+    ACR_MFMA6(acc[0][0], ap[SET][0], bp[SET][0]) ACR_MFMA6(acc[0][1], ap[SET][0], bp[SET][1])        \
+    ACR_MFMA6(acc[1][0], ap[SET][1], bp[SET][0]) ACR_MFMA6(acc[1][1], ap[SET][1], bp[SET][1])
     // stage st: wait until it has landed (stages st+1, st+2 may stay in flight: 4 DMA instructions each), publish it, refill the
     // slot stage st-1 was read from, read + mask + split stage st into register set SET while the MFMAs of stage st-1 (set SET^1) run
     auto step = [&](int st, auto set_tag, auto first_tag) {
@@ -218,9 +200,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const Conv3Args g
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) c3_split3(ra[i][0], ra[i][1], ap[SET][i][0], ap[SET][i][1], ap[SET][i][2]);
+        for (int i = 0; i < 2; ++i) split3_bf16(ra[i][0], ra[i][1], ap[SET][i][0], ap[SET][i][1], ap[SET][i][2]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c3_split3(rb[j][0], rb[j][1], bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
+        for (int j = 0; j < 2; ++j) split3_bf16(rb[j][0], rb[j][1], bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
         if (!FIRST) {
             C3_ALL(SET ^ 1)
 #pragma unroll
@@ -260,11 +242,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const Conv3Args g
 // whose ring this is: 3 slots x [A planes 12 KiB | B fp32 8 KiB], DMA two stages ahead, 3 + 2 pieces per wave and stage, counted
 // vmcnt, fence-free barrier).  B tile, tap shift, validity masks, careful edge path and K-split slabs are the kernel's above.
 // ---------------------------------------------------------------------------------------------------------------------------------
-#define C3W_PLANE_B 4096                  // one plane of a 128-row x 16-deep A stage in the tiled image
-#define C3W_STAGE_B (3 * C3W_PLANE_B + C3_TILE * 4)        // 20 KiB
+#define C3W_STAGE_B IMG_W_STAGE_B(C3_TILE)               // 20 KiB
 #define C3W_SLOTS 3
-#define C3W_RD128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
-#define C3W_RD32(dst, addr, OFF) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
 template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kernel(const Conv3Args g) {
     __shared__ __attribute__((aligned(1024))) char smem[C3W_SLOTS * C3W_STAGE_B];       // 60 KiB
     const int tid = threadIdx.x, lane = tid & 63;
@@ -279,7 +258,7 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
     const int m0 = tm * C3_BM, n0 = tn * C3_BN;
     const int nkb = (TAB ? g.t.ntap : 9) * g.C / C3_BK;     // stages per row block of the weight image
     const int xrows = TAB ? g.t.xrows : g.C, yrows = TAB ? g.t.yrows : g.M, maxoff = TAB ? g.t.maxoff : g.W + 1;
-    const char* __restrict__ pa = reinterpret_cast<const char*>(g.w) + ((int64_t)tm * nkb + sbeg) * (3 * C3W_PLANE_B) + wave * 3072 + lane * 16;
+    const char* __restrict__ pa = reinterpret_cast<const char*>(g.w) + IMG_STAGE_OFF(tm, nkb, sbeg, 3) + wave * 3072 + lane * 16;
     const float* __restrict__ pb = g.x + (int64_t)sample * xrows * g.HW;
     const bool compute = m0 + wm * 64 < g.M;
     f32x16 acc[2][2];
@@ -301,13 +280,13 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
         char* d = smem + slot * C3W_STAGE_B;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            __builtin_amdgcn_global_load_lds((c3_glb_vp)(pa + (int64_t)st * (3 * C3W_PLANE_B) + i * 1024), (c3_lds_vp)(d + (wave * 3 + i) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((c3_glb_vp)(pa + (int64_t)st * (3 * IMG_PLANE_B) + i * 1024), (c3_lds_vp)(d + (wave * 3 + i) * 1024), 16, 0, 0);
         const int k0 = (sbeg + st) * C3_BK;
         const int tap = k0 / g.C;
         int ci0 = k0 - tap * g.C, off;
         if (TAB) { off = g.t.toff[tap]; ci0 += g.t.tcb[tap]; }
         else { const int ty = tap / 3; off = (ty - 1) * g.W + (tap - 3 * ty - 1); }
-        float* db = reinterpret_cast<float*>(d + 3 * C3W_PLANE_B);
+        float* db = reinterpret_cast<float*>(d + 3 * IMG_PLANE_B);
         if (edge) {
             const int64_t i0 = (int64_t)sample * xrows * g.HW + (int64_t)ci0 * g.HW + (pix + off);
 #pragma unroll
@@ -320,19 +299,12 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
             __builtin_amdgcn_global_load_lds((c3_glb_vp)(xb + rowb[i]), (c3_lds_vp)(db + (wave * 2 + i) * 256), 16, 0, 0);
     };
     const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
-    const uint32_t fa = lbase + (wm * 64 + r) * 32 + (h ^ ((r >> 3) & 1)) * 16;
-    const uint32_t fb = lbase + 3 * C3W_PLANE_B + ((8 * h) * C3_BN + wn * 64 + r) * 4;
+    const uint32_t fa = IMG_FRAG_ADDR(lbase, wm * 64 + r, r, h);
+    const uint32_t fb = lbase + 3 * IMG_PLANE_B + ((8 * h) * C3_BN + wn * 64 + r) * 4;
     issue(0, 0);
     issue(min(1, nst - 1), 1);
     bf16x8 ap[2][2][3], bp[2][2][3];                        // [register set][block][plane]
     float rb[2][8];
-#define C3W_MFMA6(SET, I, J)                                                                                                 \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][0], bp[SET][J][2], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][2], bp[SET][J][0], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][1], bp[SET][J][1], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][0], bp[SET][J][1], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][1], bp[SET][J][0], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][0], bp[SET][J][0], acc[I][J], 0, 0, 0);
     auto step = [&](int st, int slot, auto set_tag, auto first_tag) {
         constexpr int SET = decltype(set_tag)::value;
         constexpr bool FIRST = decltype(first_tag)::value;
@@ -346,15 +318,15 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
         const uint32_t fas = fa + slot * C3W_STAGE_B, fbs = fb + slot * C3W_STAGE_B;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            C3W_RD32(rb[j][0], fbs, 0 * C3_BN * 4 + j * 128); C3W_RD32(rb[j][1], fbs, 1 * C3_BN * 4 + j * 128);
-            C3W_RD32(rb[j][2], fbs, 2 * C3_BN * 4 + j * 128); C3W_RD32(rb[j][3], fbs, 3 * C3_BN * 4 + j * 128);
-            C3W_RD32(rb[j][4], fbs, 4 * C3_BN * 4 + j * 128); C3W_RD32(rb[j][5], fbs, 5 * C3_BN * 4 + j * 128);
-            C3W_RD32(rb[j][6], fbs, 6 * C3_BN * 4 + j * 128); C3W_RD32(rb[j][7], fbs, 7 * C3_BN * 4 + j * 128);
+            IMG_RD32(rb[j][0], fbs, 0 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][1], fbs, 1 * C3_BN * 4 + j * 128);
+            IMG_RD32(rb[j][2], fbs, 2 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][3], fbs, 3 * C3_BN * 4 + j * 128);
+            IMG_RD32(rb[j][4], fbs, 4 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][5], fbs, 5 * C3_BN * 4 + j * 128);
+            IMG_RD32(rb[j][6], fbs, 6 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][7], fbs, 7 * C3_BN * 4 + j * 128);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            C3W_RD128(ap[SET][i][0], fas, 0 * C3W_PLANE_B + i * 1024); C3W_RD128(ap[SET][i][1], fas, 1 * C3W_PLANE_B + i * 1024);
-            C3W_RD128(ap[SET][i][2], fas, 2 * C3W_PLANE_B + i * 1024);
+            IMG_RD128(ap[SET][i][0], fas, 0 * IMG_PLANE_B + i * 1024); IMG_RD128(ap[SET][i][1], fas, 1 * IMG_PLANE_B + i * 1024);
+            IMG_RD128(ap[SET][i][2], fas, 2 * IMG_PLANE_B + i * 1024);
         }
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]), "+v"(rb[0][4]), "+v"(rb[0][5]), "+v"(rb[0][6]),
                      "+v"(rb[0][7]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3]), "+v"(rb[1][4]), "+v"(rb[1][5]), "+v"(rb[1][6]), "+v"(rb[1][7]));
@@ -365,10 +337,10 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
             const bool ok = (((j ? valid1 : valid0) >> tap) & 1) != 0;
             f32x4 lo = {rb[j][0], rb[j][1], rb[j][2], rb[j][3]}, hi = {rb[j][4], rb[j][5], rb[j][6], rb[j][7]};
             if (!ok) { lo = f32x4{0.f, 0.f, 0.f, 0.f}; hi = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            c3_split3(lo, hi, bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
+            split3_bf16(lo, hi, bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
         }
         if (!FIRST) {
-            C3W_MFMA6(SET ^ 1, 0, 0) C3W_MFMA6(SET ^ 1, 0, 1) C3W_MFMA6(SET ^ 1, 1, 0) C3W_MFMA6(SET ^ 1, 1, 1)
+            ACR_MFMA6(acc[0][0], ap[SET ^ 1][0], bp[SET ^ 1][0]) ACR_MFMA6(acc[0][1], ap[SET ^ 1][0], bp[SET ^ 1][1]) ACR_MFMA6(acc[1][0], ap[SET ^ 1][1], bp[SET ^ 1][0]) ACR_MFMA6(acc[1][1], ap[SET ^ 1][1], bp[SET ^ 1][1])
 #pragma unroll
             for (int it = 0; it < 24; ++it) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA of stage st - 1
@@ -390,9 +362,8 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the refills past the end (nobody may leave LDS-DMA in flight)
     if (!compute) return;
-    if (nst & 1) { C3W_MFMA6(0, 0, 0) C3W_MFMA6(0, 0, 1) C3W_MFMA6(0, 1, 0) C3W_MFMA6(0, 1, 1) }
-    else { C3W_MFMA6(1, 0, 0) C3W_MFMA6(1, 0, 1) C3W_MFMA6(1, 1, 0) C3W_MFMA6(1, 1, 1) }
-#undef C3W_MFMA6
+    if (nst & 1) { ACR_MFMA6(acc[0][0], ap[0][0], bp[0][0]) ACR_MFMA6(acc[0][1], ap[0][0], bp[0][1]) ACR_MFMA6(acc[1][0], ap[0][1], bp[0][0]) ACR_MFMA6(acc[1][1], ap[0][1], bp[0][1]) }
+    else { ACR_MFMA6(acc[0][0], ap[1][0], bp[1][0]) ACR_MFMA6(acc[0][1], ap[1][0], bp[1][1]) ACR_MFMA6(acc[1][0], ap[1][1], bp[1][0]) ACR_MFMA6(acc[1][1], ap[1][1], bp[1][1]) }
     float* yb = g.ksplit > 1 ? g.ws + ((int64_t)part * g.nsamp + sample) * g.M * g.HW : g.y + (int64_t)sample * yrows * g.HW;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -431,7 +402,7 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
     const int nkb = (TAB ? g.t.ntap : 9) * g.C / C3_BK;
     const int xrows = TAB ? g.t.xrows : g.C, yrows = TAB ? g.t.yrows : g.M, maxoff = TAB ? g.t.maxoff : g.W + 1;
     const int qa = wave < 3 ? 2 * wave : 4;                 // this wave's two A pieces: qa, qa + 1 (plane q >> 1, KiB q & 1 of its upper half)
-    const char* __restrict__ pa = reinterpret_cast<const char*>(g.w) + (int64_t)sbeg * (3 * C3W_PLANE_B) + lane * 16;
+    const char* __restrict__ pa = reinterpret_cast<const char*>(g.w) + IMG_STAGE_OFF(0, 0, sbeg, 3) + lane * 16;
     const float* __restrict__ pb = g.x + (int64_t)sample * xrows * g.HW;
     f32x16 acc[2][2];
 #pragma unroll
@@ -450,7 +421,7 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int q = qa + i;
-            __builtin_amdgcn_global_load_lds((c3_glb_vp)(pa + (int64_t)st * (3 * C3W_PLANE_B) + (q >> 1) * C3W_PLANE_B + (q & 1) * 1024),
+            __builtin_amdgcn_global_load_lds((c3_glb_vp)(pa + (int64_t)st * (3 * IMG_PLANE_B) + (q >> 1) * IMG_PLANE_B + (q & 1) * 1024),
                                              (c3_lds_vp)(d + q * 1024), 16, 0, 0);
         }
         const int k0 = (sbeg + st) * C3_BK;
@@ -471,19 +442,12 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
             __builtin_amdgcn_global_load_lds((c3_glb_vp)(xb + (int64_t)(4 * wave + i) * g.HW), (c3_lds_vp)(db + (4 * wave + i) * C3N_BN), 16, 0, 0);
     };
     const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
-    const uint32_t fa = lbase + r * 32 + (h ^ ((r >> 3) & 1)) * 16;
+    const uint32_t fa = IMG_FRAG_ADDR(lbase, r, r, h);
     const uint32_t fb = lbase + C3N_A_B + ((8 * h) * C3N_BN + wn * 64 + r) * 4;
     issue(0, 0);
     issue(min(1, nst - 1), 1);
     bf16x8 ap[2][2][3], bp[2][2][3];
     float rb[2][8];
-#define C3N_MFMA6(SET, I, J)                                                                                                 \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][0], bp[SET][J][2], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][2], bp[SET][J][0], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][1], bp[SET][J][1], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][0], bp[SET][J][1], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][1], bp[SET][J][0], acc[I][J], 0, 0, 0);                   \
-    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[SET][I][0], bp[SET][J][0], acc[I][J], 0, 0, 0);
     auto step = [&](int st, int slot, auto set_tag, auto first_tag) {
         constexpr int SET = decltype(set_tag)::value;
         constexpr bool FIRST = decltype(first_tag)::value;
@@ -494,15 +458,15 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
         const uint32_t fas = fa + slot * C3N_STAGE_B, fbs = fb + slot * C3N_STAGE_B;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            C3W_RD32(rb[j][0], fbs, 0 * C3N_BN * 4 + j * 128); C3W_RD32(rb[j][1], fbs, 1 * C3N_BN * 4 + j * 128);
-            C3W_RD32(rb[j][2], fbs, 2 * C3N_BN * 4 + j * 128); C3W_RD32(rb[j][3], fbs, 3 * C3N_BN * 4 + j * 128);
-            C3W_RD32(rb[j][4], fbs, 4 * C3N_BN * 4 + j * 128); C3W_RD32(rb[j][5], fbs, 5 * C3N_BN * 4 + j * 128);
-            C3W_RD32(rb[j][6], fbs, 6 * C3N_BN * 4 + j * 128); C3W_RD32(rb[j][7], fbs, 7 * C3N_BN * 4 + j * 128);
+            IMG_RD32(rb[j][0], fbs, 0 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][1], fbs, 1 * C3N_BN * 4 + j * 128);
+            IMG_RD32(rb[j][2], fbs, 2 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][3], fbs, 3 * C3N_BN * 4 + j * 128);
+            IMG_RD32(rb[j][4], fbs, 4 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][5], fbs, 5 * C3N_BN * 4 + j * 128);
+            IMG_RD32(rb[j][6], fbs, 6 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][7], fbs, 7 * C3N_BN * 4 + j * 128);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            C3W_RD128(ap[SET][i][0], fas, 0 * 2048 + i * 1024); C3W_RD128(ap[SET][i][1], fas, 1 * 2048 + i * 1024);
-            C3W_RD128(ap[SET][i][2], fas, 2 * 2048 + i * 1024);
+            IMG_RD128(ap[SET][i][0], fas, 0 * 2048 + i * 1024); IMG_RD128(ap[SET][i][1], fas, 1 * 2048 + i * 1024);
+            IMG_RD128(ap[SET][i][2], fas, 2 * 2048 + i * 1024);
         }
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]), "+v"(rb[0][4]), "+v"(rb[0][5]), "+v"(rb[0][6]),
                      "+v"(rb[0][7]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3]), "+v"(rb[1][4]), "+v"(rb[1][5]), "+v"(rb[1][6]), "+v"(rb[1][7]));
@@ -513,10 +477,10 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
             const bool ok = (((j ? valid1 : valid0) >> tap) & 1) != 0;
             f32x4 lo = {rb[j][0], rb[j][1], rb[j][2], rb[j][3]}, hi = {rb[j][4], rb[j][5], rb[j][6], rb[j][7]};
             if (!ok) { lo = f32x4{0.f, 0.f, 0.f, 0.f}; hi = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            c3_split3(lo, hi, bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
+            split3_bf16(lo, hi, bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
         }
         if (!FIRST) {
-            C3N_MFMA6(SET ^ 1, 0, 0) C3N_MFMA6(SET ^ 1, 0, 1) C3N_MFMA6(SET ^ 1, 1, 0) C3N_MFMA6(SET ^ 1, 1, 1)
+            ACR_MFMA6(acc[0][0], ap[SET ^ 1][0], bp[SET ^ 1][0]) ACR_MFMA6(acc[0][1], ap[SET ^ 1][0], bp[SET ^ 1][1]) ACR_MFMA6(acc[1][0], ap[SET ^ 1][1], bp[SET ^ 1][0]) ACR_MFMA6(acc[1][1], ap[SET ^ 1][1], bp[SET ^ 1][1])
 #pragma unroll
             for (int it = 0; it < 24; ++it) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -537,9 +501,8 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (nst & 1) { C3N_MFMA6(0, 0, 0) C3N_MFMA6(0, 0, 1) C3N_MFMA6(0, 1, 0) C3N_MFMA6(0, 1, 1) }
-    else { C3N_MFMA6(1, 0, 0) C3N_MFMA6(1, 0, 1) C3N_MFMA6(1, 1, 0) C3N_MFMA6(1, 1, 1) }
-#undef C3N_MFMA6
+    if (nst & 1) { ACR_MFMA6(acc[0][0], ap[0][0], bp[0][0]) ACR_MFMA6(acc[0][1], ap[0][0], bp[0][1]) ACR_MFMA6(acc[1][0], ap[0][1], bp[0][0]) ACR_MFMA6(acc[1][1], ap[0][1], bp[0][1]) }
+    else { ACR_MFMA6(acc[0][0], ap[1][0], bp[1][0]) ACR_MFMA6(acc[0][1], ap[1][0], bp[1][1]) ACR_MFMA6(acc[1][0], ap[1][1], bp[1][0]) ACR_MFMA6(acc[1][1], ap[1][1], bp[1][1]) }
     float* yb = g.ksplit > 1 ? g.ws + ((int64_t)part * g.nsamp + sample) * g.M * g.HW : g.y + (int64_t)sample * yrows * g.HW;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -691,9 +654,9 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_spli
         xh1 += C3_BK; if (xh1 >= g.W) xh1 -= g.W;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) c3_split3(ra[i][0], ra[i][1], ap[SET][i][0], ap[SET][i][1], ap[SET][i][2]);
+        for (int i = 0; i < 2; ++i) split3_bf16(ra[i][0], ra[i][1], ap[SET][i][0], ap[SET][i][1], ap[SET][i][2]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c3_split3(rb[j][0], rb[j][1], bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
+        for (int j = 0; j < 2; ++j) split3_bf16(rb[j][0], rb[j][1], bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
         if (!FIRST) {
             C3_ALL(SET ^ 1)
 #pragma unroll
@@ -848,9 +811,9 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wgrad64_ke
         xh1 += C3_BK; if (xh1 >= g.W) xh1 -= g.W;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) c3_split3(ra[i][0], ra[i][1], ap[SET][i][0], ap[SET][i][1], ap[SET][i][2]);
+        for (int i = 0; i < 2; ++i) split3_bf16(ra[i][0], ra[i][1], ap[SET][i][0], ap[SET][i][1], ap[SET][i][2]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c3_split3(rb[j][0], rb[j][1], bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
+        for (int j = 0; j < 2; ++j) split3_bf16(rb[j][0], rb[j][1], bp[SET][j][0], bp[SET][j][1], bp[SET][j][2]);
         if (!FIRST) {
             C3_ALL(SET ^ 1)
 #pragma unroll

@@ -199,7 +199,7 @@ int acr_linear_dgelu_bf16(const void* a, int64_t lda, const void* w, int64_t ldw
  * math: acr_math (how the products are evaluated; everything else is identical).
  * ws: caller-owned scratch of acr_gemm_f32_ws_floats(mode, math, M, N, K) floats (TN: the split slabs; NT / NN: slabs for the
  * K-split tail tiles, 0 when the tile count needs none -- ws may then be NULL; without ws the product runs unsplit.
- * math = ACR_MATH_BF16X3 adds the bf16 planes both operands are split into once per call (csrc/gemm_f32.hip
+ * math = ACR_MATH_BF16X3 adds the bf16 planes both operands are split into once per call (csrc/gemm_planes.hip
  * gemm_f32_planes_kernel); with ws == NULL the operand tiles are split inside the GEMM kernel instead, same results).
  * math = ACR_MATH_FP16X2 adds the fp16x2 images of both operands (row-scaled for NT / NN, column-scaled for TN) and requires ws;
  * it has no other way to run (ACR_ERR_INVALID without ws). */
@@ -259,7 +259,7 @@ int acr_conv1x1_wgrad_f32(int32_t math, const float* dy, const float* x, int32_t
  * (a Linear's input serves its forward and its weight gradient, its output gradient the input and the weight gradient:
  * models/vision_transformer.py:158-164,200,212 and their autograd backward).  An image holds the three bf16 planes of a
  * row-major fp32 matrix x[rows][cols], tiled [128 rows][16 cols] exactly as the GEMM kernels copy them to LDS
- * (csrc/gemm_f32.hip "PRE-TILED"); zero outside the matrix, so no shape conditions beyond the alignment ones.
+ * (csrc/gemm_planes.hip "PRE-TILED"; the geometry as code: csrc/acr_split.h); zero outside the matrix, so no shape conditions beyond the alignment ones.
  *   acr_x3_image_floats(rows, cols): size of an image in floats.
  *   acr_x3_image: image of x (pitch ld floats).  colsum (nullable, (cols)) receives the column sums of x from the same pass
  *                 -- the bias gradient when x = dy -- through colsum_ws (acr_x3_colsum_ws_floats(rows, cols) floats).

@@ -9,6 +9,7 @@
 unsigned long long* g_lab_stamp = nullptr;
 #endif
 #include "../../acr_wsss_amd/csrc/gemm_f32.hip"
+#include "../../acr_wsss_amd/csrc/gemm_planes.hip"          // the products on images acr_gemm_f32 dispatches to
 #include <algorithm>
 
 static thread_local char g_err[512] = "";

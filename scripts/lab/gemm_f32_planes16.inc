@@ -1,6 +1,6 @@
 // Round-4 tested NEGATIVE RESULT, kept out of the product library since round 5 (VERDICT r4 #13): the split-product image products
 // on v_mfma_f32_16x16x32_bf16 with two split terms per instruction.  Not built; to revive, paste the two blocks back into
-// acr_wsss_amd/csrc/gemm_f32.hip (after gemm_f32_planes_kernel resp. gemm_f32_planes_tn_kernel) and dispatch them from acr_gemm_x3.
+// acr_wsss_amd/csrc/gemm_planes.hip (after gemm_f32_planes_kernel resp. gemm_f32_planes_tn_kernel) and dispatch them from acr_gemm_x3.
 // Measured (round 4, scripts/lab/gemm_x3_time.py): 0.55-0.58 ms against 0.54-0.57 ms for the 32x32x16 kernels on the fc1 / fc2 shapes.
 
 // ---------------------------------------------------------------------------------------------------------------------------------
