@@ -231,7 +231,8 @@ def shard_indices(n, rank=0, world=1):
     return list(range(rank, n, world))
 
 
-def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, out_crf=None, low_alpha=1, high_alpha=12, **kw):
+def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, out_crf=None, low_alpha=1, high_alpha=12,
+                   out_pamr=None, pamr_iter=10, pamr_dilations=(1, 2, 4, 8, 12, 24), **kw):
     """Shard ``items`` -- an indexable of (name, img (1,3,h,w), label (1,C), (W,H)[, orig uint8 (W,H,3)]) -- over ranks and
     write ``<out_cam>/<name>.npy`` in the reference's wire format: a pickled {class: float32 (W,H)} dict
     (infer_cam.py:227-228, read back by evaluation.py:23-25).  Returns {name: cam_dict} of this rank.
@@ -242,7 +243,13 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
     the reference's ``chunker(img_list, 1)``, infer_cam.py:123).
     ``out_crf`` (infer_cam.py:68,218-225, defaults of --low_alpha / --high_alpha :72-73): also run the dense CRF on every
     cam_dict at both alphas, on the GPU (crf.crf_with_alpha), and write ``<out_crf>_<alpha>/<name>.npy``; needs the
-    original image as the fifth item element."""
+    original image as the fifth item element.
+    ``out_pamr`` mirrors ``out_crf`` with pixel-adaptive mask refinement (pamr.pamr_with_alpha; the reference imports pamr.py at
+    infer_cam.py:14 but never calls it) as the refinement: ``<out_pamr>_<alpha>/<name>.npy`` for both alphas, same
+    {0: background, class + 1: ...} layout, same fifth item element; both alphas share one affinity and one set of iterations.
+    The defaults ``pamr_iter`` = 10 and ``pamr_dilations`` = (1, 2, 4, 8, 12, 24) are the PAMR paper's setting as remembered: the
+    reference tree holds no PAMR call to take them from, so they are unverified; ``pamr()`` and ``PAMR`` keep the reference
+    module's own defaults (1 iteration, dilations [1]).  Images with no positive class are skipped, as for ``out_crf``."""
     dev = next(model.parameters()).device
     model.eval()
     results = {}
@@ -262,6 +269,16 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
                     folder = out_crf + ("_%s" % alpha)
                     os.makedirs(folder, exist_ok=True)
                     np.save(os.path.join(folder, name + ".npy"), crf_with_alpha(cam_dict, alpha, np.asarray(items[i][4]), device=dev))
+            if out_pamr is not None and cam_dict:
+                if len(items[i]) < 5:
+                    raise ValueError("out_pamr needs the original uint8 image as items[i][4]")
+                from .pamr import pamr_with_alpha
+                refined = pamr_with_alpha(cam_dict, (low_alpha, high_alpha), np.asarray(items[i][4]), num_iter=pamr_iter,
+                                          dilations=pamr_dilations, device=dev)
+                for alpha in (low_alpha, high_alpha):
+                    folder = out_pamr + ("_%s" % alpha)
+                    os.makedirs(folder, exist_ok=True)
+                    np.save(os.path.join(folder, name + ".npy"), refined[alpha])
             results[name] = cam_dict
 
     # one batch in flight behind the one being collected: the kernels of images i+1 are enqueued BEFORE the host blocks on the

@@ -586,6 +586,22 @@ int acr_bilinear_resize(const float* src, int64_t src_sc, int64_t src_sp, int32_
                         int32_t iw, float* dst, int32_t oh, int32_t ow, int32_t align_corners,
                         const float* chan_mul, int32_t hflip, int32_t accumulate, void* stream);
 
+/* ---- pixel-adaptive mask refinement of CAMs (pamr.py:115-144 PAMR.forward, with LocalAffinityAbs / LocalStDev /
+ * LocalAffinityCopy :10-110; imported by infer_cam.py:14 and train_acr_coco.py:15) ----
+ * fp32, planar, contiguous tensors; `dilations` is a HOST array of n_dil (1..8) values >= 1, read during the call.
+ * P = 8 * n_dil neighbours per pixel: neighbour 8 * i + j of dilation d_i sits at (y + dy * d_i, x + dx * d_i), clamped to the
+ * image (replicate padding), j walking (dy, dx) over {-1, 0, 1}^2 row-major without the centre.
+ * acr_pamr_affinity (pamr.py:133-137): x (B, K, H, W) -> w_out (B, P, H, W),
+ *   w[p] = softmax_p( mean_k -|x_k - x_k(neighbour p)| / (1e-8 + 0.1 * std_k) ), std_k the unbiased deviation of the
+ *   9 * n_dil samples of channel k (the centre counted once per dilation).  A flat neighbourhood gives exactly uniform weights.
+ * acr_pamr_propagate (pamr.py:140-141), one iteration: mask_out[c] = sum_p w[p] * mask_in[c](neighbour p) for (B, C, H, W)
+ *   masks; mask_in and mask_out must not alias (iterate by ping-pong between two buffers).
+ * No atomics, fixed summation order: bit-reproducible, and independent of the batch a sample rides in. */
+int acr_pamr_affinity(const float* x, int32_t B, int32_t K, int32_t H, int32_t W, const int32_t* dilations, int32_t n_dil,
+                      float* w_out, void* stream);
+int acr_pamr_propagate(const float* w, const float* mask_in, float* mask_out, int32_t B, int32_t C, int32_t H, int32_t W,
+                       const int32_t* dilations, int32_t n_dil, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
