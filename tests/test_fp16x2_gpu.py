@@ -4,8 +4,8 @@ exact-fp32 kernel's own error, the Linears against fp64, the parts of the model 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+import kernel_checks as KC
 from conftest import load_golden, recipe_sd
 from recipe import make_inputs
 
@@ -224,13 +224,9 @@ def test_linear_f32_fp16x2_against_fp64(M, K, N):
     y = ops.LinearF32Fn.apply(x, w, b, r, None, 2)
     dy = torch.randn(M, N, generator=g).to(DEV)
     (y * dy).sum().backward()
-    xd, wd, bd, rd = (t.detach().double().requires_grad_(True) for t in (x, w, b, r))
-    ref = xd @ wd.t() + bd + rd
-    (ref * dy.double()).sum().backward()
-    for name, got, want in (("y", y, ref), ("dx", x.grad, xd.grad), ("dw", w.grad, wd.grad), ("db", b.grad, bd.grad)):
-        err = (got.double() - want).abs().max() / want.abs().max()
-        assert err <= 1e-5, (name, float(err))
-    torch.testing.assert_close(r.grad, dy)
+    cmp = KC.Cmp()
+    KC.verify_linear(cmp, x, w, b, r, y, dy, KC.grads_of(x, w, b, r))
+    assert not cmp.failures, "\n".join(cmp.failures)
     first = (y.detach().clone(), x.grad.clone(), w.grad.clone(), b.grad.clone())
     x.grad = w.grad = b.grad = None
     y2 = ops.LinearF32Fn.apply(x, w, b, r, None, 2)
@@ -258,14 +254,9 @@ def test_mlp_f32_fp16x2_against_fp64(M, D, Hd):
         (y * dy).sum().backward()
         runs.append([t.detach().clone() for t in (y, x.grad, r.grad, fc1.weight.grad, fc1.bias.grad, fc2.weight.grad, fc2.bias.grad)])
     assert all(torch.equal(u, v) for u, v in zip(*runs))
-    xd, rd = x.detach().double().requires_grad_(True), r.detach().double().requires_grad_(True)
-    p = [t.detach().double().requires_grad_(True) for t in (fc1.weight, fc1.bias, fc2.weight, fc2.bias)]
-    ref = F.linear(F.gelu(F.linear(xd, p[0], p[1])), p[2], p[3]) + rd
-    (ref * dy.double()).sum().backward()
-    want = [ref, xd.grad, rd.grad, p[0].grad, p[1].grad, p[2].grad, p[3].grad]
-    for n, a, b in zip(["y", "dx", "dresid", "dW1", "db1", "dW2", "db2"], runs[0], want):
-        err = (a.double() - b).abs().max().item() / max(b.abs().max().item(), 1e-9)
-        assert err <= 1e-5, (n, err)
+    cmp = KC.Cmp()
+    KC.verify_mlp(cmp, x, r, [fc1.weight, fc1.bias, fc2.weight, fc2.bias], runs[0][0], dy, runs[0][1:], math=2)
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 def _model(kind="hybrid"):

@@ -8,6 +8,8 @@ import os
 import pytest
 import torch
 
+import kernel_checks as KC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -15,16 +17,11 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _ref_attn(qkv, H, want_grad=False):
-    B, T, _ = qkv.shape
-    q, k, v = qkv.double().reshape(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
-    P = ((q @ k.transpose(-2, -1)) * 64 ** -0.5).softmax(-1)
-    o = (P @ v).transpose(1, 2).reshape(B, T, H * 64)
-    return o, P
+def _ref_attn(qkv, H):
+    return KC.attn_ref(qkv.double(), H)
 
 
-def _flip_perm(p, dev):
-    return torch.arange(p * p, device=dev).reshape(p, p).flip(1).reshape(-1)
+_flip_perm = KC.flip_perm
 
 
 @pytest.mark.parametrize("B,L,p", [(1, 1, 1), (2, 3, 4), (1, 12, 14), (2, 2, 28), (1, 2, 37), (1, 3, 32)])   # p = 32: COCO 512^2
@@ -39,15 +36,9 @@ def test_consistency(B, L, p):
     cls, aff = ops.consistency(a, p)
     w = torch.tensor([1.7, -0.6], device=dev)
     (cls * w[0] + aff * w[1]).backward()
-    ad = a.detach().double().requires_grad_(True)
-    pi = _flip_perm(p, dev)
-    a1, a2 = ad[:B], ad[B:]
-    rc = (a1[:, :, 0, 1:] - a2[:, :, 0, 1:][:, :, pi]).abs().mean()
-    ra = (a1[:, :, 1:, 1:] - a2[:, :, 1:, 1:][:, :, pi][:, :, :, pi]).abs().mean()
-    (rc * w[0].double() + ra * w[1].double()).backward()
-    assert abs(float(cls) - float(rc)) <= 2e-6 * abs(float(rc)) + 1e-9
-    assert abs(float(aff) - float(ra)) <= 2e-6 * abs(float(ra)) + 1e-9
-    torch.testing.assert_close(a.grad.double(), ad.grad, rtol=1e-5, atol=1e-12)
+    cmp = KC.Cmp()
+    KC.verify_consistency(cmp, a, p, w, cls, aff, KC.grads_of(a))
+    assert not cmp.failures, "\n".join(cmp.failures)
     # in-place-flip form of the reference (train_acr.py:151-158) gives the same numbers
     b2 = a.detach()[B:].clone()
     c2, f2 = b2[:, :, 0, 1:].unsqueeze(2), b2[:, :, 1:, 1:]
@@ -125,16 +116,10 @@ def test_attention_f32(B, T, H, with_g, gen, monkeypatch):
         ((o2 * d_o).sum() + ((pm2 * gpm).sum() if with_g else 0.0)).backward()
         assert torch.equal(o2, o) and torch.equal(pm2, pm) and torch.equal(q2.grad, qkv.grad)
 
-    qd = qkv.detach().double().requires_grad_(True)
-    o_ref, P = _ref_attn(qd, H)
-    pm_ref = P.mean(1)
-    loss_ref = (o_ref * d_o.double()).sum() + ((pm_ref * gpm.double()).sum() if with_g else 0.0)
-    loss_ref.backward()
-    torch.testing.assert_close(o.double(), o_ref, rtol=1e-4, atol=2e-5)
-    torch.testing.assert_close(pm.double(), pm_ref, rtol=1e-4, atol=1e-7)
+    cmp = KC.Cmp()
+    KC.verify_attention(cmp, qkv, H, o, pm, d_o, gpm, KC.grads_of(qkv))
+    assert not cmp.failures, "\n".join(cmp.failures)
     assert torch.isnan(stack.buf[:, 0]).all()            # the other layer's slice is untouched
-    scale = qd.grad.abs().max()
-    assert (qkv.grad.double() - qd.grad).abs().max() <= 3e-5 * scale, (qkv.grad.double() - qd.grad).abs().max() / scale
 
 
 @pytest.mark.parametrize("math", [0, 1])
@@ -183,15 +168,9 @@ def test_attention_bf16(B, T, H, with_g, f32math):
         ((o.float() * d_o.float()).sum() + ((pm * gpm).sum() if with_g else 0.0)).backward()
     finally:
         _lib.BF16_F32MATH = False
-    qd = qkv.detach().double().requires_grad_(True)
-    o_ref, P = _ref_attn(qd, H)
-    ((o_ref * d_o.double()).sum() + ((P.mean(1) * gpm.double()).sum() if with_g else 0.0)).backward()
-    assert (o.double() - o_ref).abs().max() <= 1.5e-2 * o_ref.abs().max()
-    torch.testing.assert_close(pm.double(), P.mean(1), rtol=2e-3, atol=1e-6)
-    err = (qkv.grad.double() - qd.grad).abs()
-    scale = qd.grad.abs().max()
-    assert err.max() <= (1e-2 if f32math else 2.5e-2) * scale, float(err.max() / scale)
-    assert err.mean() <= (1.5e-3 if f32math else 3e-3) * scale, float(err.mean() / scale)
+    cmp = KC.Cmp()
+    KC.verify_attention(cmp, qkv, H, o, pm, d_o, gpm, KC.grads_of(qkv), f32math=f32math)
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("B,T,dtype,math", [(32, 785, torch.float32, 0), (32, 785, torch.float32, 1), (32, 785, torch.bfloat16, 0),
@@ -238,11 +217,10 @@ def test_probs_dprobs_bf16():
     lse2 = o.grad_fn.saved_tensors[2]
     P = ops.attn_probs(qkv.detach(), lse2, H)
     dP = ops.attn_dprobs(qkv.detach(), d_o, H)
-    _, P_ref = _ref_attn(qkv.detach(), H)
-    v = qkv.detach().double().reshape(B, T, 3, H, 64)[:, :, 2].permute(0, 2, 1, 3)
-    dP_ref = d_o.double().reshape(B, T, H, 64).permute(0, 2, 1, 3) @ v.transpose(-2, -1)
-    torch.testing.assert_close(P.double(), P_ref, rtol=2e-3, atol=1e-6)
-    torch.testing.assert_close(dP.double(), dP_ref, rtol=1e-3, atol=1e-3)
+    cmp = KC.Cmp()
+    KC.verify_attn_probs(cmp, qkv, H, P)
+    KC.verify_attn_dprobs(cmp, qkv, d_o, H, dP)
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("B,T,H", [(2, 145, 12), (1, 577, 12), (1, 2305, 4), (1, 3137, 2)])
@@ -256,53 +234,46 @@ def test_probs_dprobs_getam_row(B, T, H):
     lse2 = o.grad_fn.saved_tensors[2]
     P = ops.attn_probs(qkv.detach(), lse2, H)
     dP = ops.attn_dprobs(qkv.detach(), d_o, H)
-    _, P_ref = _ref_attn(qkv.detach(), H)
-    v = qkv.detach().double().reshape(B, T, 3, H, 64)[:, :, 2].permute(0, 2, 1, 3)
-    dP_ref = d_o.double().reshape(B, T, H, 64).permute(0, 2, 1, 3) @ v.transpose(-2, -1)
-    torch.testing.assert_close(P.double(), P_ref, rtol=1e-4, atol=1e-7)
-    torch.testing.assert_close(dP.double(), dP_ref, rtol=1e-4, atol=1e-4)
+    cmp = KC.Cmp()
+    P_ref = KC.verify_attn_probs(cmp, qkv, H, P)
+    dP_ref = KC.verify_attn_dprobs(cmp, qkv, d_o, H, dP)
     for func in ("grad", "cam_grad", "grad_s", "cam_grad_s"):
         for batch in range(B):
             row = torch.zeros(T, device=dev)
             ops.getam_row_accum(qkv.detach(), d_o, lse2, H, batch, func, row)
             ops.getam_row_accum(qkv.detach(), d_o, lse2, H, batch, func, row)      # accumulates
-            gr, cm = dP_ref[batch], P_ref[batch]
-            mg = gr.clamp(min=0).mean(0)
-            mcg = (gr * cm).clamp(min=0).mean(0)
-            ref = {"grad": mg, "cam_grad": mcg, "grad_s": mg * mg, "cam_grad_s": mcg * mg}[func][0] * 2
-            torch.testing.assert_close(row.double(), ref, rtol=1e-4, atol=1e-6 * float(ref.abs().max()))
+            KC.verify_getam(cmp, P_ref, dP_ref, func, row, batch=batch, times=2)
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("C", [20, 80])                     # 80: COCO (train_acr_coco.py:91)
 def test_cam_readouts(C):
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(3)
     N, D = 36, 768
     x = torch.randn(1 + N, D, generator=g).to(dev)
     w = (torch.randn(C, D, generator=g) * D ** -0.5).to(dev)
     bias = torch.randn(C, generator=g).to(dev)
+    cmp = KC.Cmp()
     pc = ops.patch_cam(x[1:], w, bias)
-    torch.testing.assert_close(pc, F.relu(F.linear(x[1:], w, bias)), rtol=1e-4, atol=1e-5)
+    KC.verify_patch_cam(cmp, x[1:], w, bias, pc)
     lab = torch.zeros(C, device=dev)
     lab[[3, 11, C - 1]] = 1.0
     for (oh, ow) in ((75, 61), (6, 6), (5, 13), (1, 1)):
-        ref = F.interpolate(pc.t().reshape(1, C, 6, 6), (oh, ow), mode="bilinear", align_corners=False)[0]
-        got = ops.bilinear_resize(pc, (oh, ow), False, chan_mul=lab, hflip=True, channels_last=False) if False else \
-            ops.bilinear_resize(pc.reshape(6, 6, C), (oh, ow), False, chan_mul=lab, hflip=True, channels_last=True)
-        torch.testing.assert_close(got, (ref * lab.view(C, 1, 1)).flip(-1), rtol=1e-5, atol=1e-6)
+        src = pc.reshape(6, 6, C)
+        got = ops.bilinear_resize(src, (oh, ow), False, chan_mul=lab, hflip=True, channels_last=True)
+        KC.verify_bilinear(cmp, src, (oh, ow), False, True, True, lab, None, got)
         src = torch.rand(2, 6, 6, generator=g).to(dev)
-        ref = F.interpolate(src[None], (oh, ow), mode="bilinear", align_corners=True)[0]
         acc = torch.ones(2, oh, ow, device=dev)
         ops.bilinear_resize(src, (oh, ow), True, out=acc)
-        torch.testing.assert_close(acc, ref + 1.0, rtol=1e-5, atol=1e-6)
+        KC.verify_bilinear(cmp, src, (oh, ow), True, False, False, None, torch.ones_like(acc), acc)
     for Ly, T, n in ((12, 37, 11), (12, 577, 3), (12, 2305, 2), (2, 3137, 1)):
         a = torch.rand(Ly, T, T, generator=g).to(dev)
         cams = torch.rand(n, T - 1, generator=g).to(dev)
         out = ops.aff_refine(a, cams)
-        ref = (a[:, 1:, 1:].sum(0).double() @ cams.double().t()).t()
-        torch.testing.assert_close(out.double(), ref, rtol=1e-5, atol=1e-6 * T)
+        KC.verify_aff_refine(cmp, a[None], cams[None], out[None])
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 def test_errors_are_loud():
@@ -358,20 +329,9 @@ def test_linear_bf16(M, N, K, bias, resid):
     y = ops.LinearBf16Fn.apply(x, w, b, r)
     dy = torch.randn(M, N, generator=g).to(dev).bfloat16()
     (y.float() * dy.float()).sum().backward()
-    xd, wd = x.detach().double().requires_grad_(True), w.detach().double().requires_grad_(True)
-    ref = xd @ wd.t()
-    if bias:
-        ref = ref + b.detach().double()
-    if resid:
-        ref = ref + r.detach().double()
-    (ref * dy.double()).sum().backward()
-    assert (y.double() - ref).abs().max() <= 1e-2 * ref.abs().max()
-    assert (x.grad.double() - xd.grad).abs().max() <= 1.5e-2 * xd.grad.abs().max()
-    assert (w.grad.double() - wd.grad).abs().max() <= 1.5e-2 * wd.grad.abs().max()
-    if bias:
-        assert (b.grad.double() - dy.double().sum(0)).abs().max() <= 1e-2 * dy.double().sum(0).abs().max() + 1e-2
-    if resid:
-        torch.testing.assert_close(r.grad, dy)
+    cmp = KC.Cmp()
+    KC.verify_linear(cmp, x, w, b, r, y, dy, KC.grads_of(x, w, b, r))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("N,C,H,W", [(2, 64, 8, 8), (3, 256, 16, 24), (2, 1024, 28, 28), (1, 64, 224, 224)])
@@ -379,7 +339,6 @@ def test_linear_bf16(M, N, K, bias, resid):
 def test_groupnorm_fused(N, C, H, W, act):
     """Fused bf16 GroupNorm(32) [+ residual] [+ ReLU] forward/backward vs torch group_norm + relu in fp64."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(C + H)
     x = (torch.randn(N, C, H, W, generator=g) * 1.7 + 0.3).to(dev).bfloat16().requires_grad_(True)
@@ -390,21 +349,9 @@ def test_groupnorm_fused(N, C, H, W, act):
     y = ops.groupnorm_act(x, w, b, act, r)
     dy = torch.randn(N, C, H, W, generator=g).to(dev).bfloat16()
     (y.float() * dy.float()).sum().backward()
-    xd, wd, bd = (t.detach().double().requires_grad_(True) for t in (x, w, b))
-    ref = F.group_norm(xd, 32, wd, bd, 1e-5)
-    if r is not None:
-        rd = r.detach().double().requires_grad_(True)
-        ref = ref + rd
-    if act != "none":
-        # take the ReLU mask from the kernel's own (bf16-rounded) output so elements that round to +-0 agree
-        ref = ref * (y.detach() > 0).double()
-    (ref * dy.double()).sum().backward()
-    assert (y.double() - ref).abs().max() <= 1.2e-2 * ref.abs().max()
-    assert (x.grad.double() - xd.grad).abs().max() <= 2e-2 * xd.grad.abs().max()
-    assert (w.grad.double() - wd.grad).abs().max() <= 2e-2 * wd.grad.abs().max() + 1e-2
-    assert (b.grad.double() - bd.grad).abs().max() <= 2e-2 * bd.grad.abs().max() + 1e-2
-    if r is not None:
-        assert (r.grad.double() - rd.grad).abs().max() <= 1e-2 * rd.grad.abs().max()
+    cmp = KC.Cmp()
+    KC.verify_groupnorm(cmp, x, w, b, r, act, y, dy, KC.grads_of(x, w, b, r))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("M,N,K", [(64, 128, 128), (100, 256, 128), (785 * 2 + 3, 768, 2304), (25120, 2304, 768),
@@ -446,20 +393,15 @@ def test_weight_std_all_fused():
     assert torch.equal(tr[1], outs[1].reshape(64, 64).t()) and torch.equal(tr[3], outs[3].reshape(33, 5).t())
     gs = [torch.randn(s, generator=g).to(dev).bfloat16() for s in shapes]
     sum((o.float() * gi.float()).sum() for o, gi in zip(outs, gs)).backward()
-    for w, o, gi in zip(ws, outs, gs):
-        wd = w.detach().double().requires_grad_(True)
-        std, mean = torch.std_mean(wd, dim=[1, 2, 3], keepdim=True, unbiased=False)
-        ref = (wd - mean) / (std + 1e-5)
-        (ref * gi.double()).sum().backward()
-        assert (o.double() - ref).abs().max() <= 1e-2 * ref.abs().max()
-        assert (w.grad.double() - wd.grad).abs().max() <= 2e-2 * wd.grad.abs().max() + 1e-3
+    cmp = KC.Cmp()
+    KC.verify_weight_std(cmp, ws, outs, gs, KC.grads_of(*ws))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("M,C", [(1, 256), (37, 768), (25120, 768), (130, 1024)])
 def test_layernorm_bf16(M, C):
     """HIP LayerNorm forward/backward (one-pass backward with dgamma/dbeta) vs torch layer_norm in fp64."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(M + C)
     x = (torch.randn(M, C, generator=g) * 2 + 0.5).to(dev).bfloat16().requires_grad_(True)
@@ -471,14 +413,9 @@ def test_layernorm_bf16(M, C):
     assert y.grad_fn is not None and "LayerNormFn" in type(y.grad_fn).__name__
     dy = torch.randn(M, C, generator=g).to(dev).bfloat16()
     (y.float() * dy.float()).sum().backward()
-    xd = x.detach().double().requires_grad_(True)
-    wd, bd = ln.weight.detach().double().requires_grad_(True), ln.bias.detach().double().requires_grad_(True)
-    ref = F.layer_norm(xd, (C,), wd, bd, 1e-6)
-    (ref * dy.double()).sum().backward()
-    assert (y.double() - ref).abs().max() <= 1.2e-2 * ref.abs().max()
-    assert (x.grad.double() - xd.grad).abs().max() <= 2e-2 * xd.grad.abs().max()
-    assert (ln.weight.grad.double() - wd.grad).abs().max() <= 1e-2 * wd.grad.abs().max() + 1e-2
-    assert (ln.bias.grad.double() - bd.grad).abs().max() <= 1e-2 * bd.grad.abs().max() + 1e-2
+    cmp = KC.Cmp()
+    KC.verify_layernorm(cmp, x, ln.weight, ln.bias, ln.eps, y, None, dy, None, KC.grads_of(x, ln.weight, ln.bias))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("N,cin,cout,H,W", [(2, 64, 64, 8, 8), (3, 64, 256, 16, 24), (2, 256, 64, 28, 28),
@@ -487,7 +424,6 @@ def test_conv1x1_bf16(N, cin, cout, H, W):
     """NCHW 1x1 convolution on the GEMM kernels: forward, input gradient, weight gradient vs fp64 conv2d; covers pixel
     tiles that run past H*W (28x28 = 784 = 6.125 tiles) and the ragged 64-pixel chunk of the weight gradient."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(cin + cout + H)
     x = torch.randn(N, cin, H, W, generator=g).to(dev).bfloat16().requires_grad_(True)
@@ -496,12 +432,9 @@ def test_conv1x1_bf16(N, cin, cout, H, W):
     y = ops.conv1x1(x, w)
     dy = torch.randn(N, cout, H, W, generator=g).to(dev).bfloat16()
     (y.float() * dy.float()).sum().backward()
-    xd, wd = x.detach().double().requires_grad_(True), w.detach().double().requires_grad_(True)
-    ref = F.conv2d(xd, wd)
-    (ref * dy.double()).sum().backward()
-    assert (y.double() - ref).abs().max() <= 1e-2 * ref.abs().max()
-    assert (x.grad.double() - xd.grad).abs().max() <= 1.5e-2 * xd.grad.abs().max()
-    assert (w.grad.double() - wd.grad).abs().max() <= 1e-2 * wd.grad.abs().max()
+    cmp = KC.Cmp()
+    KC.verify_conv1x1(cmp, x, w, y, None, dy, None, KC.grads_of(x, w))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -510,8 +443,7 @@ def test_maxpool_same_bf16(shape, dtype):
     """SAME-padded 3x3/2 max-pool (forward value, argmax routing of the gradient) vs F.pad(-inf)+max_pool2d, bf16 and fp32
     maps; values are made distinct so the argmax is unique and the comparison is exact."""
     from acr_wsss_amd import ops
-    from acr_wsss_amd.backbone import _same_pad, pad_same
-    import torch.nn.functional as F
+    from acr_wsss_amd.backbone import _same_pad
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(sum(shape))
     n = math.prod(shape)
@@ -519,14 +451,11 @@ def test_maxpool_same_bf16(shape, dtype):
     x = x.to(dev).to(dtype).requires_grad_(True)
     ph, pw = _same_pad(shape[2], 3, 2), _same_pad(shape[3], 3, 2)
     y = ops.maxpool3x3s2_same(x, ph // 2, pw // 2, ph, pw)
-    xr = x.detach().clone().requires_grad_(True)
-    yr = F.max_pool2d(pad_same(xr, 3, 2, value=-float("inf")), 3, 2)
-    assert y.shape == yr.shape and torch.equal(y, yr)
     dy = torch.randn(y.shape, generator=g).to(dev).to(dtype)
     y.backward(dy)
-    yr.backward(dy)
-    tol = 2e-2 if dtype == torch.bfloat16 else 1e-6          # a pixel collects up to 4 window gradients: summation order only
-    assert torch.allclose(x.grad.float(), xr.grad.float(), atol=tol, rtol=tol)
+    cmp = KC.Cmp()
+    KC.verify_maxpool(cmp, x, ph // 2, pw // 2, ph, pw, y, dy, KC.grads_of(x))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("M,D,Hd", [(197 * 2, 192, 768), (785, 768, 3072), (320 * 3 + 17, 128, 256)])
@@ -545,16 +474,10 @@ def test_fused_mlp_bf16(M, D, Hd):
     assert ops.mlp_fusable(x, fc1, fc2)
     y = ops.mlp(x, fc1, fc2, r)
     (y.float() * dy.float()).sum().backward()
-    got = [y, x.grad, r.grad, fc1.weight.grad, fc1.bias.grad, fc2.weight.grad, fc2.bias.grad]
-    xd, rd = x.detach().double().requires_grad_(True), r.detach().double().requires_grad_(True)
-    p = [t.detach().double().requires_grad_(True) for t in (fc1.weight, fc1.bias, fc2.weight, fc2.bias)]
-    ref = torch.nn.functional.linear(torch.nn.functional.gelu(torch.nn.functional.linear(xd, p[0], p[1])), p[2], p[3]) + rd
-    (ref * dy.double()).sum().backward()
-    want = [ref, xd.grad, rd.grad, p[0].grad, p[1].grad, p[2].grad, p[3].grad]
-    names = ["y", "dx", "dresid", "dW1", "db1", "dW2", "db2"]
-    for n, a, b in zip(names, got, want):
-        err = (a.double() - b).abs().max().item() / max(b.abs().max().item(), 1e-9)
-        assert err <= 2.5e-2, (n, err)
+    ps = [fc1.weight, fc1.bias, fc2.weight, fc2.bias]
+    cmp = KC.Cmp()
+    KC.verify_mlp(cmp, x, r, ps, y, dy, KC.grads_of(x, r, *ps))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 def test_weight_transposes_cache():
@@ -615,13 +538,9 @@ def _gemm_f32_linear_case(ops, dev, M, N, K, math=0):
     y = ops.LinearF32Fn.apply(x, w, b, r, None, math)
     dy = torch.randn(M, N, generator=g).to(dev)
     (y * dy).sum().backward()
-    xd, wd, bd, rd = (t.detach().double().requires_grad_(True) for t in (x, w, b, r))
-    ref = xd @ wd.t() + bd + rd
-    (ref * dy.double()).sum().backward()
-    for name, got, want in (("y", y, ref), ("dx", x.grad, xd.grad), ("dw", w.grad, wd.grad), ("db", b.grad, bd.grad)):
-        err = (got.double() - want).abs().max() / want.abs().max()
-        assert err <= 1e-5, (name, float(err))
-    torch.testing.assert_close(r.grad, dy)
+    cmp = KC.Cmp()
+    KC.verify_linear(cmp, x, w, b, r, y, dy, KC.grads_of(x, w, b, r))
+    assert not cmp.failures, "\n".join(cmp.failures)
     # deterministic (split-token slabs are summed in a fixed order)
     w.grad = None
     x.grad = None
@@ -779,7 +698,6 @@ def test_fused_mlp_f32(M, D, Hd, math):
     stock torch fp32 ops it replaces (same exact-erf GELU): output and all six gradients.  math = 1: split products on the bf16
     MFMA, same tolerance."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(M + D)
     fc1, fc2 = torch.nn.Linear(D, Hd).to(dev), torch.nn.Linear(Hd, D).to(dev)
@@ -793,15 +711,10 @@ def test_fused_mlp_f32(M, D, Hd, math):
     assert ops.mlp_f32_usable(x, fc1, fc2)
     y = ops.mlp_f32(x, fc1, fc2, r, math)
     (y * dy).sum().backward()
-    got = [y, x.grad, r.grad, fc1.weight.grad, fc1.bias.grad, fc2.weight.grad, fc2.bias.grad]
-    xd, rd = x.detach().double().requires_grad_(True), r.detach().double().requires_grad_(True)
-    p = [t.detach().double().requires_grad_(True) for t in (fc1.weight, fc1.bias, fc2.weight, fc2.bias)]
-    ref = F.linear(F.gelu(F.linear(xd, p[0], p[1])), p[2], p[3]) + rd
-    (ref * dy.double()).sum().backward()
-    want = [ref, xd.grad, rd.grad, p[0].grad, p[1].grad, p[2].grad, p[3].grad]
-    for n, a, b in zip(["y", "dx", "dresid", "dW1", "db1", "dW2", "db2"], got, want):
-        err = (a.double() - b).abs().max().item() / max(b.abs().max().item(), 1e-9)
-        assert err <= 2e-5, (n, err)
+    ps = [fc1.weight, fc1.bias, fc2.weight, fc2.bias]
+    cmp = KC.Cmp()
+    KC.verify_mlp(cmp, x, r, ps, y, dy, KC.grads_of(x, r, *ps), math)
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("M,C", [(1, 256), (37, 768), (25120, 768), (130, 1024)])
@@ -809,7 +722,6 @@ def test_layernorm_f32(M, C):
     """fp32 rows through the HIP LayerNorm (reference precision): forward, dx with the fused skip gradient, dgamma, dbeta
     against fp64."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(M + C)
     x = (torch.randn(M, C, generator=g) * 2 + 0.5).to(dev).requires_grad_(True)
@@ -822,13 +734,9 @@ def test_layernorm_f32(M, C):
     dy = torch.randn(M, C, generator=g).to(dev)
     ds = torch.randn(M, C, generator=g).to(dev)
     ((y * dy).sum() + (skip * ds).sum()).backward()
-    xd = x.detach().double().requires_grad_(True)
-    wd, bd = ln.weight.detach().double().requires_grad_(True), ln.bias.detach().double().requires_grad_(True)
-    ref = F.layer_norm(xd, (C,), wd, bd, 1e-6)
-    ((ref * dy.double()).sum() + (xd * ds.double()).sum()).backward()
-    for n, a, b in (("y", y, ref), ("dx", x.grad, xd.grad), ("dgamma", ln.weight.grad, wd.grad), ("dbeta", ln.bias.grad, bd.grad)):
-        err = (a.double() - b).abs().max() / b.abs().max()
-        assert err <= 2e-5, (n, float(err))
+    cmp = KC.Cmp()
+    KC.verify_layernorm(cmp, x, ln.weight, ln.bias, ln.eps, y, skip, dy, ds, KC.grads_of(x, ln.weight, ln.bias))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("M,C,N", [(2 * 785, 768, 2304), (300, 256, 576), (130, 1024, 256), (64, 512, 96)])
@@ -839,7 +747,6 @@ def test_layernorm_image_f32(M, C, N):
     image pass).  Row counts that are not multiples of 32 / 128: the image's padding rows must be ZERO (the weight gradient contracts
     over them) -- the allocator is primed with NaNs so that unwritten rows would show."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(M + C)
     x = (torch.randn(M, C, generator=g) * 2 + 0.5).to(dev).requires_grad_(True)
@@ -859,15 +766,10 @@ def test_layernorm_image_f32(M, C, N):
     ((y * dy).sum() + (skip * ds).sum()).backward()
     got = [y.detach(), x.grad.clone(), ln.weight.grad.clone(), ln.bias.grad.clone(), lin.weight.grad.clone(), lin.bias.grad.clone()]
     assert all(torch.isfinite(t).all() for t in got)
-    xd = x.detach().double().requires_grad_(True)
-    ps = [p.detach().double().requires_grad_(True) for p in (ln.weight, ln.bias, lin.weight, lin.bias)]
-    ref = F.linear(F.layer_norm(xd, (C,), ps[0], ps[1], 1e-6), ps[2], ps[3])
-    ((ref * dy.double()).sum() + (xd * ds.double()).sum()).backward()
-    want = [ref, xd.grad] + [p.grad for p in ps]
+    cmp = KC.Cmp()
+    KC.verify_ln_consumer(cmp, x, ln, "linear", [lin.weight, lin.bias], y, dy, skip, ds, got[1:])
+    assert not cmp.failures, "\n".join(cmp.failures)
     names = ("y", "dx", "dgamma", "dbeta", "dW", "db")
-    for n, a, b in zip(names, got, want):
-        err = (a.double() - b).abs().max() / b.abs().max()
-        assert err <= 2e-5, (n, float(err))
     # the two-kernel path: same numbers up to the rounding of the row statistics (another summation order)
     for p in (x, ln.weight, ln.bias, lin.weight, lin.bias):
         p.grad = None
@@ -885,12 +787,10 @@ def test_layernorm_image_f32(M, C, N):
     h, skip, hi = ops.layer_norm_image(x, ln)
     z = ops.mlp_f32(h, lin, fc2, skip, 1, hi)
     (z * ds).sum().backward()
-    ps = [p.detach().double().requires_grad_(True) for p in (x, ln.weight, ln.bias, lin.weight, lin.bias, fc2.weight, fc2.bias)]
-    zr = ps[0] + F.linear(F.gelu(F.linear(F.layer_norm(ps[0], (C,), ps[1], ps[2], 1e-6), ps[3], ps[4])), ps[5], ps[6])
-    (zr * ds.double()).sum().backward()
-    for n, a, b in [("z", z, zr)] + [("g%d" % i, p.grad, q.grad) for i, (p, q) in enumerate(zip((x, ln.weight, ln.bias, lin.weight, lin.bias, fc2.weight, fc2.bias), ps))]:
-        err = (a.double() - b).abs().max() / b.abs().max()
-        assert err <= 3e-5, (n, float(err))
+    ps = [lin.weight, lin.bias, fc2.weight, fc2.bias]
+    cmp = KC.Cmp()
+    KC.verify_ln_consumer(cmp, x, ln, "mlp", ps, z, ds, skip, None, KC.grads_of(x, ln.weight, ln.bias, *ps))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("B,D,h,w,P", [(4, 768, 28, 28, 1), (3, 192, 14, 14, 2), (2, 100, 5, 7, 1), (32, 768, 28, 28, 1)])
@@ -909,13 +809,9 @@ def test_tokens_assembly(B, D, h, w, P):
     tok = ops.tokens(y, bias, prefix, pos)
     dtok = torch.randn(tok.shape, generator=g).to(dev)
     (tok * dtok).sum().backward()
-    got = [tok.detach(), y.grad, bias.grad, prefix.grad, pos.grad]
-    y2, b2, p2, pos2 = (t.detach().clone().requires_grad_(True) for t in (y, bias, prefix, pos))
-    ref = torch.cat([p2.unsqueeze(0).expand(B, -1, -1), (y2 + b2.view(1, -1, 1, 1)).flatten(2).transpose(1, 2)], dim=1) + pos2
-    (ref * dtok).sum().backward()
-    assert torch.equal(got[0], ref) and torch.equal(got[1], y2.grad)
-    for n, a, b in (("dbias", got[2], b2.grad), ("dprefix", got[3], p2.grad), ("dpos", got[4], pos2.grad)):
-        assert (a - b).abs().max() <= 2e-6 * b.abs().max() * B ** 0.5, n
+    cmp = KC.Cmp()
+    KC.verify_tokens(cmp, y, bias, prefix, pos, tok, dtok, KC.grads_of(y, bias, prefix, pos))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("shape", [(2, 8, 16, 24), (3, 5, 9, 13), (1, 4, 7, 16), (2, 256, 112, 112)])
@@ -929,10 +825,9 @@ def test_subsample2(shape):
     y = ops.subsample2(x)
     dy = torch.randn(y.shape, generator=g).to(dev)
     (y * dy).sum().backward()
-    x2 = x.detach().clone().requires_grad_(True)
-    ref = x2[:, :, ::2, ::2].contiguous()
-    (ref * dy).sum().backward()
-    assert torch.equal(y, ref) and torch.equal(x.grad, x2.grad)
+    cmp = KC.Cmp()
+    KC.verify_subsample2(cmp, x, y, dy, KC.grads_of(x))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 def test_weight_std_all_f32():
@@ -945,13 +840,9 @@ def test_weight_std_all_f32():
     outs = ops.weight_std_all(ws)
     gs = [torch.randn(s, generator=g).to(dev) for s in shapes]
     sum((o * gi).sum() for o, gi in zip(outs, gs)).backward()
-    for w, o, gi in zip(ws, outs, gs):
-        wd = w.detach().double().requires_grad_(True)
-        std, mean = torch.std_mean(wd, dim=[1, 2, 3], keepdim=True, unbiased=False)
-        ref = (wd - mean) / (std + 1e-5)
-        (ref * gi.double()).sum().backward()
-        assert (o.double() - ref).abs().max() <= 1e-5 * ref.abs().max()
-        assert (w.grad.double() - wd.grad).abs().max() <= 5e-5 * wd.grad.abs().max()
+    cmp = KC.Cmp()
+    KC.verify_weight_std(cmp, ws, outs, gs, KC.grads_of(*ws))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("N,C,H,W", [(2, 64, 8, 8), (2, 1024, 28, 28), (2, 512, 56, 56), (2, 128, 112, 112), (2, 256, 112, 112), (1, 256, 128, 128),
@@ -992,7 +883,6 @@ def test_groupnorm_f32(N, C, H, W, act):
     groups that are register-resident in both directions (512 x 56^2, 128 x 112^2), a group too large for either (256 x 128^2,
     the COCO 512^2 geometry: streamed) and tiny groups (3 x 36)."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(C + H)
     x = (torch.randn(N, C, H, W, generator=g) * 1.7 + 0.3).to(dev).requires_grad_(True)
@@ -1003,20 +893,9 @@ def test_groupnorm_f32(N, C, H, W, act):
     y = ops.groupnorm_act(x, w, b, act, r)
     dy = torch.randn(N, C, H, W, generator=g).to(dev)
     (y * dy).sum().backward()
-    xd, wd, bd = (t.detach().double().requires_grad_(True) for t in (x, w, b))
-    ref = F.group_norm(xd, 32, wd, bd, 1e-5)
-    if r is not None:
-        rd = r.detach().double().requires_grad_(True)
-        ref = ref + rd
-    if act != "none":
-        ref = ref * (y.detach() > 0).double()               # the kernel's own mask: elements within 1e-7 of 0 may differ
-    (ref * dy.double()).sum().backward()
-    assert (y.double() - ref).abs().max() <= 1e-5 * ref.abs().max()
-    assert (x.grad.double() - xd.grad).abs().max() <= 2e-5 * xd.grad.abs().max()
-    assert (w.grad.double() - wd.grad).abs().max() <= 2e-5 * wd.grad.abs().max() + 1e-6
-    assert (b.grad.double() - bd.grad).abs().max() <= 2e-5 * bd.grad.abs().max() + 1e-6
-    if r is not None:
-        assert (r.grad.double() - rd.grad).abs().max() <= 1e-6 * rd.grad.abs().max()
+    cmp = KC.Cmp()
+    KC.verify_groupnorm(cmp, x, w, b, r, act, y, dy, KC.grads_of(x, w, b, r))
+    assert not cmp.failures, "\n".join(cmp.failures)
     # deterministic
     x2 = x.detach().clone().requires_grad_(True)
     y2 = ops.groupnorm_act(x2, w.detach(), b.detach(), act, r.detach() if r is not None else None)
@@ -1033,7 +912,6 @@ def test_conv1x1_f32(N, cin, cout, H, W, math):
     multiple of the 32-deep chunk (register-staged kernel for the weight gradient), cout = 64 fills half a tile.  math = 1: split
     products on the bf16 MFMA (the LDS-DMA shapes; the others stay on the exact kernels), same tolerance."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(cin + cout + H)
     x = torch.randn(N, cin, H, W, generator=g).to(dev).requires_grad_(True)
@@ -1043,12 +921,9 @@ def test_conv1x1_f32(N, cin, cout, H, W, math):
     dy = torch.randn(N, cout, H, W, generator=g).to(dev)
     ds = torch.randn(N, cin, H, W, generator=g).to(dev)
     ((y * dy).sum() + (skip * ds).sum()).backward()
-    xd, wd = x.detach().double().requires_grad_(True), w.detach().double().requires_grad_(True)
-    ref = F.conv2d(xd, wd)
-    ((ref * dy.double()).sum() + (xd * ds.double()).sum()).backward()
-    for n, a, b in (("y", y, ref), ("dx", x.grad, xd.grad), ("dw", w.grad, wd.grad)):
-        err = (a.double() - b).abs().max() / b.abs().max()
-        assert err <= 1e-5, (n, float(err))
+    cmp = KC.Cmp()
+    KC.verify_conv1x1(cmp, x, w, y, skip, dy, ds, KC.grads_of(x, w))
+    assert not cmp.failures, "\n".join(cmp.failures)
 
 
 @pytest.mark.parametrize("N,C,H,W,act", [(2, 1024, 24, 24, "add_relu"), (2, 256, 48, 48, "relu"), (1, 256, 96, 96, "none"), (2, 64, 96, 96, "relu")])
@@ -1057,7 +932,6 @@ def test_groupnorm_f32_small_launch_parts(N, C, H, W, act):
     (two launches, acr_groupnorm_fwd_f32 with ws) -- same values as the one-workgroup-per-group kernel up to the order of the
     fp32 sums, vs float64."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(C + H)
     x = (torch.randn(N, C, H, W, generator=g) * 2 + 0.5).to(dev)
@@ -1069,13 +943,10 @@ def test_groupnorm_f32_small_launch_parts(N, C, H, W, act):
         y = ops.groupnorm_act(x, gw, gb, act, r)            # no gradient needed: the parts path
     xg = x.clone().requires_grad_(True)
     y1 = ops.groupnorm_act(xg, gw, gb, act, r)               # gradient needed: one workgroup per (sample, group)
-    ref = F.group_norm(x.double(), 32, gw.double(), gb.double(), 1e-5)
-    if act == "add_relu":
-        ref = F.relu(ref + r.double())
-    elif act == "relu":
-        ref = F.relu(ref)
-    assert (y.double() - ref).abs().max() <= 2e-5 * max(1.0, float(ref.abs().max()))
-    assert (y - y1).abs().max() <= 2e-5 * max(1.0, float(ref.abs().max()))
+    cmp = KC.Cmp()
+    ref = KC.verify_groupnorm(cmp, x, gw, gb, r, act, y, None, [])
+    assert not cmp.failures, "\n".join(cmp.failures)
+    assert (y - y1).abs().max() <= KC.TOL["groupnorm_forward_only"] * max(1.0, float(ref.abs().max()))
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 200, 100), (128, 128, 16), (1000, 768, 772), (2500, 64, 3072), (37, 260, 40)])
@@ -1223,7 +1094,6 @@ def test_conv3x3_split(N, cin, cout, H, W, wimg, monkeypatch):
     forward / input-gradient launches take the packed weight as a split-product image (acr_conv3x3_x3, the default) or as fp32
     (acr_conv3x3_f32: both operands split in registers)."""
     from acr_wsss_amd import ops
-    import torch.nn.functional as F
     monkeypatch.setattr(ops, "CONV3X3_WIMG", wimg)
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(cin + cout + H)
@@ -1233,18 +1103,15 @@ def test_conv3x3_split(N, cin, cout, H, W, wimg, monkeypatch):
     y = ops.conv3x3(x, w)
     dy = torch.randn(N, cout, H, W, generator=g).to(dev)
     (y * dy).sum().backward()
-    xd, wd = x.detach().double().requires_grad_(True), w.detach().double().requires_grad_(True)
-    ref = F.conv2d(xd, wd, padding=1)
-    (ref * dy.double()).sum().backward()
-    for n, a, b in (("y", y, ref), ("dx", x.grad, xd.grad), ("dw", w.grad, wd.grad)):
-        err = (a.double() - b).abs().max() / b.abs().max()
-        assert err <= 1e-5, (n, float(err))
+    cmp = KC.Cmp()
+    KC.verify_conv_same(cmp, x, w, 1, y, dy, KC.grads_of(x, w))
+    assert not cmp.failures, "\n".join(cmp.failures)
     # the border is exact zero padding, not a neighbouring row / channel / sample: a one-hot input's response is the flipped kernel
     x1 = torch.zeros(1, cin, H, W, device=dev)
     x1[0, 3, 0, 0] = 1.0
     x1[0, 5, H - 1, W - 1] = 1.0
     y1 = ops.conv3x3(x1, w.detach())
-    r1 = F.conv2d(x1.double(), w.detach().double(), padding=1)
+    r1 = KC.conv_same_ref(x1.double(), w.detach().double(), 1)
     assert (y1.double() - r1).abs().max() <= 1e-6 * r1.abs().max()
     assert torch.equal(y1 == 0, r1 == 0)
     # bitwise reproducible (fixed slab order in the weight gradient)
@@ -1333,16 +1200,7 @@ def test_conv3x3_reads_nothing_outside_its_input():
     assert (dwp.permute(0, 3, 1, 2).double() - wdbl.grad).abs().max() <= 1e-5 * wdbl.grad.abs().max()
 
 
-def _same_conv_ref(xd, wd, stride):
-    """fp64 TF-SAME convolution as the reference computes it: F.pad (odd pixel right / bottom) + F.conv2d (std_conv.py:56-65)."""
-    import math
-    import torch.nn.functional as F
-    k = wd.shape[2]
-    pads = []
-    for n in (xd.shape[3], xd.shape[2]):
-        t = max((math.ceil(n / stride) - 1) * stride + k - n, 0)
-        pads += [t // 2, t - t // 2]
-    return F.conv2d(F.pad(xd, pads), wd, stride=stride)
+_same_conv_ref = KC.conv_same_ref
 
 
 @pytest.mark.parametrize("N,cin,cout,k,H,W,grads", [(2, 128, 128, 3, 112, 112, True), (2, 256, 256, 3, 56, 56, True), (3, 32, 48, 3, 40, 64, True),
@@ -1363,20 +1221,13 @@ def test_conv_s2_split(N, cin, cout, k, H, W, grads):
     with torch.set_grad_enabled(grads):
         assert ops.conv_s2_fusable(x, w, 2, 1) and not ops.conv_s2_fusable(x, w, 2, 0) and not ops.conv_s2_fusable(x, w, 1, 1)
         y = ops.conv_s2(x, w)
-    xd, wd = x.detach().double().requires_grad_(x.requires_grad), w.detach().double().requires_grad_(grads)
-    ref = _same_conv_ref(xd, wd, 2)
-    assert y.shape == ref.shape
-    pairs = [("y", y, ref)]
+    dy = None
     if grads:
         dy = torch.randn(y.shape, generator=g).to(dev)
         (y * dy).sum().backward()
-        (ref * dy.double()).sum().backward()
-        pairs.append(("dw", w.grad, wd.grad))
-        if x.requires_grad:
-            pairs.append(("dx", x.grad, xd.grad))
-    for n, a, b in pairs:
-        err = (a.double() - b).abs().max() / b.abs().max()
-        assert err <= 1e-5, (n, float(err))
+    cmp = KC.Cmp()
+    KC.verify_conv_same(cmp, x, w, 2, y, dy, KC.grads_of(x, w))
+    assert not cmp.failures, "\n".join(cmp.failures)
     # exact zero padding: a one-hot input answers with single kernel entries, zero elsewhere
     x1 = torch.zeros(1, cin, H, W, device=dev)
     x1[0, 1, 0, 0] = 1.0
@@ -1696,11 +1547,9 @@ def test_mlsm_loss(N, C, pitch):
     y = (torch.rand(N, C, generator=g) > 0.7).float().to(dev)
     loss = ops.mlsm_loss(x, y)
     (loss * 2.5).backward()
-    xd = big[:, :C].double().detach().requires_grad_(True)
-    ref = F.multilabel_soft_margin_loss(xd, y.double())
-    (ref * 2.5).backward()
-    assert abs(float(loss) - float(ref)) <= 2e-6 * abs(float(ref))
-    assert (x.grad.double() - xd.grad).abs().max() <= 2e-6 * xd.grad.abs().max()
+    cmp = KC.Cmp()
+    KC.verify_mlsm(cmp, x, y, 2.5, loss, KC.grads_of(x))
+    assert not cmp.failures, "\n".join(cmp.failures)
     stock = F.multilabel_soft_margin_loss(big[:, :C].detach(), y)
     assert abs(float(loss) - float(stock)) <= 1e-6 * abs(float(stock))
 
