@@ -184,6 +184,10 @@ SIGNATURES = {
     "acr_pamr_affinity": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int32), c_int32, c_void_p, c_void_p]),
     "acr_pamr_propagate": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int32), c_int32,
                                      c_void_p]),
+    "acr_eval_sweep_f32": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                     c_void_p, c_void_p]),
+    "acr_eval_sweep_finish": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "acr_eval_confusion_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

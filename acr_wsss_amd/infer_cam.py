@@ -39,7 +39,7 @@ def infer_cam_images(model, imgs, labels, out_hws, **kw):
 
 
 def launch_cam_images(model, imgs, labels, out_hws, start_layer=10, func="grad", aff=True, scales=(1,), truncate=True,
-                      batch_flips=True, concurrent_scales=None):
+                      batch_flips=True, concurrent_scales=None, on_device=None):
     """Enqueue the CAM generation of a batch of same-sized network inputs and return ``collect``, a callable that waits for
     THIS batch's results only and returns them -- so a caller walking a list (infer_cam_list) can enqueue the next images
     before collecting the previous ones and the GPU never waits for the host between images.
@@ -51,7 +51,11 @@ def launch_cam_images(model, imgs, labels, out_hws, start_layer=10, func="grad",
 
     Samples never interact on this path (GroupNorm / LayerNorm / attention are per sample), so images -- and, with
     ``batch_flips``, the flipped and the plain pass of a scale -- share one forward, and one backward per class rank
-    k serves the k-th positive class of every image: d(sum_i logit[i, c_i^k]) / d tokens is block-diagonal in i."""
+    k serves the k-th positive class of every image: d(sum_i logit[i, c_i^k]) / d tokens is block-diagonal in i.
+
+    ``on_device(i, classes_i, norm_cam_i)``, if given, is called on the caller's stream for every image i with a positive class,
+    with its ascending class list and the normalised (n_classes, W, H) float32 CAMs as they sit on the device -- the very values
+    copied out afterwards -- before that image's device-to-host copies are enqueued.  It must not synchronise."""
     dev = imgs.device
     if concurrent_scales is None:
         concurrent_scales = CONCURRENT_SCALES
@@ -186,6 +190,8 @@ def launch_cam_images(model, imgs, labels, out_hws, start_layer=10, func="grad",
         pa = pa[classes[i]] if classes[i] else pa[:0]      # only the positive classes' planes are returned (and copied)
         pmin, pmax = pa.amin((1, 2), keepdim=True), pa.amax((1, 2), keepdim=True)
         patch_norm = (pa - pmin) / (pmax - pmin + 1e-5)
+        if on_device is not None and classes[i]:
+            on_device(i, classes[i], norm_cam)
         hc = torch.empty(norm_cam.shape, dtype=torch.float32, pin_memory=True)
         hp = torch.empty(patch_norm.shape, dtype=torch.float32, pin_memory=True)
         hc.copy_(norm_cam, non_blocking=True)
@@ -232,7 +238,7 @@ def shard_indices(n, rank=0, world=1):
 
 
 def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, out_crf=None, low_alpha=1, high_alpha=12,
-                   out_pamr=None, pamr_iter=10, pamr_dilations=(1, 2, 4, 8, 12, 24), **kw):
+                   out_pamr=None, pamr_iter=10, pamr_dilations=(1, 2, 4, 8, 12, 24), evaluate=None, **kw):
     """Shard ``items`` -- an indexable of (name, img (1,3,h,w), label (1,C), (W,H)[, orig uint8 (W,H,3)]) -- over ranks and
     write ``<out_cam>/<name>.npy`` in the reference's wire format: a pickled {class: float32 (W,H)} dict
     (infer_cam.py:227-228, read back by evaluation.py:23-25).  Returns {name: cam_dict} of this rank.
@@ -249,11 +255,19 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
     {0: background, class + 1: ...} layout, same fifth item element; both alphas share one affinity and one set of iterations.
     The defaults ``pamr_iter`` = 10 and ``pamr_dilations`` = (1, 2, 4, 8, 12, 24) are the PAMR paper's setting as remembered: the
     reference tree holds no PAMR call to take them from, so they are unverified; ``pamr()`` and ``PAMR`` keep the reference
-    module's own defaults (1 iteration, dilations [1]).  Images with no positive class are skipped, as for ``out_crf``."""
+    module's own defaults (1 iteration, dilations [1]).  Images with no positive class are skipped, as for ``out_crf``.
+    ``evaluate`` (an ``evaluation.CamEvaluation``; unset: nothing changes): score what this call produces against
+    ``evaluate.gt_of(name)`` on the device instead of reading the files back (the reference's evaluation.py step) -- the CAMs of
+    every image in ``evaluate.cam`` before they leave the GPU, and, with ``out_crf`` / ``out_pamr``, the label map of every
+    refined dict in ``evaluate.crf[alpha]`` / ``evaluate.pamr[alpha]``.  Images with no positive class are skipped; files and the
+    returned dict are those of a run without it; each rank fills its own ``evaluate`` and the caller merges the host counters."""
     dev = next(model.parameters()).device
     model.eval()
     results = {}
     mine = shard_indices(len(items), rank, world)
+    user_hook = kw.get("on_device")          # a caller's own hook keeps being called, after evaluate's
+    if evaluate is not None:
+        evaluate.bind(dev)
 
     def finish(grp, collect):
         for i, (cam_dict, _) in zip(grp, collect()):
@@ -268,7 +282,10 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
                 for alpha in (low_alpha, high_alpha):
                     folder = out_crf + ("_%s" % alpha)
                     os.makedirs(folder, exist_ok=True)
-                    np.save(os.path.join(folder, name + ".npy"), crf_with_alpha(cam_dict, alpha, np.asarray(items[i][4]), device=dev))
+                    refined_crf = crf_with_alpha(cam_dict, alpha, np.asarray(items[i][4]), device=dev)
+                    np.save(os.path.join(folder, name + ".npy"), refined_crf)
+                    if evaluate is not None:
+                        evaluate.score_labels("crf", alpha, name, refined_crf)
             if out_pamr is not None and cam_dict:
                 if len(items[i]) < 5:
                     raise ValueError("out_pamr needs the original uint8 image as items[i][4]")
@@ -279,6 +296,10 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
                     folder = out_pamr + ("_%s" % alpha)
                     os.makedirs(folder, exist_ok=True)
                     np.save(os.path.join(folder, name + ".npy"), refined[alpha])
+                    if evaluate is not None:
+                        evaluate.score_labels("pamr", alpha, name, refined[alpha])
+            if evaluate is not None:
+                evaluate.release(name)
             results[name] = cam_dict
 
     # one batch in flight behind the one being collected: the kernels of images i+1 are enqueued BEFORE the host blocks on the
@@ -290,6 +311,15 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
         while len(grp) < batch_size and pos + len(grp) < len(mine) and items[mine[pos + len(grp)]][1].shape == shape:
             grp.append(mine[pos + len(grp)])
         pos += len(grp)
+        # the hook only notes (index in grp, classes, CAMs on the device); they are scored once the whole group is enqueued, so
+        # that a group taken again after running out of memory is not counted twice
+        scored = []
+        if evaluate is not None:
+            def note(j, cls, cam, also=user_hook):
+                scored.append((j, cls, cam))
+                if also is not None:
+                    also(j, cls, cam)
+            kw["on_device"] = note
         try:
             imgs = torch.cat([items[i][1] for i in grp], dim=0).to(dev)
             labels = torch.cat([items[i][2] for i in grp], dim=0)
@@ -306,6 +336,8 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
             batch_size = max(1, len(grp) // 2)
             pos -= len(grp)
             continue
+        for j, cls, cam in scored:
+            evaluate.score_cam(items[grp[j]][0], cls, cam)
         if pending is not None:
             finish(*pending)
         pending = (grp, collect)

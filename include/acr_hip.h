@@ -602,6 +602,30 @@ int acr_pamr_affinity(const float* x, int32_t B, int32_t K, int32_t H, int32_t W
 int acr_pamr_propagate(const float* w, const float* mask_in, float* mask_out, int32_t B, int32_t C, int32_t H, int32_t W,
                        const int32_t* dilations, int32_t n_dil, void* stream);
 
+/* ---- CAM evaluation on the device (evaluation.py:19-52: the TP / P / T counters behind the mIoU of every background threshold;
+ * --type png mode and tool/metrics.py:36-41 Evaluator._generate_matrix: the confusion matrix of a label map) ----
+ * All counters are int64 and exact: integer sums, bit-identical run to run.  2 <= num_cls <= 128 (background included).
+ * acr_eval_sweep_f32 (evaluation.py:27-49, for all thresholds in one pass): cams (n, h, w) fp32 contiguous on the device;
+ *   `classes` is a HOST array of n strictly ascending 0-based class indices in [0, num_cls - 1), read during the call,
+ *   1 <= n <= num_cls - 1; gt (h, w) uint8 on the device; thresholds (nt) fp32 on the device, strictly ascending (the CALLER's
+ *   contract, not checked here), 1 <= nt <= 256.  Per pixel with gt < num_cls (255 = ignore; a gt in num_cls..254 is ignored
+ *   too -- a deviation: the reference counts such a pixel in P only, VOC and COCO hold none): v_c = the value of class c's plane,
+ *   exactly 0.0f for a class without one; m = max_c v_c; a = 1 + the smallest c with v_c == m (np.argmax: the first maximum);
+ *   kfg = #{k : thresholds[k] < m} compared in fp32.  Then, ACCUMULATED into raw:
+ *     NVALID += 1;  T[gt] += 1;  FG[kfg][a] += 1;  HIT[kfg][a] += 1 if a == gt;  BG[kfg] += 1 if gt == 0
+ *   raw = FG (nt + 1, num_cls) | HIT (nt + 1, num_cls) | BG (nt + 1) | T (num_cls) | NVALID (1), 2 (nt + 1) num_cls + nt + num_cls + 2
+ *   values.  Inputs are finite: NaN is outside the contract.
+ * acr_eval_sweep_finish (evaluation.py:37-52): a pure function of raw that WRITES TP and P, both (nt, num_cls):
+ *   c >= 1: P[k][c] = sum_{j > k} FG[j][c], TP[k][c] = sum_{j > k} HIT[j][c];
+ *   P[k][0] = NVALID - sum_{c >= 1} P[k][c];  TP[k][0] = sum_{j <= k} BG[j].
+ * acr_eval_confusion_u8: pred, gt (n_pixels) uint8 on the device; conf (num_cls, num_cls + 1), ACCUMULATED into:
+ *   conf[gt][min(pred, num_cls)] += 1 for gt < num_cls (1 <= num_cls <= 128); the last column collects predictions outside
+ *   the label range, every other gt is ignored.  T = row sums, P = sums of the first num_cls columns, TP = diagonal. */
+int acr_eval_sweep_f32(const float* cams, const int32_t* classes, int32_t n, const uint8_t* gt, int32_t h, int32_t w,
+                       const float* thresholds, int32_t nt, int32_t num_cls, int64_t* raw, void* stream);
+int acr_eval_sweep_finish(const int64_t* raw, int32_t nt, int32_t num_cls, int64_t* TP, int64_t* P, void* stream);
+int acr_eval_confusion_u8(const uint8_t* pred, const uint8_t* gt, int64_t n_pixels, int32_t num_cls, int64_t* conf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
