@@ -188,6 +188,10 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "acr_eval_sweep_finish": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "acr_eval_confusion_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "acr_pseudo_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "acr_pseudo_label_f32": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "acr_pseudo_compose": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                     ctypes.c_double, c_float, ctypes.c_double, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

@@ -91,6 +91,11 @@ class _Kernel:
 
 def crf_inference(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
     """tool/imutils.py:345-362.  img (h, w, 3) uint8, probs (labels, h, w) -> Q (labels, h, w) float32 numpy array."""
+    return crf_inference_device(img, probs, t, scale_factor, labels, device).cpu().numpy()
+
+
+def crf_inference_device(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
+    """``crf_inference`` with Q left where it was computed: a (labels, h, w) float32 tensor on ``device``."""
     lib = L.load()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -111,17 +116,28 @@ def crf_inference(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
             for k, m in zip(kernels, msg):
                 k.apply(q, out=m)
             L.check(lib.acr_crf_update(L.ptr(unary), L.ptr(msg[0]), L.ptr(msg[1]), L.ptr(q), n, labels, L.stream_ptr()), "acr_crf_update")
-    return q.reshape(labels, h, w).cpu().numpy()
+    return q.reshape(labels, h, w)
 
 
 def crf_with_alpha(cam_dict, alpha, orig_img, device="cuda"):
     """infer_cam.py:27-40: {class: cam (h, w)} -> {0: background, class + 1: ...} after the CRF, background score
     (1 - max_c cam)^alpha."""
+    classes, refined = crf_with_alpha_device(cam_dict, alpha, orig_img, device=device)
+    return score_dict(classes, refined.cpu().numpy())
+
+
+def crf_with_alpha_device(cam_dict, alpha, orig_img, device="cuda"):
+    """``crf_with_alpha`` with the refined scores left on the device: (classes in the dict's order, (1 + len(classes), h, w)
+    float32 tensor, plane 0 the background and plane i + 1 class ``classes[i]``) -- what pseudo.seg_label takes."""
     classes = list(cam_dict.keys())
     cams = np.stack([cam_dict[c] for c in classes], axis=0)
     background = np.power(1 - cams.max(axis=0, keepdims=True), alpha)
     scores = np.concatenate((background, cams), axis=0)
-    refined = crf_inference(orig_img, scores, labels=scores.shape[0], device=device)
+    return classes, crf_inference_device(orig_img, scores, labels=scores.shape[0], device=device)
+
+
+def score_dict(classes, refined):
+    """{0: background, class + 1: ...} of a host (1 + len(classes), h, w) array: the layout infer_cam.py:38-40 writes."""
     out = {0: refined[0]}
     for i, c in enumerate(classes):
         out[c + 1] = refined[i + 1]

@@ -367,9 +367,11 @@ def label_map(score_dict):
 
 class CamEvaluation:
     """What ``infer_cam_list(..., evaluate=...)`` fills while it walks its list: ``cam``, the threshold sweep of the CAMs scored on
-    the device before they are copied out, and ``crf`` / ``pamr``, {alpha: DeviceLabelCounters} of the refined label maps (created
-    when the first one arrives).  ``gt_of(name)`` returns the uint8 (W, H) ground truth of an item, 255 = ignore.  Counters live
-    on the model's device; a sharded run gives each rank its own and the caller merges their ``to_host()`` results."""
+    the device before they are copied out, ``crf`` / ``pamr``, {alpha: DeviceLabelCounters} of the refined label maps (created
+    when the first one arrives), and ``pseudo``, the DeviceLabelCounters of the pseudo-labels written with ``out_pseudo`` (None
+    without it; a pseudo-label of 255 falls into the counters' last column, outside every class).  ``gt_of(name)`` returns the
+    uint8 (W, H) ground truth of an item, 255 = ignore.  Counters live on the model's device; a sharded run gives each rank its own
+    and the caller merges their ``to_host()`` results."""
 
     def __init__(self, gt_of, thresholds=None, num_cls=21):
         self.gt_of = gt_of
@@ -377,6 +379,7 @@ class CamEvaluation:
         self.num_cls = int(num_cls)
         self.cam = None
         self.crf, self.pamr = {}, {}
+        self.pseudo = None
         self._gts = {}
         self._free = {}        # shape -> [(pinned buffer, event after its last upload)]: buffers of released images, reused
 
@@ -426,3 +429,13 @@ class CamEvaluation:
         if alpha not in table:
             table[alpha] = DeviceLabelCounters(self.num_cls, self.cam.device)
         table[alpha].add(label_map(score_dict), self.gt_device(name))
+
+    def bind_pseudo(self):
+        """Create the pseudo-label counters next to the CAM counters (once; infer_cam_list calls this with ``out_pseudo``)."""
+        if self.pseudo is None:
+            self.pseudo = DeviceLabelCounters(self.num_cls, self.cam.device)
+        return self.pseudo
+
+    def score_pseudo(self, name, label):
+        """label: the uint8 (W, H) pseudo-label as it sits on the device (pseudo.seg_label)."""
+        self.bind_pseudo().add(label, self.gt_device(name))

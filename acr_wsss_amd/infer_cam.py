@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, pseudo
 from .backbone import pass_graph
 
 
@@ -238,7 +238,8 @@ def shard_indices(n, rank=0, world=1):
 
 
 def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, out_crf=None, low_alpha=1, high_alpha=12,
-                   out_pamr=None, pamr_iter=10, pamr_dilations=(1, 2, 4, 8, 12, 24), evaluate=None, **kw):
+                   out_pamr=None, pamr_iter=10, pamr_dilations=(1, 2, 4, 8, 12, 24), evaluate=None, out_pseudo=None,
+                   pseudo_source="crf", pseudo_uncertain=False, pseudo_bg_alpha=36, **kw):
     """Shard ``items`` -- an indexable of (name, img (1,3,h,w), label (1,C), (W,H)[, orig uint8 (W,H,3)]) -- over ranks and
     write ``<out_cam>/<name>.npy`` in the reference's wire format: a pickled {class: float32 (W,H)} dict
     (infer_cam.py:227-228, read back by evaluation.py:23-25).  Returns {name: cam_dict} of this rank.
@@ -260,7 +261,17 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
     ``evaluate.gt_of(name)`` on the device instead of reading the files back (the reference's evaluation.py step) -- the CAMs of
     every image in ``evaluate.cam`` before they leave the GPU, and, with ``out_crf`` / ``out_pamr``, the label map of every
     refined dict in ``evaluate.crf[alpha]`` / ``evaluate.pamr[alpha]``.  Images with no positive class are skipped; files and the
-    returned dict are those of a run without it; each rank fills its own ``evaluate`` and the caller merges the host counters."""
+    returned dict are those of a run without it; each rank fills its own ``evaluate`` and the caller merges the host counters.
+    ``out_pseudo`` (unset: nothing changes): also write ``<out_pseudo>/<name>.png``, the pseudo-label mask of every image of this
+    rank -- the reference's compute_seg_label_rrm (myTool.py:674-744) in ``pseudo.seg_label`` -- from the refinement named by
+    ``pseudo_source`` ("crf" or "pamr") at ``low_alpha`` / ``high_alpha`` of this call: a ``P``-mode PNG with the VOC colour map
+    holding the labels 0..C and 255 (``pseudo.save_label_png``).  The refinement runs once per image whether or not ``out_crf`` /
+    ``out_pamr`` ask for its files as well, and its scores reach ``seg_label`` on the device; needs the original image as the
+    fifth item element.  ``pseudo_uncertain``: apply the confidence rule (``ignore_uncertain``), with ``pseudo_bg_alpha`` as its
+    background exponent.  An image with no positive class gets an all-background PNG and is not scored; with ``evaluate`` the
+    other pseudo-labels are counted in ``evaluate.pseudo`` before they leave the GPU."""
+    if out_pseudo is not None and pseudo_source not in ("crf", "pamr"):
+        raise ValueError("pseudo_source must be 'crf' or 'pamr', got %r" % (pseudo_source,))
     dev = next(model.parameters()).device
     model.eval()
     results = {}
@@ -268,6 +279,10 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
     user_hook = kw.get("on_device")          # a caller's own hook keeps being called, after evaluate's
     if evaluate is not None:
         evaluate.bind(dev)
+        if out_pseudo is not None:
+            evaluate.bind_pseudo()
+    pseudo_crf = out_pseudo is not None and pseudo_source == "crf"
+    pseudo_pamr = out_pseudo is not None and pseudo_source == "pamr"
 
     def finish(grp, collect):
         for i, (cam_dict, _) in zip(grp, collect()):
@@ -275,29 +290,59 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
             if out_cam is not None:
                 os.makedirs(out_cam, exist_ok=True)
                 np.save(os.path.join(out_cam, name + ".npy"), cam_dict)
-            if out_crf is not None and cam_dict:
+            if out_pseudo is not None and cam_dict and len(items[i]) < 5:
+                raise ValueError("out_pseudo needs the original uint8 image as items[i][4]")
+            low_high = None                              # the refined scores of the pseudo-label's source, on the device
+            if (out_crf is not None or pseudo_crf) and cam_dict:
                 if len(items[i]) < 5:
                     raise ValueError("out_crf needs the original uint8 image as items[i][4] (infer_cam.py:217)")
-                from .crf import crf_with_alpha
+                from .crf import crf_with_alpha_device, score_dict
+                on_dev = []
                 for alpha in (low_alpha, high_alpha):
-                    folder = out_crf + ("_%s" % alpha)
-                    os.makedirs(folder, exist_ok=True)
-                    refined_crf = crf_with_alpha(cam_dict, alpha, np.asarray(items[i][4]), device=dev)
-                    np.save(os.path.join(folder, name + ".npy"), refined_crf)
-                    if evaluate is not None:
-                        evaluate.score_labels("crf", alpha, name, refined_crf)
-            if out_pamr is not None and cam_dict:
+                    classes, scores = crf_with_alpha_device(cam_dict, alpha, np.asarray(items[i][4]), device=dev)
+                    on_dev.append(scores)
+                    if out_crf is not None:
+                        folder = out_crf + ("_%s" % alpha)
+                        os.makedirs(folder, exist_ok=True)
+                        refined_crf = score_dict(classes, scores.cpu().numpy())
+                        np.save(os.path.join(folder, name + ".npy"), refined_crf)
+                        if evaluate is not None:
+                            evaluate.score_labels("crf", alpha, name, refined_crf)
+                if pseudo_crf:
+                    low_high = on_dev
+            if (out_pamr is not None or pseudo_pamr) and cam_dict:
                 if len(items[i]) < 5:
                     raise ValueError("out_pamr needs the original uint8 image as items[i][4]")
-                from .pamr import pamr_with_alpha
-                refined = pamr_with_alpha(cam_dict, (low_alpha, high_alpha), np.asarray(items[i][4]), num_iter=pamr_iter,
-                                          dilations=pamr_dilations, device=dev)
-                for alpha in (low_alpha, high_alpha):
-                    folder = out_pamr + ("_%s" % alpha)
-                    os.makedirs(folder, exist_ok=True)
-                    np.save(os.path.join(folder, name + ".npy"), refined[alpha])
+                from .pamr import pamr_with_alpha_device
+                from .crf import score_dict
+                classes, scores = pamr_with_alpha_device(cam_dict, (low_alpha, high_alpha), np.asarray(items[i][4]), num_iter=pamr_iter,
+                                                         dilations=pamr_dilations, device=dev)
+                n = 1 + len(classes)
+                if out_pamr is not None:
+                    host = scores.cpu().numpy()
+                    for ai, alpha in enumerate((low_alpha, high_alpha)):
+                        folder = out_pamr + ("_%s" % alpha)
+                        os.makedirs(folder, exist_ok=True)
+                        refined = score_dict(classes, host[ai * n:(ai + 1) * n])
+                        np.save(os.path.join(folder, name + ".npy"), refined)
+                        if evaluate is not None:
+                            evaluate.score_labels("pamr", alpha, name, refined)
+                if pseudo_pamr:
+                    low_high = [scores[:n], scores[n:]]
+            if out_pseudo is not None:
+                os.makedirs(out_pseudo, exist_ok=True)
+                if cam_dict:
+                    classes = list(cam_dict.keys())          # ascending: launch_cam_images walks the label vector
+                    cams = np.stack([cam_dict[c] for c in classes]).astype(np.float32, copy=False)
+                    with torch.cuda.device(dev):
+                        label = pseudo.seg_label(cams, classes, low_high[0], low_high[1], ignore_uncertain=pseudo_uncertain,
+                                                 bg_alpha=pseudo_bg_alpha, num_classes=items[i][2].shape[1], device=dev)
                     if evaluate is not None:
-                        evaluate.score_labels("pamr", alpha, name, refined[alpha])
+                        evaluate.score_pseudo(name, label)
+                    label = label.cpu().numpy()
+                else:
+                    label = np.zeros(tuple(items[i][3]), np.uint8)
+                pseudo.save_label_png(os.path.join(out_pseudo, name + ".png"), label)
             if evaluate is not None:
                 evaluate.release(name)
             results[name] = cam_dict

@@ -96,6 +96,23 @@ def pamr_with_alpha(cam_dict, alphas, orig_img, num_iter=1, dilations=(1,), devi
     depends on the image only and is computed once, and the planes of every alpha ride as channels through the same
     iterations.  orig_img: (h, w, 3) uint8, uploaded as it is and converted on the device (the weights are invariant under a
     positive per-channel affine map of the image, so the raw 0..255 values serve as well as the normalised ones)."""
+    alphas = list(alphas)
+    classes, refined = pamr_with_alpha_device(cam_dict, alphas, orig_img, num_iter, dilations, device)
+    refined = refined.cpu().numpy()
+    n = 1 + len(classes)
+    out = {}
+    for ai, a in enumerate(alphas):
+        d = {0: refined[ai * n]}
+        for i, c in enumerate(classes):
+            d[c + 1] = refined[ai * n + i + 1]
+        out[a] = d
+    return out
+
+
+def pamr_with_alpha_device(cam_dict, alphas, orig_img, num_iter=1, dilations=(1,), device="cuda"):
+    """``pamr_with_alpha`` with the refined scores left on the device: (classes in the dict's order, (len(alphas) * n, h, w)
+    float32 tensor with n = 1 + len(classes): planes [ai * n, (ai + 1) * n) are the background and the classes at alphas[ai]) --
+    what pseudo.seg_label takes."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise L.AcrHipError("pamr_with_alpha needs a GPU (no CPU path in the product)")
@@ -110,12 +127,4 @@ def pamr_with_alpha(cam_dict, alphas, orig_img, num_iter=1, dilations=(1,), devi
         raise ValueError("orig_img must be (h, w, 3) uint8 matching the cams %s, got %s %s" % (cams.shape[1:], tuple(img.shape), img.dtype))
     with torch.cuda.device(dev):
         x = img.to(dev).permute(2, 0, 1).to(torch.float32).contiguous()[None]
-        refined = pamr(x, torch.as_tensor(scores).to(dev)[None], num_iter, dilations)[0].cpu().numpy()
-    n = 1 + len(classes)
-    out = {}
-    for ai, a in enumerate(alphas):
-        d = {0: refined[ai * n]}
-        for i, c in enumerate(classes):
-            d[c + 1] = refined[ai * n + i + 1]
-        out[a] = d
-    return out
+        return classes, pamr(x, torch.as_tensor(scores).to(dev)[None], num_iter, dilations)[0]

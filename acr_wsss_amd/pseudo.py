@@ -1,0 +1,153 @@
+"""Pseudo-label masks from refined CAMs on the GPU: the reference's ``compute_seg_label_rrm`` (myTool.py:674-744) -- the label
+maps of the low- and high-alpha refinements (:705-706), their combination (:707-708, :732) and, with ``ignore_uncertain``, the
+confidence rule (:694-701, :710-735) applied by the line the reference keeps commented at :737 (live in its sibling at :109).
+All of it runs in csrc/pseudo.hip behind the C ABI (``acr_pseudo_label_f32``, ``acr_pseudo_compose``, ``acr_pseudo_ws_bytes``,
+include/acr_hip.h states the rule in full); there is no CPU path -- without the HIP library and a GPU these raise.  The result is
+an exact function of the inputs: uint8 labels 0..C and 255 (ignore), identical bits run to run.  One definition beyond the
+reference: a label of the low-alpha map whose class never wins the CAM argmax above ``cam_floor`` has no sure pixel (the reference
+raises IndexError there).  Only this rule is covered; the reference's saliency variants are not."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MAX_LABELS = 128                          # C + 1 <= 128 (include/acr_hip.h)
+
+
+def _class_array(classes, num_classes):
+    cl = [int(c) for c in classes]
+    if not cl:
+        raise ValueError("no classes: an image without a positive class has no scores to label")
+    if not 1 <= int(num_classes) <= MAX_LABELS - 1:
+        raise ValueError("num_classes=%d outside 1..%d" % (num_classes, MAX_LABELS - 1))
+    if any(c < 0 or c >= num_classes for c in cl):
+        raise ValueError("classes %s outside 0..%d" % (cl, num_classes - 1))
+    if any(b <= a for a, b in zip(cl, cl[1:])):
+        raise ValueError("classes %s must be strictly ascending (sorted, no duplicates)" % (cl,))
+    return (ctypes.c_int32 * len(cl))(*cl), len(cl)
+
+
+def _device_of(tensors, device):
+    """The GPU the call runs on: that of the first device tensor among ``tensors``, else ``device``; AcrHipError without one."""
+    for t in tensors:
+        if torch.is_tensor(t):
+            L.require_gpu(t)
+            return t.device
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise L.AcrHipError("pseudo-label composition needs a GPU (got device %r): there is no CPU path" % (device,))
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _planes(a, name, dev, n, hw=None):
+    """(n, W, H) contiguous float32 on ``dev``; numpy arrays are uploaded."""
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            raise ValueError("%s must be float32, got %s" % (name, a.dtype))
+        a = torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+    L.require_gpu(a)
+    if a.dtype != torch.float32 or not a.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 tensor, got %s with strides %s" % (name, a.dtype, tuple(a.stride())))
+    if a.device != dev:
+        raise ValueError("%s lies on %s, the other inputs on %s" % (name, a.device, dev))
+    if a.dim() != 3 or a.shape[0] != n or a.numel() == 0 or (hw is not None and tuple(a.shape[1:]) != tuple(hw)):
+        raise ValueError("%s %s must be (%d, W, H)%s" % (name, tuple(a.shape), n, "" if hw is None else " with (W, H) = %s" % (tuple(hw),)))
+    return a
+
+
+def label_map(scores, labels, num_classes=20, device="cuda"):
+    """Step A on the device (myTool.py:705-706): scores (n, W, H) float32, plane i the score of label ``labels[i]`` -- ascending,
+    ``labels[0] == 0`` the background, label c + 1 class c, the layout of a refined dict -- -> the uint8 (W, H) argmax over the
+    labels 0..num_classes, a label without a plane counting as 0.0 and the smallest label among the maxima winning (``np.argmax``
+    over the reference's dense array; on a refined dict, whose scores are positive, this is ``evaluation.label_map``)."""
+    labels = [int(l) for l in labels]
+    if not labels or labels[0] != 0:
+        raise ValueError("labels %s must start with the background label 0" % (labels,))
+    arr, k = _class_array([l - 1 for l in labels[1:]], num_classes)
+    dev = _device_of((scores,), device)
+    lib = L.load()
+    scores = _planes(scores, "scores", dev, k + 1)
+    _, w, h = scores.shape
+    with torch.cuda.device(dev):
+        out = torch.empty((w, h), dtype=torch.uint8, device=dev)
+        L.check(lib.acr_pseudo_label_f32(L.ptr(scores), arr, k, w, h, int(num_classes), L.ptr(out), L.stream_ptr()), "acr_pseudo_label_f32")
+    return out
+
+
+def seg_label(cams, classes, la, ha, *, ignore_uncertain=False, bg_alpha=36, cam_floor=0.1, fg_quantile=0.3, bg_sure=0.3,
+              crf_sure=0.8, num_classes=20, device="cuda"):
+    """``compute_seg_label_rrm`` for one image: cams (K, W, H) float32, plane j the CAM of class ``classes[j]`` (0-based,
+    strictly ascending); la / ha (K + 1, W, H) float32, the scores refined at the low / high background alpha (plane 0 the
+    background, plane j + 1 class ``classes[j]``).  Device tensors, or numpy arrays (uploaded to ``device``).  Returns the uint8
+    (W, H) pseudo-label on the device: the low-alpha label, 255 where that is background, 0 where the high-alpha label is
+    background; with ``ignore_uncertain`` also 255 wherever the refined score or the CAM is not confident (defaults: the
+    reference's constants).  Nothing here synchronises."""
+    arr, k = _class_array(classes, num_classes)
+    if not (cam_floor >= 0 and 0 <= fg_quantile < 1 and crf_sure > 0):
+        raise ValueError("need cam_floor >= 0, 0 <= fg_quantile < 1, crf_sure > 0 (got %r, %r, %r)" % (cam_floor, fg_quantile, crf_sure))
+    dev = _device_of((cams, la, ha), device)
+    lib = L.load()
+    cams = _planes(cams, "cams", dev, k)
+    hw = tuple(cams.shape[1:])
+    la = _planes(la, "la", dev, k + 1, hw)
+    ha = _planes(ha, "ha", dev, k + 1, hw)
+    w, h = hw
+    with torch.cuda.device(dev):
+        out = torch.empty((w, h), dtype=torch.uint8, device=dev)
+        ws, nbytes = None, 0
+        if ignore_uncertain:
+            nbytes = lib.acr_pseudo_ws_bytes(k, w, h)
+            if nbytes < 0:
+                L.check(-1, "acr_pseudo_ws_bytes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.check(lib.acr_pseudo_compose(L.ptr(cams), arr, k, L.ptr(la), L.ptr(ha), w, h, int(num_classes), 1 if ignore_uncertain else 0,
+                                       float(bg_alpha), float(cam_floor), float(fg_quantile), float(bg_sure), float(crf_sure),
+                                       L.ptr(ws), nbytes, L.ptr(out), L.stream_ptr()), "acr_pseudo_compose")
+    return out
+
+
+def stack_dicts(cam_dict, la_dict, ha_dict):
+    """The wire formats infer_cam_list writes -- {class: (W, H)} and two refined {0: background, class + 1: ...} dicts -- as
+    (cams (K, W, H), ascending classes, la (K + 1, W, H), ha (K + 1, W, H)) float32 numpy arrays."""
+    classes = sorted(int(c) for c in cam_dict)
+    if not classes:
+        raise ValueError("empty cam_dict: an image without a positive class has no pseudo-label to compose")
+    want = [0] + [c + 1 for c in classes]
+    for name, d in (("la_dict", la_dict), ("ha_dict", ha_dict)):
+        if sorted(int(k) for k in d) != want:
+            raise ValueError("%s holds the labels %s, the CAMs ask for %s" % (name, sorted(d), want))
+    cams = np.stack([np.asarray(cam_dict[c]) for c in classes]).astype(np.float32, copy=False)
+    la = np.stack([np.asarray(la_dict[l]) for l in want]).astype(np.float32, copy=False)
+    ha = np.stack([np.asarray(ha_dict[l]) for l in want]).astype(np.float32, copy=False)
+    return cams, classes, la, ha
+
+
+def seg_label_from_dicts(cam_dict, la_dict, ha_dict, **kw):
+    """``seg_label`` on the dictionaries infer_cam_list writes with out_cam and out_crf / out_pamr; returns a numpy uint8 (W, H)."""
+    cams, classes, la, ha = stack_dicts(cam_dict, la_dict, ha_dict)
+    return seg_label(cams, classes, la, ha, **kw).cpu().numpy()
+
+
+def voc_palette():
+    """The 256 x 3 uint8 PASCAL VOC colour map: bit b of label i goes to bit 7 - b // 3 of channel b % 3."""
+    pal = np.zeros((256, 3), np.uint8)
+    for i in range(256):
+        for b in range(8):
+            if (i >> b) & 1:
+                pal[i, b % 3] |= 1 << (7 - b // 3)
+    return pal
+
+
+def save_label_png(path, label):
+    """Write a uint8 (W, H) label map as a ``P``-mode PNG with the VOC colour map; ``np.array(PIL.Image.open(path))`` returns the
+    map unchanged (what the reference's evaluation.py reads with input_type='png')."""
+    from PIL import Image
+    label = np.asarray(label)
+    if label.dtype != np.uint8 or label.ndim != 2:
+        raise ValueError("label must be a 2-d uint8 array, got %s %s" % (label.dtype, label.shape))
+    im = Image.fromarray(np.ascontiguousarray(label))     # mode L; attaching a palette makes it P, the pixel bytes stay
+    im.putpalette(voc_palette().reshape(-1).tolist())
+    im.save(path, format="PNG")

@@ -626,6 +626,37 @@ int acr_eval_sweep_f32(const float* cams, const int32_t* classes, int32_t n, con
 int acr_eval_sweep_finish(const int64_t* raw, int32_t nt, int32_t num_cls, int64_t* TP, int64_t* P, void* stream);
 int acr_eval_confusion_u8(const uint8_t* pred, const uint8_t* gt, int64_t n_pixels, int32_t num_cls, int64_t* conf, void* stream);
 
+/* ---- pseudo-label composition from refined CAMs (myTool.py:674-744 compute_seg_label_rrm) ----
+ * All outputs are uint8 label maps, exact functions of their inputs (no float sums, integer atomics only): bit-identical run to
+ * run.  num_classes = C (background excluded), C + 1 <= 128.  `classes` is a HOST array of K strictly ascending 0-based class
+ * indices in [0, C), 1 <= K <= C, read during the call.  A score stack is (K + 1, h, w) fp32 contiguous on the device: plane 0 is
+ * label 0 (background), plane j + 1 label classes[j] + 1.  Inputs are finite: NaN is outside the contract.
+ * acr_pseudo_label_f32 (myTool.py:705-706, np.argmax over the dense (C + 1, h, w) array): out (h, w) = the smallest label among
+ *   the maxima over the labels 0..C, a label without a plane counting as 0.0f (the convention of acr_eval_sweep_f32).
+ * acr_pseudo_compose (myTool.py:694-735 and the line kept commented at :737): cams (K, h, w) fp32, plane j the CAM of classes[j];
+ *   la / ha the score stacks refined at the low / high background alpha.  With L_la, L_ha their label maps as above:
+ *     out = L_la;  out = 255 where L_la == 0;  out = 0 where L_ha == 0                                        (:707-708, :732)
+ *   and, if ignore_uncertain != 0, out = 255 wherever  max(ha[0], la[1..K]) < crf_sure  or the pixel is not sure  (:733-737):
+ *     m = max_j cams[j] (and 0.0f if K < C);  bg = (float)pow((double)(1.0f - m), bg_alpha);  M = the label map of {0: bg,
+ *     classes[j] + 1: cams[j]} as above                                                                        (:694-701)
+ *     for every label l that occurs in L_la, and only those                                                    (:710-712)
+ *       l == 0: sure where M == 0 and bg > bg_sure                                                             (:724-728)
+ *       l > 0:  S = the values cams[l] where M == l and the value > cam_floor, n = |S|; n == 0 (always so for a label without
+ *               a plane): no pixel of l is sure -- the reference raises IndexError there; otherwise v = sort(S)[(int)(n *
+ *               fg_quantile)], the product in double, and sure where M == l and cams[l] > v                    (:714-722)
+ *   All comparisons are fp32.  v is an exact selection on the fp32 bit patterns (a fixed four radix passes over all classes at
+ *   once; nothing depends on the data, nothing is read back).  Requires cam_floor >= 0, 0 <= fg_quantile < 1, crf_sure > 0.
+ *   ws: acr_pseudo_ws_bytes(K, h, w) bytes on the device, 4-byte aligned, contents arbitrary (cleared here by a kernel on the stream); used
+ *   only if ignore_uncertain != 0 (else it may be null).
+ * acr_pseudo_ws_bytes: host only; negative for arguments outside the supported range.
+ * The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+int64_t acr_pseudo_ws_bytes(int32_t K, int32_t h, int32_t w);
+int acr_pseudo_label_f32(const float* scores, const int32_t* classes, int32_t K, int32_t h, int32_t w, int32_t num_classes,
+                         uint8_t* out, void* stream);
+int acr_pseudo_compose(const float* cams, const int32_t* classes, int32_t K, const float* la, const float* ha, int32_t h, int32_t w,
+                       int32_t num_classes, int32_t ignore_uncertain, double bg_alpha, float cam_floor, double fg_quantile,
+                       float bg_sure, float crf_sure, void* ws, int64_t ws_bytes, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
