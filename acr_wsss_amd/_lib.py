@@ -192,6 +192,12 @@ SIGNATURES = {
     "acr_pseudo_label_f32": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_pseudo_compose": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                      ctypes.c_double, c_float, ctypes.c_double, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_segloss_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "acr_segloss_fwd": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_segloss_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                  c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_dense_energy_dot": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

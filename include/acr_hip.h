@@ -657,6 +657,53 @@ int acr_pseudo_compose(const float* cams, const int32_t* classes, int32_t K, con
                        int32_t num_classes, int32_t ignore_uncertain, double bg_alpha, float cam_floor, double fg_quantile,
                        float bg_sure, float crf_sure, void* ws, int64_t ws_bytes, uint8_t* out, void* stream);
 
+/* ---- pseudo-label segmentation loss (myTool.py:825-857 compute_joint_loss: the bilinear upsampling of the logits :831, the
+ * background-only / foreground-only cross-entropies with ignore :845-855 -- nn.CrossEntropyLoss(ignore_index=255), or
+ * SegmentationLosses.CrossEntropyLoss tool/loss.py:21-33 with batch_average -- and the softmax probabilities :832-833) ----
+ * "h, w" / "W, H" are the first and second spatial axis (the reference swaps the names itself, :829-831).
+ * logits (B, K, h, w) fp32 contiguous; label (B, W, H) uint8 on the device, 0..K-1 or ignore: 255, and any value in K..254 too.
+ * Requires 1 <= B <= 65535, 2 <= K <= 128, 1 <= h <= W, 1 <= w <= H, W * H < 2^31; anything else returns ACR_ERR_INVALID.
+ * acr_segloss_fwd: per label pixel pred = bilinear(logits) by torch's align_corners=False rule in fp32 (the rule of
+ *   acr_bilinear_resize: src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out), log-softmax over K, and per image
+ *     sum_bg = sum_{label == 0} -log p_0,  n_bg,  sum_fg = sum_{1 <= label < K} -log p_label,  n_fg
+ *   written to sums (B, 2) fp32 and counts (B + 1, 2) int64 (row B: the totals over the batch).  Then, over the whole batch,
+ *     bg = sum_bg / n_bg,  fg = sum_fg / n_fg  (each also / B if batch_average != 0),  loss (3) = { bg + fg, bg, fg }.
+ *   A count of 0 gives NaN for that term (0 / 0), as torch's mean over no pixel does.
+ *   probs (B, K, W, H), nullable: the softmax of pred (pred_probs, :832-833).  rowstat (B, W, H, 2), nullable, 8-byte aligned:
+ *   the row maximum and the sum of exp(pred - max) per pixel -- what acr_segloss_bwd takes.
+ * acr_segloss_bwd: d_logits (B, K, h, w), WRITTEN:
+ *     d_logits[b,k,y,x] = sum_pixels bilinear_weight * ( coef(pixel) * (p_k - [k == label]) + p_k * (d_probs_k - sum_j p_j d_probs_j) )
+ *   coef = (g[0] + g[1]) / n_bg for label 0, (g[0] + g[2]) / n_fg for 1 <= label < K, 0 for an ignored pixel (each / B under
+ *   batch_average); g (3) fp32 ON THE DEVICE: the gradients of { celoss, bg, fg }.  An ignored pixel contributes exactly 0, so a
+ *   count of 0 puts no Inf or NaN into d_logits.  d_probs (B, K, W, H) nullable (the energy term's gradient enters there) and
+ *   then requires the probs the forward wrote.  A gather per low-resolution logit in a fixed order: bit-identical run to run.
+ * ws: acr_segloss_ws_bytes(...) bytes on the device, 8-byte aligned, contents arbitrary; the backward uses it only with d_probs.
+ * acr_segloss_ws_bytes: host only; negative for arguments outside the supported range.
+ * All sums over pixels run in double in a fixed order (no float atomics); counts are integers.
+ *
+ * Dense energy on the lattice (the --densecrfloss / --rloss-scale / --sigma-rgb / --sigma-xy flags of infer_cam.py:58-65).  The
+ * reference passes its DenseEnergyLosslayer in as an argument and does not contain the class -- only its filter,
+ * bilateralfilter_batch (wrapper/bilateralfilter/bilateralfilter.cpp:42-55) -- so THE DEFINITION IS THIS PROJECT'S OWN.  For image
+ * b with probabilities S (K, n), roi (n) in [0, 1] and F_b the bilateral lattice filter of acr_lattice_filter on the features
+ * (x / sigma_xy, y / sigma_xy, rgb / sigma_rgb) (bilateralfilter.cpp:4-20):
+ *     AS = roi * F_b[roi * S],   E = -(weight / B) * sum_b sum_k sum_i S[k,i] * AS[k,i],   dE/dS := -(2 * weight / B) * AS
+ *   The gradient treats the filter as symmetric, as the regularised-loss layer does; it is a definition, not a derivative of the
+ *   lattice's arithmetic.
+ * acr_dense_energy_dot: out[0] = sum_i s[i] * as[i] over count = K * n values (products and sum in double, fixed order, one
+ *   rounding to fp32); grad (count), nullable: grad[i] = grad_scale * as[i].  ws: ACR_DENSE_ENERGY_WS_BYTES on the device,
+ *   8-byte aligned.
+ * The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+#define ACR_DENSE_ENERGY_WS_BYTES 2048
+int64_t acr_segloss_ws_bytes(int32_t B, int32_t K, int32_t h, int32_t w, int32_t W, int32_t H);
+int acr_segloss_fwd(const float* logits, const uint8_t* label, int32_t B, int32_t K, int32_t h, int32_t w, int32_t W, int32_t H,
+                    int32_t batch_average, void* ws, int64_t ws_bytes, float* probs, float* rowstat, float* sums, int64_t* counts,
+                    float* loss, void* stream);
+int acr_segloss_bwd(const float* logits, const uint8_t* label, const float* rowstat, const int64_t* counts, const float* g,
+                    const float* probs, const float* d_probs, int32_t B, int32_t K, int32_t h, int32_t w, int32_t W, int32_t H,
+                    int32_t batch_average, void* ws, int64_t ws_bytes, float* d_logits, void* stream);
+int acr_dense_energy_dot(const float* s, const float* as, int64_t count, float grad_scale, float* grad, void* ws, int64_t ws_bytes,
+                         float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
