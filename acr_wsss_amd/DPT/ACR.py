@@ -49,8 +49,6 @@ class DPT(BaseModel):
         if backbone not in _BACKBONES:
             print(f"Backbone '{backbone}' not implemented")
             assert False
-        if seg:
-            raise NotImplementedError("seg=True (DPT decoder) is outside the ACR hot path (SURVEY 2 #6)")
         self.channels_last = channels_last
         self.attention = use_attention
         vit_kw, scratch_in, (tap3, tap4) = _BACKBONES[backbone]
@@ -61,11 +59,12 @@ class DPT(BaseModel):
         self.pretrained = nn.Module()
         self.pretrained.model = vit
         self.pretrained.activations = {}
-        if backbone in ("vitl16_384", "deitb16_384", "deitb16_distil_384"):
+        if backbone in ("vitl16_384", "deitb16_384", "deitb16_distil_384") or (seg and backbone == "vitb16_384"):
             # DPT/blocks.py:29-35,62-82 builds these three without `seg=seg`, so DPT/vit.py:263-341 (default seg=True) attaches
             # the four read-out heads to `pretrained` although ACR never runs them: their 14 tensors are part of every
             # checkpoint of these backbones.  Created for state-dict compatibility only (indices 3 / 4 of each Sequential hold
-            # the parameters; 0-2 are the parameter-free read-out / transpose / unflatten steps).
+            # the parameters; 0-2 are the parameter-free read-out / transpose / unflatten steps).  vitb16_384 gets them under
+            # seg=True only (blocks.py:51-57).
             D, f = vit.embed_dim, scratch_in
             tails = ([nn.Conv2d(D, f[0], 1), nn.ConvTranspose2d(f[0], f[0], 4, stride=4)],
                      [nn.Conv2d(D, f[1], 1), nn.ConvTranspose2d(f[1], f[1], 2, stride=2)],
@@ -74,9 +73,21 @@ class DPT(BaseModel):
             for i, tail in enumerate(tails):
                 setattr(self.pretrained, "act_postprocess%d" % (i + 1),
                         nn.Sequential(nn.Identity(), nn.Identity(), nn.Identity(), *tail))
-        self.scratch = nn.Module()                     # created, never used in the ACR forward (blocks.py:97-147)
+        elif seg and backbone == "vitb_rn50_384":
+            # DPT/vit.py:444-530: the hybrid's read-outs under seg=True -- taps 1 and 2 are stem stages (nothing to learn), taps 3
+            # and 4 a 1x1 projection, tap 4 also the stride-2 3x3 that takes it to H/32.  decoder.layers_rn runs them.
+            D, f = vit.embed_dim, scratch_in
+            tails = ([], [], [nn.Conv2d(D, f[2], 1)], [nn.Conv2d(D, f[3], 1), nn.Conv2d(f[3], f[3], 3, stride=2, padding=1)])
+            for i, tail in enumerate(tails):
+                setattr(self.pretrained, "act_postprocess%d" % (i + 1),
+                        nn.Sequential(nn.Identity(), nn.Identity(), nn.Identity(), *tail))
+        self.scratch = nn.Module()                     # never used in the ACR forward (blocks.py:97-147); decoder.decode runs it
         for i, cin in enumerate(scratch_in):
             setattr(self.scratch, "layer%d_rn" % (i + 1), nn.Conv2d(cin, features, 3, 1, 1, bias=False))
+        if seg:                                        # DPT/ACR.py:81-85: the fusion blocks (acr_wsss_amd/decoder.py)
+            from ..decoder import make_fusion_block
+            for i in (1, 2, 3, 4):
+                setattr(self.scratch, "refinenet%d" % i, make_fusion_block(features, use_bn))
         self.cls_head = nn.Linear(vit.embed_dim, self.num_class)
         self.use_gap = True
         self.truncate_at = None                        # GETAM: stop the backward at this block (None = full)

@@ -198,6 +198,15 @@ SIGNATURES = {
     "acr_segloss_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "acr_dense_energy_dot": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_bn2d_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "acr_bn2d_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                               ctypes.c_double, ctypes.c_double, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "acr_bn2d_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                               c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_relu_fwd_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_relu_bwd_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_upsample2x_fwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "acr_upsample2x_bwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

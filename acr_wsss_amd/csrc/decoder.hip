@@ -1,0 +1,510 @@
+// DPT decoder kernels (the reference's fusion blocks, DPT/blocks.py:277-413, and its head, DPT/DPT.py:376-383): BatchNorm2d with
+// batch or running statistics, an optional ReLU and up to two residual addends in the same pass (blocks.py:312-343,402), its
+// backward, the x2 bilinear upsampling with align_corners=True (blocks.py:407-409) and its backward, and the leading ReLU of a
+// residual unit (blocks.py:330).  fp32 NCHW contiguous tensors.
+//
+// Mapping of the norm: a channel's data are N separate rows of H*W floats.  A launch is C * S workgroups, workgroup (c, s) owning
+// slab s of channel c: a contiguous range of the channel's N*H*W values in (n, i) order, so a slab is a few whole rows (small
+// levels) or a piece of one (large levels).  Inside a slab a wave takes a row when there are at least four, otherwise all 256
+// threads share a row; a row piece is walked as an unaligned head of at most 3 floats, 16-byte vectors, and a tail of at most 3 --
+// nothing outside the piece is touched.  Every tensor of a call has the same shape and a 16-byte aligned base, so one head / tail
+// split serves all of them.  Sums: a thread adds its values in double in a fixed order, an LDS tree adds the threads, a finish
+// kernel adds the slabs in ascending order.  No atomics; bit-identical run to run.  The variance is the shifted sum
+// (sum d^2 - (sum d)^2 / n) / n with d = x - x[first value of the channel] in double: a large mean costs nothing.
+// The normalisation itself is one double FMA per value, y = fp32(a_c * x + b_c (+ r1 + r2)), rounded once.
+// The ReLU mask of the backward is recomputed from the saved output (y > 0); no mask bytes are kept.
+//
+// Upsampling: forward one thread per pair of output pixels (8-byte stores: an output row has 2 W floats); backward a GATHER per
+// input pixel over the exact range of output rows / columns whose first tap is i - 1 or i, found with the forward's own fp32
+// source-index function, summed in ascending order in double.
+#include "acr_common.h"
+
+#define BN_MAX_SLABS 64
+
+static int bn_slabs(int64_t M, int C) {
+    const int64_t by_size = (M + 1023) / 1024;            // no slab below 1024 values ...
+    const int64_t fill = (1024 + C - 1) / C;              // ... about 1024 workgroups (256 CUs x 4) where the level is small ...
+    int64_t s = by_size < fill ? by_size : fill;
+    const int64_t big = (M + 16383) / 16384;              // ... and no slab above 16384 values where it is large
+    if (big > s) s = big;
+    return (int)(s < 1 ? 1 : (s > BN_MAX_SLABS ? BN_MAX_SLABS : s));
+}
+
+// the values [start, end) of channel c in (n, i) order: f1(offset) per single float, f4(offset) per 16-byte aligned group of 4
+template <typename F1, typename F4>
+__device__ __forceinline__ void bn_walk(int64_t start, int64_t end, int HW, int C, int c, F1 f1, F4 f4) {
+    if (start >= end) return;
+    const int n0 = (int)(start / HW), n1 = (int)((end - 1) / HW);
+    const int gsz = (n1 - n0 + 1) >= 4 ? 64 : 256;
+    const int grp = threadIdx.x / gsz, ngrp = 256 / gsz, lane = threadIdx.x % gsz;
+    for (int n = n0 + grp; n <= n1; n += ngrp) {
+        const int64_t base = ((int64_t)n * C + c) * HW;
+        const int lo = n == n0 ? (int)(start - (int64_t)n0 * HW) : 0;
+        const int hi = n == n1 ? (int)(end - (int64_t)n1 * HW) : HW;
+        int head = (int)((4 - ((base + lo) & 3)) & 3);
+        if (head > hi - lo) head = hi - lo;
+        const int nvec = (hi - lo - head) >> 2;
+        const int tail0 = lo + head + 4 * nvec;
+        if (lane < head) f1(base + lo + lane);
+        for (int v = lane; v < nvec; v += gsz) f4(base + lo + head + 4 * v);
+        if (lane < hi - tail0) f1(base + tail0 + lane);
+    }
+}
+
+__device__ __forceinline__ void bn_slab_range(int64_t M, int S, int s, int64_t& start, int64_t& end) {
+    const int64_t chunk = (M + S - 1) / S;
+    start = (int64_t)s * chunk;
+    end = start + chunk < M ? start + chunk : M;
+}
+
+// (a, b) summed over the workgroup in a fixed order; valid in thread 0
+__device__ __forceinline__ void bn_block_sum(double& a, double& b) {
+    __shared__ double rd[512];
+    const int tid = threadIdx.x;
+    rd[tid] = a;
+    rd[256 + tid] = b;
+    for (int off = 128; off > 0; off >>= 1) {
+        __syncthreads();
+        if (tid < off) {
+            rd[tid] += rd[tid + off];
+            rd[256 + tid] += rd[256 + tid + off];
+        }
+    }
+    a = rd[0];
+    b = rd[256];
+}
+
+__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int C, int HW, int64_t M, int S,
+                                                       double* __restrict__ part) {
+    const int c = blockIdx.x / S, s = blockIdx.x % S;
+    int64_t start, end;
+    bn_slab_range(M, S, s, start, end);
+    const double shift = (double)x[(int64_t)c * HW];
+    double a = 0.0, b = 0.0;
+    bn_walk(
+        start, end, HW, C, c,
+        [&](int64_t o) {
+            const double d = (double)x[o] - shift;
+            a += d;
+            b += d * d;
+        },
+        [&](int64_t o) {
+            const f32x4 v = acr_load4<float>(x + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double d = (double)v[j] - shift;
+                a += d;
+                b += d * d;
+            }
+        });
+    bn_block_sum(a, b);
+    if (threadIdx.x == 0) {
+        part[2 * (int64_t)blockIdx.x] = a;
+        part[2 * (int64_t)blockIdx.x + 1] = b;
+    }
+}
+
+// one thread per channel: the slabs in ascending order, the statistics, the running update, the coefficients of y = a x + b
+__global__ __launch_bounds__(256) void bn_fwd_finish_kernel(const float* __restrict__ x, const double* __restrict__ part,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ running_mean, float* __restrict__ running_var, int C,
+                                                            int HW, int64_t M, int S, int training, double eps, double momentum,
+                                                            double* __restrict__ stats, double* __restrict__ coef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double mean, invstd;
+    if (training) {
+        double a = 0.0, b = 0.0;
+        for (int s = 0; s < S; ++s) {
+            a += part[2 * ((int64_t)c * S + s)];
+            b += part[2 * ((int64_t)c * S + s) + 1];
+        }
+        const double n = (double)M;
+        mean = (double)x[(int64_t)c * HW] + a / n;
+        double var = (b - a * a / n) / n;
+        var = var > 0.0 ? var : 0.0;
+        invstd = 1.0 / sqrt(var + eps);
+        if (running_mean) running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
+        if (running_var) running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * (var * n / (n - 1.0)));
+    } else {
+        mean = (double)running_mean[c];
+        invstd = 1.0 / sqrt((double)running_var[c] + eps);
+    }
+    stats[2 * c] = mean;
+    stats[2 * c + 1] = invstd;
+    const double k = (double)gamma[c] * invstd;
+    coef[2 * c] = k;
+    coef[2 * c + 1] = (double)beta[c] - mean * k;
+}
+
+template <bool RELU, int NRES>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const double* __restrict__ coef,
+                                                       const float* __restrict__ r1, const float* __restrict__ r2, int C, int HW,
+                                                       int64_t M, int S, float* __restrict__ y) {
+    const int c = blockIdx.x / S, s = blockIdx.x % S;
+    int64_t start, end;
+    bn_slab_range(M, S, s, start, end);
+    const double ka = coef[2 * c], kb = coef[2 * c + 1];
+    auto one = [&](float xv, float a1, float a2) {
+        double v = (double)xv * ka + kb;
+        if (NRES >= 1) v += (double)a1;
+        if (NRES >= 2) v += (double)a2;
+        const float f = (float)v;
+        return RELU ? (f > 0.f ? f : 0.f) : f;
+    };
+    bn_walk(
+        start, end, HW, C, c, [&](int64_t o) { y[o] = one(x[o], NRES >= 1 ? r1[o] : 0.f, NRES >= 2 ? r2[o] : 0.f); },
+        [&](int64_t o) {
+            const f32x4 v = acr_load4<float>(x + o);
+            f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f}, out;
+            if (NRES >= 1) a1 = acr_load4<float>(r1 + o);
+            if (NRES >= 2) a2 = acr_load4<float>(r2 + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out[j] = one(v[j], a1[j], a2[j]);
+            acr_store4<float>(y + o, out);
+        });
+}
+
+// backward, first pass: part = (sum g, sum g * xhat) per slab, g = dy through the ReLU mask of the saved output
+template <bool RELU>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                            const float* __restrict__ dy, const double* __restrict__ stats, int C,
+                                                            int HW, int64_t M, int S, double* __restrict__ part) {
+    const int c = blockIdx.x / S, s = blockIdx.x % S;
+    int64_t start, end;
+    bn_slab_range(M, S, s, start, end);
+    const double mean = stats[2 * c], invstd = stats[2 * c + 1];
+    double a = 0.0, b = 0.0;
+    bn_walk(
+        start, end, HW, C, c,
+        [&](int64_t o) {
+            const double g = (!RELU || y[o] > 0.f) ? (double)dy[o] : 0.0;
+            a += g;
+            b += g * (((double)x[o] - mean) * invstd);
+        },
+        [&](int64_t o) {
+            const f32x4 xv = acr_load4<float>(x + o), gv = acr_load4<float>(dy + o);
+            f32x4 yv = {1.f, 1.f, 1.f, 1.f};
+            if (RELU) yv = acr_load4<float>(y + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double g = yv[j] > 0.f ? (double)gv[j] : 0.0;
+                a += g;
+                b += g * (((double)xv[j] - mean) * invstd);
+            }
+        });
+    bn_block_sum(a, b);
+    if (threadIdx.x == 0) {
+        part[2 * (int64_t)blockIdx.x] = a;
+        part[2 * (int64_t)blockIdx.x + 1] = b;
+    }
+}
+
+// coef (C, 3): k = gamma * invstd, mean(g), mean(g * xhat) (the last two 0 in eval mode: the statistics are constants)
+__global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __restrict__ part, const float* __restrict__ gamma,
+                                                            const double* __restrict__ stats, int C, int64_t M, int S, int training,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                            double* __restrict__ coef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int s = 0; s < S; ++s) {
+        a += part[2 * ((int64_t)c * S + s)];
+        b += part[2 * ((int64_t)c * S + s) + 1];
+    }
+    if (dbeta) dbeta[c] = (float)a;
+    if (dgamma) dgamma[c] = (float)b;
+    coef[3 * c] = (double)gamma[c] * stats[2 * c + 1];
+    coef[3 * c + 1] = training ? a / (double)M : 0.0;
+    coef[3 * c + 2] = training ? b / (double)M : 0.0;
+}
+
+template <bool RELU>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                           const float* __restrict__ dy, const double* __restrict__ stats,
+                                                           const double* __restrict__ coef, int C, int HW, int64_t M, int S,
+                                                           float* __restrict__ dx, float* __restrict__ dres) {
+    const int c = blockIdx.x / S, s = blockIdx.x % S;
+    int64_t start, end;
+    bn_slab_range(M, S, s, start, end);
+    const double mean = stats[2 * c], invstd = stats[2 * c + 1];
+    const double k = coef[3 * c], mg = coef[3 * c + 1], mgx = coef[3 * c + 2];
+    auto one = [&](float xv, float g) { return (float)(k * ((double)g - mg - (((double)xv - mean) * invstd) * mgx)); };
+    bn_walk(
+        start, end, HW, C, c,
+        [&](int64_t o) {
+            const float g = (!RELU || y[o] > 0.f) ? dy[o] : 0.f;
+            if (dx) dx[o] = one(x[o], g);
+            if (RELU && dres) dres[o] = g;
+        },
+        [&](int64_t o) {
+            const f32x4 xv = acr_load4<float>(x + o);
+            f32x4 gv = acr_load4<float>(dy + o), out;
+            if (RELU) {
+                const f32x4 yv = acr_load4<float>(y + o);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gv[j] = yv[j] > 0.f ? gv[j] : 0.f;
+            }
+            if (dx) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) out[j] = one(xv[j], gv[j]);
+                acr_store4<float>(dx + o, out);
+            }
+            if (RELU && dres) acr_store4<float>(dres + o, gv);
+        });
+}
+
+// ---- ReLU of a residual unit's input (blocks.py:330) and its backward from the saved output ---------------------------------
+__global__ __launch_bounds__(256) void relu_fwd_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ y) {
+    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        f32x4 v = acr_load4<float>(x + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
+        acr_store4<float>(y + 4 * i, v);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const float v = x[4 * n4 + threadIdx.x];
+        y[4 * n4 + threadIdx.x] = v > 0.f ? v : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, int64_t n,
+                                                       float* __restrict__ dx) {
+    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const f32x4 v = acr_load4<float>(y + 4 * i);
+        f32x4 g = acr_load4<float>(dy + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g[j] = v[j] > 0.f ? g[j] : 0.f;
+        acr_store4<float>(dx + 4 * i, g);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t o = 4 * n4 + threadIdx.x;
+        dx[o] = y[o] > 0.f ? dy[o] : 0.f;
+    }
+}
+
+// ---- x2 bilinear upsampling, align_corners=True (torch upsample_bilinear2d; aten/src/ATen/native/UpSample.h) -----------------
+struct up_tap {
+    int i0, i1;
+    float l0, l1;                          // weights of i0 and i1
+};
+
+__device__ __forceinline__ up_tap up_tap_of(float scale, int dst, int n_in) {
+    up_tap t;
+    const float src = scale * (float)dst;
+    int i0 = (int)src;
+    i0 = i0 < n_in - 1 ? i0 : n_in - 1;
+    float l = src - (float)i0;
+    l = l < 0.f ? 0.f : (l > 1.f ? 1.f : l);
+    t.i0 = i0;
+    t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+    t.l1 = l;
+    t.l0 = 1.f - l;
+    return t;
+}
+
+__device__ __forceinline__ float up_interp(const float* __restrict__ p, int W, const up_tap& ty, const up_tap& tx) {
+    return ty.l0 * (tx.l0 * p[ty.i0 * W + tx.i0] + tx.l1 * p[ty.i0 * W + tx.i1]) +
+           ty.l1 * (tx.l0 * p[ty.i1 * W + tx.i0] + tx.l1 * p[ty.i1 * W + tx.i1]);
+}
+
+// one thread per pair of output pixels (Y, 2 xp), (Y, 2 xp + 1)
+__global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const float* __restrict__ x, int64_t planes, int H, int W, float sh, float sw,
+                                                             float* __restrict__ y) {
+    const int OH = 2 * H, OW = 2 * W;
+    const int64_t total = planes * OH * W;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int xp = (int)(idx % W), Y = (int)((idx / W) % OH);
+        const int64_t p = idx / ((int64_t)W * OH);
+        const float* plane = x + p * H * W;
+        const up_tap ty = up_tap_of(sh, Y, H);
+        const up_tap ta = up_tap_of(sw, 2 * xp, W), tb = up_tap_of(sw, 2 * xp + 1, W);
+        float2 o;
+        o.x = up_interp(plane, W, ty, ta);
+        o.y = up_interp(plane, W, ty, tb);
+        *reinterpret_cast<float2*>(y + (p * OH + Y) * OW + 2 * xp) = o;
+    }
+}
+
+// the smallest destination index in [0, n_out] whose first tap is >= t; the source index is monotone in the destination
+__device__ __forceinline__ int up_first_dst(int t, int n_out, int n_in, float scale, float inv) {
+    if (t <= 0) return 0;
+    if (t > n_in - 1) return n_out;
+    float e = (float)t * inv;
+    e = e < 0.f ? 0.f : (e > (float)n_out ? (float)n_out : e);
+    int d = (int)e;
+    while (d > 0 && up_tap_of(scale, d - 1, n_in).i0 >= t) --d;
+    while (d < n_out && up_tap_of(scale, d, n_in).i0 < t) ++d;
+    return d;
+}
+
+// one thread per input pixel, lanes along x
+__global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const float* __restrict__ dy, int64_t planes, int H, int W, float sh, float sw,
+                                                             float ish, float isw, float* __restrict__ dx) {
+    const int OH = 2 * H, OW = 2 * W;
+    const int64_t total = planes * H * W;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int xx = (int)(idx % W), yy = (int)((idx / W) % H);
+        const int64_t p = idx / ((int64_t)W * H);
+        const float* g = dy + p * OH * OW;
+        const int Ya = up_first_dst(yy - 1, OH, H, sh, ish), Yb = up_first_dst(yy + 1, OH, H, sh, ish);
+        const int Xa = up_first_dst(xx - 1, OW, W, sw, isw), Xb = up_first_dst(xx + 1, OW, W, sw, isw);
+        double acc = 0.0;
+        for (int Y = Ya; Y < Yb; ++Y) {
+            const up_tap ty = up_tap_of(sh, Y, H);
+            const float wy = (ty.i0 == yy ? ty.l0 : 0.f) + (ty.i1 == yy ? ty.l1 : 0.f);
+            for (int X = Xa; X < Xb; ++X) {
+                const up_tap tx = up_tap_of(sw, X, W);
+                const float wx = (tx.i0 == xx ? tx.l0 : 0.f) + (tx.i1 == xx ? tx.l1 : 0.f);
+                acc += (double)wy * (double)wx * (double)g[(int64_t)Y * OW + X];
+            }
+        }
+        dx[idx] = (float)acc;
+    }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+#define BN_ALIGNED(p) ((((uintptr_t)(p)) & 15) == 0)
+
+static int bn_check(const char* who, int32_t N, int32_t C, int32_t HW) {
+    ACR_CHECK_ARG(N >= 1 && C >= 1 && HW >= 1, "%s: N=%d C=%d HW=%d must be positive", who, N, C, HW);
+    ACR_CHECK_ARG((int64_t)N * HW < (1ll << 31), "%s: N * H * W = %lld values per channel, 2^31 - 1 at most", who, (long long)N * HW);
+    ACR_CHECK_ARG((int64_t)C * BN_MAX_SLABS < (1ll << 31), "%s: C=%d too large", who, C);
+    return ACR_OK;
+}
+
+extern "C" int64_t acr_bn2d_ws_bytes(int32_t N, int32_t C, int32_t HW) {
+    if (bn_check("acr_bn2d_ws_bytes", N, C, HW) != ACR_OK) return ACR_ERR_INVALID;
+    return 8 * ((int64_t)C * bn_slabs((int64_t)N * HW, C) * 2 + 3 * (int64_t)C);
+}
+
+extern "C" int acr_bn2d_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            const float* resid, const float* resid2, int32_t N, int32_t C, int32_t HW, int32_t training, double eps,
+                            double momentum, int32_t relu, void* ws, int64_t ws_bytes, double* stats, float* y, void* stream) {
+    const int rc = bn_check("acr_bn2d_fwd", N, C, HW);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && gamma && beta && stats && y, "acr_bn2d_fwd: null pointer");
+    ACR_CHECK_ARG(resid || !resid2, "acr_bn2d_fwd: resid2 given without resid");
+    ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(resid) && BN_ALIGNED(resid2), "acr_bn2d_fwd: a tensor is not 16-byte aligned");
+    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0, "acr_bn2d_fwd: null workspace, or ws / stats not aligned to 8 bytes");
+    ACR_CHECK_ARG(ws_bytes >= acr_bn2d_ws_bytes(N, C, HW), "acr_bn2d_fwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                  (long long)acr_bn2d_ws_bytes(N, C, HW));
+    const int64_t M = (int64_t)N * HW;
+    if (training)
+        ACR_CHECK_ARG(M >= 2, "acr_bn2d_fwd: %lld value per channel in training mode, 2 at least", (long long)M);
+    else
+        ACR_CHECK_ARG(running_mean && running_var, "acr_bn2d_fwd: eval mode needs the running statistics");
+    ACR_CHECK_ARG(eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0, "acr_bn2d_fwd: eps=%g, momentum=%g", eps, momentum);
+    hipStream_t st = (hipStream_t)stream;
+    const int S = bn_slabs(M, C);
+    double* part = reinterpret_cast<double*>(ws);
+    double* coef = part + (int64_t)C * S * 2;
+    const dim3 grid((unsigned)(C * S)), cgrid((unsigned)((C + 255) / 256));
+    if (training) hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, st, x, C, HW, M, S, part);
+    hipLaunchKernelGGL(bn_fwd_finish_kernel, cgrid, dim3(256), 0, st, x, (const double*)part, gamma, beta, running_mean, running_var, C,
+                       HW, M, S, training ? 1 : 0, eps, momentum, stats, coef);
+#define BN_APPLY(R, K) \
+    hipLaunchKernelGGL((bn_apply_kernel<R, K>), grid, dim3(256), 0, st, x, (const double*)coef, resid, resid2, C, HW, M, S, y)
+    const int nres = resid2 ? 2 : (resid ? 1 : 0);
+    if (relu) {
+        if (nres == 0) BN_APPLY(true, 0);
+        else if (nres == 1) BN_APPLY(true, 1);
+        else BN_APPLY(true, 2);
+    } else {
+        if (nres == 0) BN_APPLY(false, 0);
+        else if (nres == 1) BN_APPLY(false, 1);
+        else BN_APPLY(false, 2);
+    }
+#undef BN_APPLY
+    return acr_check_launch("acr_bn2d_fwd");
+}
+
+extern "C" int acr_bn2d_bwd(const float* x, const float* y, const float* dy, const float* gamma, const double* stats, int32_t N,
+                            int32_t C, int32_t HW, int32_t training, int32_t relu, void* ws, int64_t ws_bytes, float* dx,
+                            float* dgamma, float* dbeta, float* dres, void* stream) {
+    const int rc = bn_check("acr_bn2d_bwd", N, C, HW);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && dy && gamma && stats, "acr_bn2d_bwd: null pointer");
+    ACR_CHECK_ARG(!relu || y, "acr_bn2d_bwd: a fused ReLU needs the saved output");
+    ACR_CHECK_ARG(relu || !dres, "acr_bn2d_bwd: without a fused ReLU the addends' gradient is dy itself; dres must be null");
+    ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(dy) && BN_ALIGNED(dx) && BN_ALIGNED(dres),
+                  "acr_bn2d_bwd: a tensor is not 16-byte aligned");
+    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0, "acr_bn2d_bwd: null workspace, or ws / stats not aligned to 8 bytes");
+    ACR_CHECK_ARG(ws_bytes >= acr_bn2d_ws_bytes(N, C, HW), "acr_bn2d_bwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                  (long long)acr_bn2d_ws_bytes(N, C, HW));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t M = (int64_t)N * HW;
+    const int S = bn_slabs(M, C);
+    double* part = reinterpret_cast<double*>(ws);
+    double* coef = part + (int64_t)C * S * 2;
+    const dim3 grid((unsigned)(C * S)), cgrid((unsigned)((C + 255) / 256));
+    if (relu)
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(256), 0, st, x, y, dy, stats, C, HW, M, S, part);
+    else
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(256), 0, st, x, y, dy, stats, C, HW, M, S, part);
+    hipLaunchKernelGGL(bn_bwd_finish_kernel, cgrid, dim3(256), 0, st, (const double*)part, gamma, stats, C, M, S, training ? 1 : 0, dgamma,
+                       dbeta, coef);
+    if (dx || dres) {
+        if (relu)
+            hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(256), 0, st, x, y, dy, stats, (const double*)coef, C, HW, M, S, dx, dres);
+        else
+            hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(256), 0, st, x, y, dy, stats, (const double*)coef, C, HW, M, S, dx, dres);
+    }
+    return acr_check_launch("acr_bn2d_bwd");
+}
+
+static int relu_grid(int64_t n) {
+    const int64_t nb = ((n >> 2) + 255) / 256;
+    return (int)(nb < 1 ? 1 : (nb > 8192 ? 8192 : nb));
+}
+
+extern "C" int acr_relu_fwd_f32(const float* x, int64_t n, float* y, void* stream) {
+    ACR_CHECK_ARG(x && y && n >= 1, "acr_relu_fwd_f32: null pointer or n=%lld < 1", (long long)n);
+    ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y), "acr_relu_fwd_f32: a tensor is not 16-byte aligned");
+    hipLaunchKernelGGL(relu_fwd_kernel, dim3(relu_grid(n)), dim3(256), 0, (hipStream_t)stream, x, n, y);
+    return acr_check_launch("acr_relu_fwd_f32");
+}
+
+extern "C" int acr_relu_bwd_f32(const float* y, const float* dy, int64_t n, float* dx, void* stream) {
+    ACR_CHECK_ARG(y && dy && dx && n >= 1, "acr_relu_bwd_f32: null pointer or n=%lld < 1", (long long)n);
+    ACR_CHECK_ARG(BN_ALIGNED(y) && BN_ALIGNED(dy) && BN_ALIGNED(dx), "acr_relu_bwd_f32: a tensor is not 16-byte aligned");
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(relu_grid(n)), dim3(256), 0, (hipStream_t)stream, y, dy, n, dx);
+    return acr_check_launch("acr_relu_bwd_f32");
+}
+
+static int up_check(const char* who, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW) {
+    ACR_CHECK_ARG(planes >= 1 && H >= 1 && W >= 1, "%s: planes=%lld H=%d W=%d must be positive", who, (long long)planes, H, W);
+    if (OH != 2 * H || OW != 2 * W) {
+        acr_set_error("%s: only out = 2 * in per axis is built (%d x %d -> %d x %d)", who, H, W, OH, OW);
+        return ACR_ERR_UNSUPPORTED;
+    }
+    ACR_CHECK_ARG((int64_t)OH * OW < (1ll << 31) && planes * OH * OW < (1ll << 40), "%s: tensor too large", who);
+    return ACR_OK;
+}
+
+static int up_grid(int64_t total) {
+    const int64_t nb = (total + 255) / 256;
+    return (int)(nb > 16384 ? 16384 : nb);
+}
+
+extern "C" int acr_upsample2x_fwd(const float* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* y, void* stream) {
+    const int rc = up_check("acr_upsample2x_fwd", planes, H, W, OH, OW);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && y && ((uintptr_t)y & 7) == 0, "acr_upsample2x_fwd: null pointer, or y not aligned to 8 bytes");
+    const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f, sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    hipLaunchKernelGGL(upsample2x_fwd_kernel, dim3(up_grid(planes * OH * W)), dim3(256), 0, (hipStream_t)stream, x, planes, H, W, sh, sw, y);
+    return acr_check_launch("acr_upsample2x_fwd");
+}
+
+extern "C" int acr_upsample2x_bwd(const float* dy, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* dx, void* stream) {
+    const int rc = up_check("acr_upsample2x_bwd", planes, H, W, OH, OW);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(dy && dx, "acr_upsample2x_bwd: null pointer");
+    const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f, sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    const float ish = H > 1 ? (float)(OH - 1) / (float)(H - 1) : 0.f, isw = W > 1 ? (float)(OW - 1) / (float)(W - 1) : 0.f;
+    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(up_grid(planes * H * W)), dim3(256), 0, (hipStream_t)stream, dy, planes, H, W, sh, sw, ish,
+                       isw, dx);
+    return acr_check_launch("acr_upsample2x_bwd");
+}

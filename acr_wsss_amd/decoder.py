@@ -1,0 +1,324 @@
+"""The DPT decoder, ``ACR(..., seg=True)`` (DPT/ACR.py:51,78-85): the segmentation head's feature path that turns the encoder's
+four taps into ``path_1`` -- ``forward_vit`` (DPT/vit.py:103-148), ``layerN_rn`` and ``refinenet4 .. 1`` (DPT/DPT.py:274-286) --
+and the head itself (DPT/DPT.py:376-383), whose logits ``segloss.joint_loss`` takes.
+
+BatchNorm2d (training and eval; optional fused ReLU and up to two residual addends), the x2 ``align_corners=True`` bilinear
+upsampling and the leading ReLU of a residual unit run in csrc/decoder.hip behind ``acr_bn2d_*``, ``acr_upsample2x_*`` and
+``acr_relu_*`` (include/acr_hip.h states the rules in full); the 3x3 and 1x1 convolutions go through ``ops.conv3x3`` /
+``ops.conv1x1`` where ``ops.conv3x3_fusable`` / ``ops.conv1x1_fusable`` accept the shape and through ``F.conv2d`` otherwise.
+There is no CPU path: a CPU tensor raises ``AcrHipError``.  Forward and backward are bit-identical run to run.
+
+Precision: fp32 tensors under ``math="f32"`` and ``math="f32_split"``; bf16 is not built (``decode`` raises).
+Multi-GPU: the reference converts the model to ``SyncBatchNorm`` (train_acr.py:95); here the batch statistics are PER RANK --
+cross-rank statistics are not built."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.autograd import Function
+
+from . import _lib as L
+from . import ops
+
+
+def _dev32(t, what):
+    if not torch.is_tensor(t):
+        raise ValueError("%s must be a torch tensor on the GPU, got %s" % (what, type(t).__name__))
+    L.require_gpu(t)
+    if t.dtype != torch.float32 or t.dim() != 4 or t.numel() == 0:
+        raise ValueError("%s must be a non-empty (N, C, H, W) float32 tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    return t
+
+
+def _c16(t):
+    """contiguous with a 16-byte aligned base (a view into a larger buffer may start anywhere)"""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+# ------------------------------------------------------------------------------------------------
+# autograd functions over the C ABI
+# ------------------------------------------------------------------------------------------------
+class _BatchNormAct(Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, relu, resid, resid2):
+        lib = L.load()
+        x, resid, resid2 = _c16(x), _c16(resid), _c16(resid2)
+        n, c, h, w = x.shape
+        dev = x.device
+        with torch.cuda.device(dev):
+            nbytes = lib.acr_bn2d_ws_bytes(n, c, h * w)
+            if nbytes < 0:
+                L.check(-1, "acr_bn2d_ws_bytes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            stats = torch.empty((c, 2), dtype=torch.float64, device=dev)
+            y = torch.empty_like(x)
+            L.check(lib.acr_bn2d_fwd(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
+                                     L.ptr(resid2), n, c, h * w, 1 if training else 0, float(eps), float(momentum), 1 if relu else 0,
+                                     L.ptr(ws), nbytes, L.ptr(stats), L.ptr(y), L.stream_ptr()), "acr_bn2d_fwd")
+        ctx.save_for_backward(x, weight, stats, y if relu else None)
+        ctx.training, ctx.relu, ctx.ws = bool(training), bool(relu), ws
+        ctx.nres = (resid is not None) + (resid2 is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        x, weight, stats, y = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dev = x.device
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_r = ctx.nres and (ctx.needs_input_grad[9] or ctx.needs_input_grad[10])
+        with torch.cuda.device(dev):
+            dy = _c16(dy.to(torch.float32))
+            dx = torch.empty_like(x) if need_x else None
+            dgamma = torch.empty(c, dtype=torch.float32, device=dev) if need_w else None
+            dbeta = torch.empty(c, dtype=torch.float32, device=dev) if need_b else None
+            dres = torch.empty_like(x) if (need_r and ctx.relu) else None
+            if need_x or need_w or need_b or dres is not None:
+                L.check(lib.acr_bn2d_bwd(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(weight), L.ptr(stats), n, c, h * w, 1 if ctx.training else 0,
+                                         1 if ctx.relu else 0, L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta),
+                                         L.ptr(dres), L.stream_ptr()), "acr_bn2d_bwd")
+        if need_r and not ctx.relu:
+            dres = dy                                       # without a ReLU the addends' gradient is dy itself
+        d1 = dres if (ctx.nres >= 1 and ctx.needs_input_grad[9]) else None
+        d2 = dres if (ctx.nres >= 2 and ctx.needs_input_grad[10]) else None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, d1, d2
+
+
+def batch_norm_act(x, bn, act="none", resid=None, resid2=None):
+    """``act(bn(x) [+ resid] [+ resid2])`` in one pass: ``bn`` an ``nn.BatchNorm2d`` (affine, a float ``momentum``), ``act``
+    "none" or "relu", the addends shaped like ``x`` (``resid2`` only with ``resid``).  In training mode the batch statistics
+    (biased variance) normalise and the module's ``running_mean`` / ``running_var`` / ``num_batches_tracked`` are updated as
+    ``nn.BatchNorm2d`` updates them (the running variance unbiased); in eval mode the running statistics normalise and the
+    backward treats them as constants.  One value per channel in training mode raises ValueError, as torch does.  Statistics are
+    those of this process's batch: nothing is exchanged between ranks.  Differentiable in x, the affine parameters and the
+    addends."""
+    if act not in ("none", "relu"):
+        raise ValueError("act must be \"none\" or \"relu\", got %r" % (act,))
+    if not isinstance(bn, nn.BatchNorm2d) or not bn.affine:
+        raise NotImplementedError("batch_norm_act takes an affine nn.BatchNorm2d, got %s" % type(bn).__name__)
+    if bn.momentum is None and bn.track_running_stats:
+        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative average) is not built; give a float momentum")
+    if resid2 is not None and resid is None:
+        raise ValueError("resid2 given without resid")
+    x = _dev32(x, "x")
+    if x.shape[1] != bn.num_features:
+        raise ValueError("x has %d channels, the norm %d" % (x.shape[1], bn.num_features))
+    for r in (resid, resid2):
+        if r is not None and (_dev32(r, "resid").shape != x.shape or r.device != x.device):
+            raise ValueError("an addend %s on %s does not match x %s on %s" % (tuple(r.shape), r.device, tuple(x.shape), x.device))
+    if bn.weight.dtype != torch.float32 or bn.weight.device != x.device:
+        raise ValueError("the norm's parameters must be float32 on %s" % x.device)
+    training = bn.training or bn.running_mean is None
+    if training and x.shape[0] * x.shape[2] * x.shape[3] < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+    if bn.training and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _BatchNormAct.apply(x, bn.weight, bn.bias, rm, rv, training, bn.momentum or 0.0, bn.eps, act == "relu", resid, resid2)
+
+
+class _Relu(Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _c16(x)
+        y = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.check(L.load().acr_relu_fwd_f32(L.ptr(x), x.numel(), L.ptr(y), L.stream_ptr()), "acr_relu_fwd_f32")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        dy = _c16(dy.to(torch.float32))
+        dx = torch.empty_like(y)
+        with torch.cuda.device(y.device):
+            L.check(L.load().acr_relu_bwd_f32(L.ptr(y), L.ptr(dy), y.numel(), L.ptr(dx), L.stream_ptr()), "acr_relu_bwd_f32")
+        return dx
+
+
+def relu(x):
+    """``max(x, 0)`` as a new tensor: the leading ``activation(x)`` of a residual unit (blocks.py:330), whose raw ``x`` stays
+    untouched for the skip (:343).  (The reference's own ``nn.ReLU(False)`` is out of place for the same reason.)"""
+    return _Relu.apply(_dev32(x, "x"))
+
+
+class _Upsample2x(Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        n, c, h, w = x.shape
+        y = torch.empty((n, c, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            L.check(L.load().acr_upsample2x_fwd(L.ptr(x), n * c, h, w, 2 * h, 2 * w, L.ptr(y), L.stream_ptr()), "acr_upsample2x_fwd")
+        ctx.shape = (n, c, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        n, c, h, w = ctx.shape
+        dy = dy.to(torch.float32).contiguous()
+        dx = torch.empty((n, c, h, w), dtype=torch.float32, device=dy.device)
+        with torch.cuda.device(dy.device):
+            L.check(L.load().acr_upsample2x_bwd(L.ptr(dy), n * c, h, w, 2 * h, 2 * w, L.ptr(dx), L.stream_ptr()), "acr_upsample2x_bwd")
+        return dx
+
+
+def upsample2x(x):
+    """``F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)`` (blocks.py:407-409) with its backward."""
+    return _Upsample2x.apply(_dev32(x, "x"))
+
+
+def conv(m, x, math):
+    """The ``nn.Conv2d`` ``m`` on x: the hand-written 3x3 / 1x1 kernels where they cover the shape (bias added after), torch's
+    convolution otherwise (a stride-2 convolution, channel counts off the tile, a map narrower than 16: the H/32 level at 384^2
+    and 448^2)."""
+    k, s, p = m.kernel_size, m.stride, m.padding
+    if m.groups == 1 and m.dilation == (1, 1) and s == (1, 1):
+        y = None
+        if k == (3, 3) and p == (1, 1) and ops.conv3x3_fusable(x, m.weight, 1, math):
+            y = ops.conv3x3(x, m.weight)
+        elif k == (1, 1) and p == (0, 0) and ops.conv1x1_fusable(x, m.weight, 1):
+            y = ops.conv1x1(x, m.weight, None, math)
+        if y is not None:
+            return y if m.bias is None else y + m.bias.view(1, -1, 1, 1)
+    return F.conv2d(x, m.weight, m.bias, s, p, m.dilation, m.groups)
+
+
+# ------------------------------------------------------------------------------------------------
+# modules: DPT/blocks.py:277-413, DPT/DPT.py:376-383
+# ------------------------------------------------------------------------------------------------
+def _relu_only(activation):
+    if not isinstance(activation, nn.ReLU):
+        raise NotImplementedError("the decoder's activation is nn.ReLU (DPT/ACR.py:18), got %s" % type(activation).__name__)
+
+
+class ResidualConvUnit_custom(nn.Module):
+    """blocks.py:277-345 with ``bn=True``, ``groups=1``: relu, conv1, bn1, relu, conv2, bn2, + x."""
+    acr_math = 0
+
+    def __init__(self, features, activation, bn):
+        super().__init__()
+        _relu_only(activation)
+        if bn is not True:
+            raise NotImplementedError("ResidualConvUnit_custom is built with bn=True only (DPT/ACR.py:153)")
+        self.bn = bn
+        self.groups = 1
+        self.conv1 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=False, groups=1)
+        self.conv2 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=False, groups=1)
+        self.bn1 = nn.BatchNorm2d(features)
+        self.bn2 = nn.BatchNorm2d(features)
+        self.activation = activation
+
+    def forward(self, x, addend=None):
+        """``addend``: a second skip added in the same pass as ``+ x`` (the fusion block's ``output + res``, blocks.py:402)"""
+        out = relu(x)
+        out = conv(self.conv1, out, self.acr_math)
+        out = batch_norm_act(out, self.bn1, "relu")              # bn1 and the second activation (:333-335)
+        out = conv(self.conv2, out, self.acr_math)
+        return batch_norm_act(out, self.bn2, "none", x, addend)
+
+
+class FeatureFusionBlock_custom(nn.Module):
+    """blocks.py:348-413 in the configuration ``_make_fusion_block`` builds (DPT/ACR.py:15-23)."""
+    acr_math = 0
+
+    def __init__(self, features, activation, deconv=False, bn=False, expand=False, align_corners=True):
+        super().__init__()
+        _relu_only(activation)
+        if deconv or expand or not align_corners or bn is not True:
+            raise NotImplementedError("FeatureFusionBlock_custom is built for bn=True, deconv=False, expand=False, align_corners=True "
+                                      "(got bn=%r, deconv=%r, expand=%r, align_corners=%r)" % (bn, deconv, expand, align_corners))
+        self.deconv, self.align_corners, self.groups, self.expand = deconv, align_corners, 1, expand
+        self.out_conv = nn.Conv2d(features, features, kernel_size=1, stride=1, padding=0, bias=True, groups=1)
+        self.resConfUnit1 = ResidualConvUnit_custom(features, activation, bn)
+        self.resConfUnit2 = ResidualConvUnit_custom(features, activation, bn)
+
+    def forward(self, *xs):
+        if len(xs) not in (1, 2):
+            raise ValueError("a fusion block takes one or two inputs, got %d" % len(xs))
+        output = xs[0]
+        if len(xs) == 2:
+            output = self.resConfUnit1(xs[1], addend=output)    # res = unit1(xs[1]); output + res
+        output = self.resConfUnit2(output)
+        output = upsample2x(output)
+        return conv(self.out_conv, output, self.acr_math)
+
+
+class _Interpolate2x(nn.Module):
+    def forward(self, x):
+        return upsample2x(x)
+
+
+class SegmentationHead(nn.Sequential):
+    """DPT/DPT.py:376-383 with that ``nn.Sequential``'s state-dict keys (0: 3x3 convolution without bias, 1: BatchNorm, 2: ReLU,
+    3: Dropout 0.1, 4: 1x1 convolution to ``num_classes + 1``, 5: x2 upsampling).  Norm and ReLU run as one pass."""
+    acr_math = 0
+
+    def __init__(self, features, num_classes):
+        super().__init__(nn.Conv2d(features, features, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(features), nn.ReLU(True),
+                         nn.Dropout(0.1, False), nn.Conv2d(features, num_classes + 1, kernel_size=1), _Interpolate2x())
+
+    def forward(self, x):
+        x = batch_norm_act(conv(self[0], x, self.acr_math), self[1], "relu")
+        return self[5](conv(self[4], self[3](x), self.acr_math))
+
+
+def make_fusion_block(features, use_bn):
+    """DPT/ACR.py:15-23"""
+    return FeatureFusionBlock_custom(features, nn.ReLU(False), deconv=False, bn=use_bn, expand=False, align_corners=True)
+
+
+# ------------------------------------------------------------------------------------------------
+# the decoder pass
+# ------------------------------------------------------------------------------------------------
+def layers_rn(model, x):
+    """``forward_vit`` (DPT/vit.py:103-148) and ``scratch.layerN_rn`` (DPT/DPT.py:274-281) of a hybrid ``seg=True`` model:
+    the four (B, features, h / 4 .. h / 32, ...) maps the fusion blocks take.  Taps 1 and 2 are the stem stages the encoder
+    records; taps 3 and 4 drop the class token (``readout="ignore"``), become (B, D, h / 16, w / 16) and go through
+    ``act_postprocess3`` / ``act_postprocess4``."""
+    from .backbone import HybridEmbed
+    if not hasattr(model.scratch, "refinenet1"):
+        raise ValueError("decode needs a model built with seg=True")
+    vit = model.pretrained.model
+    if not isinstance(vit.patch_embed, HybridEmbed):
+        raise NotImplementedError("decode is built for the hybrid backbone; the ConvTranspose2d read-outs of %s are not" % model.cur_backbone)
+    if not torch.is_tensor(x):
+        raise ValueError("x must be a torch tensor on the GPU, got %s" % type(x).__name__)
+    L.require_gpu(x)
+    if x.dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
+        raise NotImplementedError("decode is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s input / %s weights"
+                                  % (x.dtype, model.cls_head.weight.dtype))
+    b, _, h, w = x.shape
+    model._encode(x)
+    taps = model.pretrained.activations
+    gh, gw = h // vit.patch_size[1], w // vit.patch_size[0]
+    skip = vit.num_tokens                                    # 1: the class token (Slice(start_index=1), DPT/vit.py:57-63)
+    math = vit.acr_math
+
+    def grid(tok):
+        return tok[:, skip:].transpose(1, 2).reshape(b, tok.shape[2], gh, gw).contiguous()
+    pp, sc = model.pretrained, model.scratch
+    layer_3 = conv(pp.act_postprocess3[3], grid(taps["3"]), math)
+    layer_4 = conv(pp.act_postprocess4[4], conv(pp.act_postprocess4[3], grid(taps["4"]), math), math)
+    return (conv(sc.layer1_rn, taps["1"].contiguous(), math), conv(sc.layer2_rn, taps["2"].contiguous(), math),
+            conv(sc.layer3_rn, layer_3, math), conv(sc.layer4_rn, layer_4, math))
+
+
+def fuse(model, l1, l2, l3, l4):
+    """``refinenet4 .. 1`` (DPT/DPT.py:283-286) on the four ``layerN_rn`` maps: ``path_1``"""
+    sc = model.scratch
+    path_4 = sc.refinenet4(l4)
+    path_3 = sc.refinenet3(path_4, l3)
+    path_2 = sc.refinenet2(path_3, l2)
+    return sc.refinenet1(path_2, l1)
+
+
+def decode(model, x):
+    """x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> ``path_1`` (B, features, h / 2, w / 2) of a hybrid
+    ``ACR(..., seg=True)`` (DPT/DPT.py:274-286); ``SegmentationHead`` turns it into (B, num_classes + 1, h, w) logits.  Other
+    backbones and bf16 raise NotImplementedError.  BatchNorm statistics are per process (see the module docstring)."""
+    return fuse(model, *layers_rn(model, x))

@@ -704,6 +704,54 @@ int acr_segloss_bwd(const float* logits, const uint8_t* label, const float* rows
 int acr_dense_energy_dot(const float* s, const float* as, int64_t count, float grad_scale, float* grad, void* ws, int64_t ws_bytes,
                          float* out, void* stream);
 
+/* ---- DPT decoder (ACR(..., seg=True), DPT/ACR.py:51,78-85: the fusion blocks DPT/blocks.py:277-413 and the head
+ * DPT/DPT.py:376-383): BatchNorm2d, the x2 bilinear upsampling and the leading ReLU of a residual unit ----
+ * All tensors fp32, NCHW, contiguous, 16-byte aligned bases; HW = H * W; n = N * HW values per channel, n < 2^31.
+ * acr_bn2d_fwd (nn.BatchNorm2d of blocks.py:312-338):
+ *   training != 0: per channel mu = mean over N, H, W and the biased variance var = mean (x - mu)^2, accumulated in double as
+ *     a shifted sum (the shift is the channel's first value), so a large mean costs no digits; n >= 2 or ACR_ERR_INVALID, as
+ *     torch refuses one value per channel.  running_mean / running_var (C, nullable together) are UPDATED in place:
+ *       running_mean = (1 - momentum) * running_mean + momentum * mu
+ *       running_var  = (1 - momentum) * running_var  + momentum * var * n / (n - 1)        (the unbiased variance)
+ *   training == 0: mu = running_mean, var = running_var (required); nothing is updated.
+ *   invstd = 1 / sqrt(var + eps);   y = act( gamma * (x - mu) * invstd + beta [+ resid] [+ resid2] )
+ *   act = ReLU for relu != 0, else the identity.  resid is the residual unit's `out + x` (blocks.py:343), resid2 the fusion
+ *   block's `output + res` (:402); both nullable, resid2 only with resid.  The expression is evaluated in double per value and
+ *   rounded to fp32 once.  stats (C, 2) double, WRITTEN: mu and invstd -- what acr_bn2d_bwd takes.
+ * acr_bn2d_bwd: with g = dy where the saved output y > 0 (relu != 0; y is then required) and g = dy otherwise,
+ *   xhat = (x - mu) * invstd:
+ *       dbeta = sum g,   dgamma = sum g * xhat                                             (each nullable)
+ *       dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat))      training != 0
+ *       dx = gamma * invstd * g                                          training == 0 (the statistics are constants)
+ *   dres (nullable, only with relu != 0): g, the gradient of either addend; without a fused ReLU that gradient is dy itself
+ *   and nothing is written.  dx nullable.
+ * ws: acr_bn2d_ws_bytes(N, C, HW) bytes on the device, 8-byte aligned, contents arbitrary (host only; negative for arguments
+ *   outside the supported range).  Every sum runs in double in a fixed order (thread, LDS tree, slabs ascending): no float
+ *   atomics, bit-identical run to run.  Nothing outside a plane is read or written.
+ * acr_relu_fwd_f32 / acr_relu_bwd_f32: y = max(x, 0) over n values (the `activation(x)` of blocks.py:330; the raw x stays with
+ *   the caller for the skip, :343) and dx = dy where y > 0, else 0.
+ * acr_upsample2x_fwd (F.interpolate(scale_factor=2, mode="bilinear", align_corners=True), blocks.py:407-409 and the head's
+ *   Interpolate): x (planes, H, W) -> y (planes, OH, OW), y 8-byte aligned.  Only OH = 2 H and OW = 2 W are built: anything else
+ *   returns ACR_ERR_UNSUPPORTED.  Per axis, in fp32 (torch's rule, aten/src/ATen/native/UpSample.h):
+ *       scale = (in - 1) / (out - 1)  (0 when out == 1),  src = scale * dst,  i0 = min((int)src, in - 1),
+ *       lambda = src - i0,  i1 = i0 + (i0 < in - 1),  value = (1 - lambda) * v[i0] + lambda * v[i1]
+ *   rows outside, columns inside: y = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11).
+ * acr_upsample2x_bwd: dx (planes, H, W), WRITTEN: the adjoint, as a gather per input pixel over exactly the output rows and
+ *   columns whose first tap is i - 1 or i (found with the forward's own fp32 index function), summed in ascending order in
+ *   double: bit-identical run to run.
+ * The entry points allocate nothing, launch on `stream` and read nothing back; they capture into a hipGraph. */
+int64_t acr_bn2d_ws_bytes(int32_t N, int32_t C, int32_t HW);
+int acr_bn2d_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, const float* resid,
+                 const float* resid2, int32_t N, int32_t C, int32_t HW, int32_t training, double eps, double momentum, int32_t relu,
+                 void* ws, int64_t ws_bytes, double* stats, float* y, void* stream);
+int acr_bn2d_bwd(const float* x, const float* y, const float* dy, const float* gamma, const double* stats, int32_t N, int32_t C,
+                 int32_t HW, int32_t training, int32_t relu, void* ws, int64_t ws_bytes, float* dx, float* dgamma, float* dbeta,
+                 float* dres, void* stream);
+int acr_relu_fwd_f32(const float* x, int64_t n, float* y, void* stream);
+int acr_relu_bwd_f32(const float* y, const float* dy, int64_t n, float* dx, void* stream);
+int acr_upsample2x_fwd(const float* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* y, void* stream);
+int acr_upsample2x_bwd(const float* dy, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Micro-benchmark of the DPT decoder kernels (csrc/decoder.hip) and of one fusion block, forward and backward, at the decoder's
+production width: 16 x 256 x {28^2, 112^2} fp32.
+
+    python scripts/bench_decoder.py [--sizes 28 112] [--repeats 7] [--iters 10]
+
+Each entry is timed with device events around ``iters`` calls that ROTATE over enough buffer sets to exceed the 256 MiB Infinity
+Cache (so a 13 MB tensor at 28^2 is not served from cache), repeated ``repeats`` times: the median and the [min, max] range are
+printed.  GB/s are ALGORITHMIC bytes -- what the operation has to move, each tensor once -- over the median; the two-pass
+norm kernels read more than that (x twice in the forward, x and dy twice in the backward) and the table says so.  Every
+hand-written entry runs next to torch's own operator on the same machine, alternating; the fusion block runs next to a plain torch
+composition (nn.BatchNorm2d, F.conv2d, F.relu, F.interpolate) built here.  Needs a GPU: there is no fallback."""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from acr_wsss_amd import decoder as D  # noqa: E402
+from acr_wsss_amd.backbone import set_math  # noqa: E402
+
+DEV = "cuda:0"
+N, C = 16, 256
+CACHE_BYTES = 256 << 20
+
+
+def timed(fns, iters, repeats):
+    """fns: name -> callable(i) (i = rotation index).  Alternates the entries inside every repeat; returns name -> list of us"""
+    out = {k: [] for k in fns}
+    for k, fn in fns.items():                                # warm-up: code objects, library algorithm choice
+        for i in range(3):
+            fn(i)
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(iters):
+                fn(i)
+            e1.record()
+            e1.synchronize()
+            out[k].append(e0.elapsed_time(e1) / iters * 1e3)
+    return out
+
+
+def report(title, times, nbytes):
+    for k, v in times.items():
+        med = statistics.median(v)
+        print("%-34s %-6s median %9.1f us  [%9.1f, %9.1f]  %8.1f GB/s algorithmic" % (title, k, med, min(v), max(v), nbytes / med / 1e3))
+
+
+def rotation(elem_bytes_per_set):
+    return max(2, min(24, -(-2 * CACHE_BYTES // elem_bytes_per_set)))
+
+
+class TorchRCU(nn.Module):
+    def __init__(self, f):
+        super().__init__()
+        self.conv1, self.conv2 = nn.Conv2d(f, f, 3, 1, 1, bias=False), nn.Conv2d(f, f, 3, 1, 1, bias=False)
+        self.bn1, self.bn2 = nn.BatchNorm2d(f), nn.BatchNorm2d(f)
+
+    def forward(self, x):
+        return self.bn2(self.conv2(F.relu(self.bn1(self.conv1(F.relu(x)))))) + x
+
+
+class TorchFusion(nn.Module):
+    def __init__(self, f):
+        super().__init__()
+        self.out_conv = nn.Conv2d(f, f, 1)
+        self.resConfUnit1, self.resConfUnit2 = TorchRCU(f), TorchRCU(f)
+
+    def forward(self, a, b):
+        out = self.resConfUnit2(a + self.resConfUnit1(b))
+        return self.out_conv(F.interpolate(out, scale_factor=2, mode="bilinear", align_corners=True))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[28, 112])
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_decoder.py needs a GPU"
+    print("device: %s   N x C = %d x %d fp32   repeats %d x iters %d" % (torch.cuda.get_device_name(0), N, C, args.repeats, args.iters))
+    for s in args.sizes:
+        n = N * C * s * s
+        tb = 4 * n                                          # bytes of one (N, C, s, s) tensor
+        R = rotation(3 * tb)
+        print("\n== %d x %d x %d x %d (%.1f MB per tensor, %d rotating buffer sets) ==" % (N, C, s, s, tb / 1e6, R))
+        xs = [torch.randn(N, C, s, s, device=DEV) for _ in range(R)]
+        rs = [torch.randn(N, C, s, s, device=DEV) for _ in range(R)]
+        gs = [torch.randn(N, C, s, s, device=DEV) for _ in range(R)]
+        bn = nn.BatchNorm2d(C).to(DEV).train()
+        with torch.no_grad():
+            # ---- forward entries
+            report("bn fwd (train)", timed({"hip": lambda i: D.batch_norm_act(xs[i % R], bn),
+                                            "torch": lambda i: F.batch_norm(xs[i % R], bn.running_mean, bn.running_var, bn.weight, bn.bias, True, 0.1, 1e-5)},
+                                           args.iters, args.repeats), 2 * tb)
+            report("bn+relu+2 addends fwd (train)",
+                   timed({"hip": lambda i: D.batch_norm_act(xs[i % R], bn, "relu", rs[i % R], gs[i % R]),
+                          "torch": lambda i: F.relu(F.batch_norm(xs[i % R], bn.running_mean, bn.running_var, bn.weight, bn.bias, True, 0.1, 1e-5)
+                                                    + rs[i % R] + gs[i % R])}, args.iters, args.repeats), 4 * tb)
+            bn.eval()
+            report("bn fwd (eval)", timed({"hip": lambda i: D.batch_norm_act(xs[i % R], bn),
+                                           "torch": lambda i: F.batch_norm(xs[i % R], bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.1, 1e-5)},
+                                          args.iters, args.repeats), 2 * tb)
+            bn.train()
+            report("relu fwd", timed({"hip": lambda i: D.relu(xs[i % R]), "torch": lambda i: F.relu(xs[i % R])}, args.iters, args.repeats), 2 * tb)
+            report("upsample x2 fwd", timed({"hip": lambda i: D.upsample2x(xs[i % R]),
+                                             "torch": lambda i: F.interpolate(xs[i % R], scale_factor=2, mode="bilinear", align_corners=True)},
+                                            args.iters, args.repeats), 5 * tb)
+        # ---- backward entries: the graph is built once per buffer set, the timed call is the backward alone
+        def graphs(fn):
+            leaves = [x.detach().clone().requires_grad_(True) for x in xs]
+            return leaves, [fn(x) for x in leaves]
+
+        def bwd(leaves, outs, seeds):
+            params = [bn.weight, bn.bias]
+
+            def run(i):
+                torch.autograd.grad(outs[i % R], [leaves[i % R]] + params, seeds[i % len(seeds)], retain_graph=True, allow_unused=True)
+            return run
+        h = graphs(lambda x: D.batch_norm_act(x, bn))
+        t = graphs(lambda x: F.batch_norm(x, None, None, bn.weight, bn.bias, True, 0.1, 1e-5))
+        report("bn bwd (train)", timed({"hip": bwd(*h, gs), "torch": bwd(*t, gs)}, args.iters, args.repeats), 3 * tb)
+        del h, t
+        h = graphs(lambda x: D.batch_norm_act(x, bn, "relu"))
+        t = graphs(lambda x: F.relu(F.batch_norm(x, None, None, bn.weight, bn.bias, True, 0.1, 1e-5)))
+        report("bn+relu bwd (train)", timed({"hip": bwd(*h, gs), "torch": bwd(*t, gs)}, args.iters, args.repeats), 4 * tb)
+        del h, t
+        R4 = max(2, R // 4)
+        g4 = [torch.randn(N, C, 2 * s, 2 * s, device=DEV) for _ in range(R4)]
+        h = graphs(D.upsample2x)
+        t = graphs(lambda x: F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True))
+
+        def ubwd(leaves, outs):
+            def run(i):
+                torch.autograd.grad(outs[i % R], [leaves[i % R]], g4[i % R4], retain_graph=True)
+            return run
+        report("upsample x2 bwd", timed({"hip": ubwd(*h), "torch": ubwd(*t)}, args.iters, args.repeats), 5 * tb)
+        del h, t, g4
+        # ---- one fusion block, two inputs, forward + backward, split-product convolutions against torch's own composition
+        torch.manual_seed(0)
+        ours = set_math(D.FeatureFusionBlock_custom(C, nn.ReLU(False), bn=True).to(DEV).train(), "f32_split")
+        ref = TorchFusion(C).to(DEV).train()
+        ref.load_state_dict(ours.state_dict())
+        ga = torch.randn(N, C, 2 * s, 2 * s, device=DEV)
+
+        def block(m):
+            def run(i):
+                a, b = xs[i % R].requires_grad_(True), rs[i % R].requires_grad_(True)
+                m(a, b).backward(ga)
+                a.grad = b.grad = None
+                m.zero_grad(set_to_none=True)
+            return run
+        with torch.no_grad():
+            a, b = ours(xs[0], rs[0]), ref(xs[0], rs[0])
+            print("fusion block output, hand-written vs torch composition: max |diff| %.3e of max %.3e" % (float((a - b).abs().max()), float(b.abs().max())))
+        times = timed({"hip": block(ours), "torch": block(ref)}, max(2, args.iters // 2), args.repeats)
+        for k, v in times.items():
+            print("%-34s %-6s median %9.1f us  [%9.1f, %9.1f]" % ("fusion block fwd+bwd (2 inputs)", k, statistics.median(v), min(v), max(v)))
+        del xs, rs, gs, ours, ref
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,420 @@
+"""The DPT decoder on the device (csrc/decoder.hip behind acr_bn2d_* / acr_upsample2x_* / acr_relu_*, acr_wsss_amd/decoder.py)
+against the float64 restatement tests/decoder_ref.py -- pinned to torch's float64 autograd and to the reference's own fusion
+block by test_decoder_cpu.py -- and against the reference's results themselves (tests/golden/decoder_block_{a,b}.npz,
+decoder_hybrid_64.npz).
+
+Kernel-level tolerance (the rule of tests/test_segloss_gpu.py): the device result and torch's CPU fp32 result are each compared
+with the float64 restatement; the device's error may be at most 2x the error torch's own fp32 result shows on the same case, with
+a floor of 4 fp32 ulps (4 * 2^-23) of the largest reference value.  No absolute number is fixed in advance.
+A fused ReLU is only tested on decisive inputs: every pre-ReLU value of the restatement lies further from 0 than 8x torch's own
+fp32 deviation on that tensor (4x the bound the device is held to), no element excluded; the seeds below were picked for that
+and the test asserts it.
+Block and model level: the bounds tests/test_model_gpu.py::_train_case uses for reference fixtures, 2e-4 of the maximum for
+activations and 2e-3 for gradients."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+import decoder_ref as R
+from conftest import load_golden
+from kernel_checks import Cmp
+from recipe import make_inputs, recipe_tensor
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+ULPS = 4 * 2.0 ** -23
+MARGIN = 8.0
+MOMENTUM, EPS = 0.1, 1e-5
+# tag -> (shape, mean of x): odd planes; the smallest legal channel; general odd sizes; more channels than workgroups in a grid
+# row, tiny planes; several slabs (partial sums) per channel; the aligned wide path; cancellation in the variance
+BN_SHAPES = {"odd": ((2, 16, 5, 7), 0.0), "min": ((1, 1, 1, 2), 0.0), "gen": ((3, 5, 9, 4), 0.0), "chan": ((2, 300, 1, 3), 0.0),
+             "slabs": ((2, 16, 70, 33), 0.0), "wide": ((4, 64, 16, 16), 0.0), "mean1000": ((2, 16, 5, 7), 1000.0)}
+# seeds for which the ReLU inputs are decisive (found on the CPU with bn_case; asserted in every test that fuses a ReLU)
+BN_SEEDS = {("mean1000", True, 1, True): 1, ("wide", True, 2, True): 1, ("slabs", True, 2, False): 1}
+UP_SHAPES = [(1, 1, 1, 1), (2, 3, 5, 7), (2, 5, 1, 9), (2, 5, 9, 1), (1, 16, 16, 20), (1, 2, 33, 70)]
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.abs(a - b).max() / (np.abs(b).max() + 1e-30)
+
+
+def compare(cmp, what, dev, tor, ref):
+    """the tolerance rule of the module docstring for one quantity"""
+    ref = torch.as_tensor(np.asarray(ref, np.float64))
+    dev, tor = torch.as_tensor(np.asarray(dev)).double().reshape(ref.shape), torch.as_tensor(np.asarray(tor)).double().reshape(ref.shape)
+    terr, derr = float((tor - ref).abs().max()), float((dev - ref).abs().max())
+    floor = ULPS * float(ref.abs().max())
+    print("%s %s: device err %.3e, torch fp32 err %.3e, ratio %.2f, floor %.3e%s"
+          % (cmp.where, what, derr, terr, derr / max(terr, 1e-300), floor, "  (passes on the floor)" if 2.0 * terr < derr <= floor else ""))
+    cmp.check(what, dev, ref, atol=max(2.0 * terr, floor))
+
+
+# ------------------------------------------------------------------------------------------------
+# BatchNorm2d
+# ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def bn_case(tag, relu, nres, training=True, seed=None):
+    """inputs (fp32 numpy), the float64 restatement and torch's CPU fp32 result of one case; treat as read-only"""
+    shape, mean = BN_SHAPES[tag]
+    if seed is None:
+        seed = BN_SEEDS.get((tag, relu, nres, training), 0)
+    rng = np.random.default_rng(100 * seed + len(tag) + 7 * nres)
+    c = shape[1]
+    x = (mean + rng.standard_normal(shape)).astype(np.float32)
+    dy = rng.standard_normal(shape).astype(np.float32)
+    res = [rng.standard_normal(shape).astype(np.float32) for _ in range(nres)]
+    gamma, beta = (1 + 0.1 * rng.standard_normal(c)).astype(np.float32), (0.1 * rng.standard_normal(c)).astype(np.float32)
+    rm, rv = (mean + 0.2 * rng.standard_normal(c)).astype(np.float32), (0.5 + rng.random(c)).astype(np.float32)
+    f = R.bn_fwd(x, gamma, beta, rm, rv, training, MOMENTUM, EPS, relu, *(res + [None, None])[:2])
+    dx, dgamma, dbeta, dres = R.bn_bwd(x, gamma, f["mean"], f["invstd"], dy, training, mask=(f["pre"] > 0) if relu else None)
+    ref = dict(y=f["y"], running_mean=f["running_mean"], running_var=f["running_var"], dx=dx, dgamma=dgamma, dbeta=dbeta, dres=dres)
+    # torch, CPU fp32
+    bn = nn.BatchNorm2d(c, eps=EPS, momentum=MOMENTUM).train(training)
+    with torch.no_grad():
+        for t, v in ((bn.weight, gamma), (bn.bias, beta), (bn.running_mean, rm), (bn.running_var, rv)):
+            t.copy_(torch.from_numpy(v))
+    xt = torch.from_numpy(x).clone().requires_grad_(True)
+    rt = [torch.from_numpy(r).clone().requires_grad_(True) for r in res]
+    pre = bn(xt)
+    for r in rt:
+        pre = pre + r
+    yt = F.relu(pre) if relu else pre
+    yt.backward(torch.from_numpy(dy))
+    tor = dict(y=yt.detach(), running_mean=bn.running_mean.clone(), running_var=bn.running_var.clone(), dx=xt.grad, dgamma=bn.weight.grad,
+               dbeta=bn.bias.grad, dres=rt[0].grad if rt else None)
+    decisive = True
+    if relu:
+        dev = float(np.abs(pre.detach().numpy().astype(np.float64) - f["pre"]).max())
+        decisive = float(np.abs(f["pre"]).min()) > MARGIN * dev
+    return dict(x=x, dy=dy, res=res, gamma=gamma, beta=beta, rm=rm, rv=rv, ref=ref, tor=tor, decisive=decisive)
+
+
+def bn_device(case, relu, training=True, steps=1):
+    from acr_wsss_amd import decoder as D
+    c = case["x"].shape[1]
+    bn = nn.BatchNorm2d(c, eps=EPS, momentum=MOMENTUM).to(DEV).train(training)
+    with torch.no_grad():
+        for t, v in ((bn.weight, case["gamma"]), (bn.bias, case["beta"]), (bn.running_mean, case["rm"]), (bn.running_var, case["rv"])):
+            t.copy_(torch.from_numpy(v))
+    for _ in range(steps):
+        bn.zero_grad()
+        x = torch.from_numpy(case["x"]).to(DEV).requires_grad_(True)
+        res = [torch.from_numpy(r).to(DEV).requires_grad_(True) for r in case["res"]]
+        y = D.batch_norm_act(x, bn, "relu" if relu else "none", *res)
+        y.backward(torch.from_numpy(case["dy"]).to(DEV))
+    out = dict(y=y.detach().cpu(), running_mean=bn.running_mean.cpu(), running_var=bn.running_var.cpu(), dx=x.grad.cpu(),
+               dgamma=bn.weight.grad.cpu(), dbeta=bn.bias.grad.cpu(), dres=[r.grad.cpu() for r in res],
+               tracked=int(bn.num_batches_tracked))
+    return out
+
+
+def check_bn(tag, relu, nres, training=True):
+    case = bn_case(tag, relu, nres, training)
+    assert case["decisive"], "the ReLU inputs of %s are not decisive: pick another seed" % ((tag, relu, nres, training),)
+    dev = bn_device(case, relu, training)
+    cmp = Cmp()
+    cmp.where = "bn %s relu%d res%d train%d" % (tag, relu, nres, training)
+    names = ["y", "dx", "dgamma", "dbeta"] + (["running_mean", "running_var"] if training else [])
+    for name in names:
+        compare(cmp, name, dev[name], case["tor"][name], case["ref"][name])
+    for d in dev["dres"]:
+        compare(cmp, "dres", d, case["tor"]["dres"], case["ref"]["dres"])
+    if not training:
+        assert np.array_equal(dev["running_mean"].numpy(), case["rm"]) and np.array_equal(dev["running_var"].numpy(), case["rv"])
+    assert dev["tracked"] == (1 if training else 0)
+    assert not cmp.failures, "\n".join(cmp.failures)
+    return case, dev
+
+
+@pytest.mark.parametrize("nres", [0, 1, 2])
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("tag", sorted(BN_SHAPES))
+def test_batchnorm_forward_and_backward(tag, relu, nres):
+    case, dev = check_bn(tag, relu, nres)
+    if tag == "mean1000":                                    # a plain fp32 E[x^2] - E[x]^2 would lose the variance: 1e6 * 2^-24 ~ 0.06
+        assert abs(float(case["x"].mean()) - 1000) < 1 and 0.5 < float(case["x"].var()) < 2
+
+
+@pytest.mark.parametrize("relu,nres", [(False, 0), (True, 2)])
+@pytest.mark.parametrize("tag", ["odd", "slabs"])
+def test_batchnorm_eval_mode(tag, relu, nres):
+    check_bn(tag, relu, nres, training=False)
+
+
+@pytest.mark.parametrize("tag", ["gen", "mean1000"])
+def test_running_statistics_after_one_and_three_steps(tag):
+    case = bn_case(tag, False, 0)
+    want = {"m": case["rm"].astype(np.float64), "v": case["rv"].astype(np.float64)}
+    bn = nn.BatchNorm2d(case["x"].shape[1], eps=EPS, momentum=MOMENTUM)
+    with torch.no_grad():
+        bn.running_mean.copy_(torch.from_numpy(case["rm"]))
+        bn.running_var.copy_(torch.from_numpy(case["rv"]))
+    for steps in (1, 2, 3):
+        f = R.bn_fwd(case["x"], case["gamma"], case["beta"], want["m"], want["v"], True, MOMENTUM, EPS)
+        want = {"m": f["running_mean"], "v": f["running_var"]}
+        bn(torch.from_numpy(case["x"]))
+        if steps == 2:
+            continue
+        dev = bn_device(case, False, steps=steps)
+        cmp = Cmp()
+        cmp.where = "bn %s after %d steps" % (tag, steps)
+        compare(cmp, "running_mean", dev["running_mean"], bn.running_mean, want["m"])
+        compare(cmp, "running_var", dev["running_var"], bn.running_var, want["v"])
+        assert dev["tracked"] == steps
+        assert not cmp.failures, "\n".join(cmp.failures)
+
+
+def test_one_value_per_channel_in_training_mode_raises():
+    from acr_wsss_amd import _lib as L
+    from acr_wsss_amd import decoder as D
+    x = torch.zeros(1, 3, 1, 1, device=DEV)
+    bn = nn.BatchNorm2d(3).to(DEV)
+    with pytest.raises(ValueError):
+        D.batch_norm_act(x, bn)
+    assert int(bn.num_batches_tracked) == 0
+    # the C ABI refuses it as well
+    lib = L.load()
+    ws = torch.empty(lib.acr_bn2d_ws_bytes(1, 3, 1), dtype=torch.uint8, device=DEV)
+    stats, y = torch.empty(3, 2, dtype=torch.float64, device=DEV), torch.empty_like(x)
+    rc = lib.acr_bn2d_fwd(L.ptr(x), L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var), None, None, 1, 3, 1, 1,
+                          1e-5, 0.1, 0, L.ptr(ws), ws.numel(), L.ptr(stats), L.ptr(y), L.stream_ptr())
+    assert rc == -1
+    y = D.batch_norm_act(x, bn.eval())                        # eval mode takes it
+    assert torch.isfinite(y).all()
+
+
+def test_batchnorm_repeats_bit_for_bit_and_takes_unaligned_views():
+    from acr_wsss_amd import decoder as D
+    case = bn_case("slabs", True, 2)
+    one, two = bn_device(case, True), bn_device(case, True)
+    for name in ("y", "dx", "dgamma", "dbeta", "running_mean", "running_var"):
+        assert one[name].numpy().tobytes() == two[name].numpy().tobytes(), name
+    for a, b in zip(one["dres"], two["dres"]):
+        assert a.numpy().tobytes() == b.numpy().tobytes()
+    # a contiguous view that starts 4 bytes into its buffer: same bits
+    shape = case["x"].shape
+    buf = torch.zeros(case["x"].size + 1, device=DEV)
+    buf[1:].copy_(torch.from_numpy(case["x"]).reshape(-1))
+    view = buf[1:].view(shape)
+    assert view.data_ptr() % 16 != 0 and view.is_contiguous()
+    bn = nn.BatchNorm2d(shape[1], eps=EPS, momentum=MOMENTUM).to(DEV)
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(case["gamma"]))
+        bn.bias.copy_(torch.from_numpy(case["beta"]))
+    res = [torch.from_numpy(r).to(DEV) for r in case["res"]]
+    assert torch.equal(D.batch_norm_act(view, bn, "relu", *res).cpu(), one["y"])
+
+
+# ------------------------------------------------------------------------------------------------
+# x2 upsampling, ReLU
+# ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def up_case(shape):
+    rng = np.random.default_rng(17 + sum(shape))
+    x = rng.standard_normal(shape).astype(np.float32)
+    dy = rng.standard_normal(shape[:2] + (2 * shape[2], 2 * shape[3])).astype(np.float32)
+    xt = torch.from_numpy(x).clone().requires_grad_(True)
+    yt = F.interpolate(xt, scale_factor=2, mode="bilinear", align_corners=True)
+    yt.backward(torch.from_numpy(dy))
+    return x, dy, dict(y=R.upsample2x(x), dx=R.upsample2x_bwd(dy)), dict(y=yt.detach(), dx=xt.grad)
+
+
+def up_device(x, dy):
+    from acr_wsss_amd import decoder as D
+    xd = torch.from_numpy(x).to(DEV).requires_grad_(True)
+    y = D.upsample2x(xd)
+    y.backward(torch.from_numpy(dy).to(DEV))
+    return dict(y=y.detach().cpu(), dx=xd.grad.cpu())
+
+
+@pytest.mark.parametrize("shape", UP_SHAPES)
+def test_upsampling_forward_and_backward(shape):
+    x, dy, ref, tor = up_case(shape)
+    dev = up_device(x, dy)
+    assert tuple(dev["y"].shape) == shape[:2] + (2 * shape[2], 2 * shape[3])
+    cmp = Cmp()
+    cmp.where = "upsample %s" % (shape,)
+    compare(cmp, "y", dev["y"], tor["y"], ref["y"])
+    compare(cmp, "dx", dev["dx"], tor["dx"], ref["dx"])
+    assert not cmp.failures, "\n".join(cmp.failures)
+
+
+def test_upsampling_and_relu_repeat_bit_for_bit_and_other_factors_are_unsupported():
+    from acr_wsss_amd import _lib as L
+    from acr_wsss_amd import decoder as D
+    x, dy, _, _ = up_case((1, 2, 33, 70))
+    one, two = up_device(x, dy), up_device(x, dy)
+    for name in ("y", "dx"):
+        assert one[name].numpy().tobytes() == two[name].numpy().tobytes(), name
+    lib = L.load()
+    xd = torch.from_numpy(x).to(DEV)
+    y = torch.empty(1, 2, 99, 140, device=DEV)
+    assert lib.acr_upsample2x_fwd(L.ptr(xd), 2, 33, 70, 99, 140, L.ptr(y), L.stream_ptr()) == -3          # ACR_ERR_UNSUPPORTED
+    assert lib.acr_upsample2x_bwd(L.ptr(y), 2, 33, 70, 66, 141, L.ptr(xd), L.stream_ptr()) == -3
+    # the leading ReLU of a residual unit: exact, and x itself stays untouched
+    for n in (1, 3, 4, 2310 * 2 + 1):
+        v = torch.from_numpy(np.random.default_rng(n).standard_normal((1, 1, 1, n)).astype(np.float32)).to(DEV).requires_grad_(True)
+        keep = v.detach().clone()
+        r = D.relu(v)
+        g = torch.from_numpy(np.random.default_rng(n + 1).standard_normal((1, 1, 1, n)).astype(np.float32)).to(DEV)
+        r.backward(g)
+        assert torch.equal(r.detach(), keep.clamp(min=0)) and torch.equal(v.detach(), keep)
+        assert torch.equal(v.grad, g * (keep > 0))
+
+
+# ------------------------------------------------------------------------------------------------
+# fusion block against the reference's results
+# ------------------------------------------------------------------------------------------------
+def _block(fx, math):
+    from acr_wsss_amd import decoder as D
+    from acr_wsss_amd.backbone import set_math
+    blk = D.FeatureFusionBlock_custom(int(fx["features"]), nn.ReLU(False), deconv=False, bn=True, expand=False, align_corners=True)
+    bad = blk.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in R.block_params(fx).items()}, strict=False)
+    assert not bad.unexpected_keys and all(k.endswith("num_batches_tracked") for k in bad.missing_keys)
+    return set_math(blk.to(DEV), math)
+
+
+@pytest.mark.parametrize("tag,mode,math", [("a", "train", "f32"), ("a", "train", "f32_split"), ("b", "train", "f32"), ("b", "eval", "f32")])
+def test_fusion_block_against_the_reference_fixture(tag, mode, math):
+    fx = load_golden("decoder_block_" + tag)
+    pre = "" if mode == "train" else "eval_"
+    stride = int(fx["stride"])
+    # no ReLU decision of this fixture hangs on rounding (the generator chose the seed so; test_decoder_cpu.py restates the tensors)
+    assert (fx[pre + "relu_min64"] > MARGIN * fx[pre + "relu_dev32"]).all()
+    blk = _block(fx, math).train(mode == "train")
+    xs = [torch.from_numpy(fx["x%d" % i]).to(DEV).requires_grad_(True) for i in range(2) if "x%d" % i in fx]
+    if tag == "a" and math == "f32_split":                   # this case is here to reach the hand-written convolutions
+        from acr_wsss_amd import ops
+        assert ops.conv3x3_fusable(xs[0].detach(), blk.resConfUnit1.conv1.weight, 1, 1)
+    out = blk(*xs)
+    out.backward(torch.from_numpy(fx["dy"]).to(DEV))
+    worst = {}
+    for ref in ("32", "64"):
+        worst["out" + ref] = _rel(R.sample(out.detach().cpu().numpy(), stride), fx[pre + "out" + ref])
+        assert worst["out" + ref] <= 2e-4, worst
+        for i, x in enumerate(xs):
+            worst["dx%d_%s" % (i, ref)] = _rel(R.sample(x.grad.cpu().numpy(), stride), fx[pre + "dx%d_%s" % (i, ref)])
+            assert worst["dx%d_%s" % (i, ref)] <= 2e-3, worst
+    params, seen = dict(blk.named_parameters()), 0
+    for k, v in fx.items():
+        if k.startswith(pre + "grad64:"):
+            name = k.split(":", 1)[1]
+            worst[k] = _rel(R.sample(params[name].grad.cpu().numpy(), stride), v)
+            assert worst[k] <= 2e-3, (k, worst[k])
+            seen += 1
+    assert seen == (14 if len(xs) == 2 else 8)
+    assert all(p.grad is None for n, p in params.items() if n.startswith("resConfUnit1.")) == (len(xs) == 1)
+    sd = blk.state_dict()
+    for k in sd:
+        if "running_" in k:
+            if mode == "train" and (len(xs) == 2 or k.startswith("resConfUnit2.")):
+                assert _rel(sd[k].cpu().numpy(), fx["after64:" + k]) <= 2e-4, k
+            else:
+                assert np.array_equal(sd[k].cpu().numpy(), fx["before:" + k]), k
+    print("fusion block %s %s %s: worst %s" % (tag, mode, math, {k: "%.2e" % v for k, v in worst.items() if not k.startswith("grad")}),
+          "worst grad %.2e" % max(v for k, v in worst.items() if "grad" in k))
+
+
+# ------------------------------------------------------------------------------------------------
+# the whole decoder
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def seg_model():
+    from acr_wsss_amd.DPT.ACR import ACR
+    fx = load_golden("decoder_hybrid_64")
+    m = ACR(20, "vitb_hybrid", seg=True, features=int(fx["meta"][4]), use_pretrain=False)
+    sd = {}
+    for k, v in m.state_dict().items():
+        if "running_" in k:
+            sd[k] = torch.from_numpy(fx["before:" + k])
+        elif torch.is_floating_point(v):
+            sd[k] = recipe_tensor(k, v.shape, 0)
+        else:
+            sd[k] = torch.zeros_like(v)
+    m.load_state_dict(sd, strict=True)
+    return m.to(DEV), fx, sd
+
+
+def _reset(m, sd):
+    with torch.no_grad():
+        for k, v in m.state_dict().items():
+            if "running_" in k or k.endswith("num_batches_tracked"):
+                v.copy_(sd[k])
+
+
+@pytest.mark.parametrize("math", ["f32", "f32_split"])
+def test_decode_against_the_reference_fixture(seg_model, math):
+    from acr_wsss_amd import decoder as D
+    m, fx, sd = seg_model
+    _reset(m, sd)
+    m.set_math(math).train()
+    size, batch, ncls, seed, _ = [int(v) for v in fx["meta"]]
+    img, _ = make_inputs(batch, size, ncls, seed)
+    with torch.no_grad():
+        rn = D.layers_rn(m, img.to(DEV))
+        path_1 = D.fuse(m, *rn)
+    for i, t in enumerate(rn):
+        r = _rel(t.cpu().numpy(), fx["layer_%d_rn" % (i + 1)])
+        print("decode %s layer_%d_rn %.2e" % (math, i + 1, r))
+        assert r <= 2e-4, (i, r)
+    r = _rel(path_1.cpu().numpy(), fx["path_1"])
+    print("decode %s path_1 %.2e" % (math, r))
+    assert tuple(path_1.shape) == (batch, 16, size // 2, size // 2) and r <= 2e-4, r
+    for k, v in m.state_dict().items():
+        if "running_" in k:
+            assert _rel(v.cpu().numpy(), fx["after:" + k]) <= 2e-4, k
+    m.set_math("f32")
+
+
+def test_decode_refuses_bf16(seg_model):
+    from acr_wsss_amd import decoder as D
+    m, fx, sd = seg_model
+    with pytest.raises(NotImplementedError):
+        D.decode(m, torch.zeros(1, 3, 64, 64, device=DEV, dtype=torch.bfloat16))
+
+
+def test_head_loss_and_backward_end_to_end_repeat_bit_for_bit(seg_model):
+    """SegmentationHead(decode(model, x)) into segloss.split_cross_entropy with a random label map, then backward(): every decoder
+    and head parameter receives a finite gradient, and the whole thing repeats bit for bit"""
+    from acr_wsss_amd import decoder as D
+    from acr_wsss_amd import segloss as S
+    m, fx, sd = seg_model
+    m.set_math("f32_split").train()
+    torch.manual_seed(5)
+    head = D.SegmentationHead(16, 20).to(DEV).train()
+    from acr_wsss_amd.backbone import set_math
+    set_math(head, "f32_split")
+    img, _ = make_inputs(2, 64, 20, 43)
+    rng = np.random.default_rng(43)
+    label = rng.integers(0, 21, (2, 64, 64)).astype(np.uint8)
+    label[rng.random(label.shape) < 0.1] = 255
+    runs = []
+    for _ in range(2):
+        _reset(m, sd)
+        m.zero_grad()
+        head.zero_grad()
+        torch.manual_seed(6)                                 # the head's Dropout
+        logits = head(D.decode(m, img.to(DEV)))
+        assert tuple(logits.shape) == (2, 21, 64, 64)
+        ce, bg, fg = S.split_cross_entropy(logits, label)
+        ce.backward()
+        grads = {"head." + k: p.grad for k, p in head.named_parameters()}
+        # refinenet4 takes one input (DPT/DPT.py:283): its resConfUnit1 never runs, in the reference either
+        idle = "scratch.refinenet4.resConfUnit1."
+        assert all(p.grad is None for k, p in m.named_parameters() if k.startswith(idle))
+        grads.update({k: p.grad for k, p in m.named_parameters()
+                      if k.startswith(("scratch.", "pretrained.act_postprocess")) and not k.startswith(idle)})
+        assert len(grads) == 5 + 4 + 4 * 14 - 6 + 6          # head, layerN_rn, fusion blocks, read-outs
+        for k, g in grads.items():
+            assert g is not None and torch.isfinite(g).all() and float(g.abs().max()) > 0, k
+        runs.append((ce.detach().cpu(), {k: g.cpu().clone() for k, g in grads.items()}))
+    assert torch.isfinite(runs[0][0]) and runs[0][0].numpy().tobytes() == runs[1][0].numpy().tobytes()
+    for k in runs[0][1]:
+        assert runs[0][1][k].numpy().tobytes() == runs[1][1][k].numpy().tobytes(), k
+    m.set_math("f32")
