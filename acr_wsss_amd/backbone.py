@@ -362,7 +362,7 @@ class Mlp(nn.Module):
         and the block's residual add inside their epilogues; anything else takes the two Linears one by one."""
         if Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_fusable(x, self.fc1, self.fc2):
             return ops.mlp(x, self.fc1, self.fc2, resid)     # GELU / GELU' inside the GEMM epilogues
-        if (Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_f32_usable(x, self.fc1, self.fc2)
+        if (Attention.hip_linear and isinstance(self.act, nn.GELU) and ops.mlp_f32_usable(x, self.fc1, self.fc2, resid)
                 and not torch.is_autocast_enabled()):
             return ops.mlp_f32(x, self.fc1, self.fc2, resid, self.acr_math)  # reference precision: fp32 GEMMs, same fusion
         h = self.act(ops.linear_or_hip(x, self.fc1, None, Attention.hip_linear, math=self.acr_math))

@@ -464,10 +464,17 @@ class LinearBf16Fn(Function):
         return dx, dw, db, (dy if ctx.has_resid else None), None
 
 
+def _al16(*ts):
+    """Every given tensor (None passes) starts on a 16-byte boundary: what the entry points ask of the operands their kernels read
+    and write as 16-byte vectors.  A predicate that says yes must have looked: a contiguous view may start anywhere in its buffer."""
+    return all(t is None or t.data_ptr() % 16 == 0 for t in ts)
+
+
 def mlp_fusable(x, fc1, fc2):
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and fc1.weight.dtype == torch.bfloat16
             and fc1.bias is not None and fc2.bias is not None and fc1.weight.shape[1] % 64 == 0
-            and fc1.weight.shape[0] % 64 == 0 and fc2.weight.shape[0] % 64 == 0)
+            and fc1.weight.shape[0] % 64 == 0 and fc2.weight.shape[0] % 64 == 0
+            and _al16(x, fc1.weight, fc1.bias, fc2.weight, fc2.bias))
 
 
 class MlpFn(Function):
@@ -707,7 +714,8 @@ def linear_f32_usable(x, weight):
     K = x.shape[-1]
     N = weight.shape[0]
     return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_contiguous()
-            and weight.is_contiguous() and K % 4 == 0 and N % 4 == 0 and K >= 32 and N >= 32 and x.numel() // K >= 1)
+            and weight.is_contiguous() and K % 4 == 0 and N % 4 == 0 and K >= 32 and N >= 32 and x.numel() // K >= 1
+            and _al16(x, weight))
 
 
 class LinearF32Fn(Function):
@@ -873,9 +881,10 @@ class MlpF32Fn(Function):
         return dx, dw1, db1, dw2, db2, (dy if ctx.has_resid else None), None, None, None, None
 
 
-def mlp_f32_usable(x, fc1, fc2):
+def mlp_f32_usable(x, fc1, fc2, resid=None):
     return (linear_f32_usable(x, fc1.weight) and fc2.weight.dtype == torch.float32 and fc1.bias is not None
-            and fc2.bias is not None and fc2.weight.is_contiguous() and fc2.weight.shape[0] % 4 == 0)
+            and fc2.bias is not None and fc2.weight.is_contiguous() and fc2.weight.shape[0] % 4 == 0
+            and _al16(fc2.weight, fc1.bias, fc2.bias, resid))
 
 
 def mlp_f32(x, fc1, fc2, resid=None, math=0, x_image=None):
@@ -888,9 +897,11 @@ def linear_or_hip(x, lin, resid=None, use_hip=True, math=0, x_image=None):
     if x_image is not None:
         return LinearF32Fn.apply(x, lin.weight, lin.bias, resid, lin, math, x_image)
     if (use_hip and x.is_cuda and x.dtype == torch.bfloat16 and lin.weight.dtype == torch.bfloat16
-            and lin.weight.shape[1] % 64 == 0 and x.is_contiguous()):
+            and lin.weight.shape[1] % 64 == 0 and x.is_contiguous() and _al16(x, lin.weight)):
         return LinearBf16Fn.apply(x, lin.weight, lin.bias, resid, lin)
-    if use_hip and linear_f32_usable(x, lin.weight) and not torch.is_autocast_enabled():
+    # (fp16x2 has no scalar epilogue: its bias and residual are read as vectors too)
+    if (use_hip and linear_f32_usable(x, lin.weight) and not torch.is_autocast_enabled()
+            and (math != 2 or _al16(lin.bias, resid))):
         return LinearF32Fn.apply(x, lin.weight, lin.bias, resid, lin, math)
     y = torch.nn.functional.linear(x, lin.weight, lin.bias)
     return y if resid is None else resid + y
@@ -962,7 +973,7 @@ def conv1x1_fusable(x, weight, stride):
     if x.dtype == torch.float32 and torch.is_autocast_enabled():
         return False
     return (stride == 1 and weight.shape[2] == 1 and weight.shape[3] == 1 and ci % 64 == 0 and co % 64 == 0
-            and (H * W) % 8 == 0)
+            and (H * W) % 8 == 0 and _al16(x, weight))
 
 
 def _conv1x1_f32_launch(math, w2, w_transposed, x, addend, y, N, co, ci, hw, img=None):
@@ -1047,7 +1058,7 @@ def conv3x3_fusable(x, weight, stride, math):
     return (math == 1 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and stride == 1
             and tuple(weight.shape[2:]) == (3, 3) and x.is_contiguous() and not torch.is_autocast_enabled()
             and x.shape[1] % 16 == 0 and weight.shape[0] % 16 == 0 and x.shape[3] % 4 == 0 and x.shape[3] >= 16
-            and (x.shape[2] * x.shape[3]) % 16 == 0)
+            and (x.shape[2] * x.shape[3]) % 16 == 0 and _al16(x))
 
 
 CONV3X3_WIMG = True      # A/B: 3x3 convolutions with the packed weight as a split-product image
@@ -1204,6 +1215,7 @@ def conv_s2_plan(k, C, H, W, device):
 def conv_s2_fusable(x, weight, stride, math):
     """fp32 NCHW k x k stride-2 SAME convolution with split products that the tap-table kernels cover (k = 3 on C % 16 == 0 channels,
     k = 7 on <= 4): forward always; with gradients only on the shapes the weight-gradient kernel and the depth-to-space pass take."""
+    # (no alignment clause: the space-to-depth pass reads an input that is not 16-byte aligned scalar by scalar)
     if not (math == 1 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and stride == 2
             and x.is_contiguous() and not torch.is_autocast_enabled() and weight.shape[2] == weight.shape[3]):
         return False
@@ -1214,6 +1226,8 @@ def conv_s2_fusable(x, weight, stride, math):
     if (H2 * W2) % 4 != 0:
         return False
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+        if k == 7 and x.requires_grad:                      # the 7x7 reads the image: its tap plan has no input-gradient pass
+            return False
         return H % 2 == 0 and W % 8 == 0 and W2 >= 16 and (H2 * W2) % 16 == 0
     return True
 
@@ -1346,7 +1360,8 @@ class LayerNormFn(Function):
 def layer_norm_fusable(x, ln):
     C = x.shape[-1]
     return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and ln.weight.dtype == x.dtype and x.is_contiguous()
-            and C % 256 == 0 and C <= 1024 and not (x.dtype == torch.float32 and torch.is_autocast_enabled()))
+            and C % 256 == 0 and C <= 1024 and not (x.dtype == torch.float32 and torch.is_autocast_enabled())
+            and _al16(x, ln.weight, ln.bias))
 
 
 def layer_norm(x, ln):
@@ -1391,7 +1406,7 @@ class TokensFn(Function):
 
 def tokens_fusable(y, bias, prefix, pos):
     return (y.is_cuda and y.dim() == 4 and all(t.dtype == torch.float32 and t.is_contiguous() for t in (y, bias, prefix, pos))
-            and prefix.shape[0] <= 8 and pos.shape[1] == prefix.shape[0] + y.shape[2] * y.shape[3] and not torch.is_autocast_enabled())
+            and 1 <= prefix.shape[0] <= 8 and pos.shape[1] == prefix.shape[0] + y.shape[2] * y.shape[3] and not torch.is_autocast_enabled())
 
 
 def tokens(y, bias, prefix, pos):
@@ -1417,14 +1432,16 @@ GN_ACT = {"none": 0, "relu": 1, "add_relu": 2}
 
 
 def groupnorm_fusable(x, resid=None):
-    """Shapes/dtypes the fused bf16 GroupNorm kernel handles (everything else stays on torch ops)."""
-    if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.dim() == 4 and x.is_contiguous()):
+    """Shapes/dtypes the fused GroupNorm kernels handle (everything else stays on torch ops): exactly what gnf_check
+    (csrc/groupnorm_f32.hip) resp. gn_check (csrc/groupnorm.hip) and the entry points' alignment checks accept."""
+    if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.dim() == 4 and x.is_contiguous() and _al16(x, resid)):
         return False
     N, C, H, W = x.shape
-    if x.dtype == torch.float32:                            # streaming fp32 kernels: any group size, HW % 4 == 0
-        if C % 32 or (H * W) % 4 or torch.is_autocast_enabled():
+    if x.dtype == torch.float32:                            # streaming fp32 kernels: any map with HW % 4 == 0, up to 32 channels per group
+        if C % 32 or C // 32 > 32 or (H * W) % 4 or torch.is_autocast_enabled():
             return False
-    elif C % 32 or (H * W) % 8 or (C // 32) * H * W // 8 > 1024 * 13:
+    # register-resident bf16 kernels: up to 64 channels per group and 13 vectors of 8 per lane of a 1024-thread workgroup
+    elif C % 32 or C // 32 > 64 or (H * W) % 8 or (C // 32) * H * W // 8 > 1024 * 13:
         return False
     return resid is None or (resid.shape == x.shape and resid.dtype == x.dtype and resid.is_contiguous())
 

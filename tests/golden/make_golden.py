@@ -359,6 +359,17 @@ def main():
         run_infer_case("infer_hybrid_64", model, 64, (50, 70), 3)
     if "infer96" in which:
         run_infer_case("infer_hybrid_96", model, 96, (75, 61), 4)
+    # sizes that are no multiple of 32: stage maps 20/10/5 and 28/14/7 (H*W = 400, 100, 25 resp. 784, 196, 49), an odd token grid --
+    # the shapes at which the HIP dispatch predicates send some stages to the kernels and others to the library.  Named only:
+    # not part of the default set, so regenerating the others leaves these alone and the other way round
+    if "hyb80" in which:
+        run_train_case("train_hybrid_80_b1", model, model.forward_mirror, 80, 1, 20, 125, 14, gnames)
+    if "hyb112" in which:
+        run_train_case("train_hybrid_112_b1", model, model.forward_mirror, 112, 1, 20, 125, 15, gnames)
+    if "infer80" in which:
+        run_infer_case("infer_hybrid_80", model, 80, (67, 93), 16)
+    if "ms160" in which:             # the scale set at base 160: token grids 5, 10, 15, 20 -> T in {26, 101, 226, 401}
+        run_infer_case_big("infer_ms_hybrid_160", model, 160, (78, 104), 17, (0.5, 1.0, 1.5, 2.0), [("grad", 10, True)], [6, 14])
     if "hyb448" in which:
         run_train_case("train_hybrid_448_b1", model, model.forward_mirror, 448, 1, 20, 125, 5, gnames, sub=(97, 89))
 

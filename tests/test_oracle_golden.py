@@ -65,11 +65,19 @@ def test_train_hybrid_96(hybrid_sd):
     _check_train(load_golden("train_hybrid_96_b1"), hybrid_sd, O.HYBRID_BASE)
 
 
+def test_train_hybrid_80(hybrid_sd):
+    _check_train(load_golden("train_hybrid_80_b1"), hybrid_sd, O.HYBRID_BASE)
+
+
+def test_train_hybrid_112(hybrid_sd):
+    _check_train(load_golden("train_hybrid_112_b1"), hybrid_sd, O.HYBRID_BASE)
+
+
 def test_train_tiny_224(tiny_sd):
     _check_train(load_golden("train_tiny_224_b2"), tiny_sd, O.VIT_TINY)
 
 
-@pytest.mark.parametrize("name", ["infer_hybrid_64", "infer_hybrid_96"])
+@pytest.mark.parametrize("name", ["infer_hybrid_64", "infer_hybrid_96", "infer_hybrid_80"])
 def test_infer(hybrid_sd, name):
     fx = load_golden(name)
     size, W, H, seed = [int(v) for v in fx["meta"]]
@@ -100,7 +108,7 @@ def test_train_coco_512():
 
 
 def _big_cases():
-    names = ["infer_ms_hybrid_96", "infer_hybrid_384"]
+    names = ["infer_ms_hybrid_96", "infer_hybrid_384", "infer_ms_hybrid_160"]
     if os.environ.get("ACR_SLOW_ORACLE") == "1":          # ~4 min of CPU at T up to 2305: opt-in (the GPU test uses the fixture)
         names.append("infer_ms_hybrid_384")
     return names
