@@ -207,6 +207,8 @@ SIGNATURES = {
     "acr_relu_bwd_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "acr_upsample2x_fwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_upsample2x_bwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "acr_segpred_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                  c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

@@ -1,6 +1,7 @@
 """Dense-CRF refinement of CAMs on the GPU: the host mirror of ``imutils.crf_inference``
 (tool/imutils.py:345-362 -- pydensecrf's ``DenseCRF2D`` with ``addPairwiseGaussian(sxy=3, compat=3)``,
-``addPairwiseBilateral(sxy=80, srgb=13, compat=10)`` and ``inference(t)``) and of ``_crf_with_alpha``
+``addPairwiseBilateral(sxy=80, srgb=13, compat=10)`` and ``inference(t)``), of ``imutils.crf_inference_inf`` (:365-384, the
+validation's parameter set: bilateral sxy=83, srgb=5, compat=4) and of ``_crf_with_alpha``
 (infer_cam.py:27-40), same names, arguments and return layout.  All arithmetic runs in csrc/crf.hip behind the C ABI
 (``acr_lattice_*``, ``acr_crf_*``); there is no CPU path -- without the HIP library and a GPU these raise."""
 import ctypes
@@ -96,6 +97,26 @@ def crf_inference(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
 
 def crf_inference_device(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
     """``crf_inference`` with Q left where it was computed: a (labels, h, w) float32 tensor on ``device``."""
+    return _mean_field(img, probs, t, labels, device, (3 / scale_factor, 3), (80 / scale_factor, 13, 10))
+
+
+def crf_inference_inf(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
+    """tool/imutils.py:365-384, the parameter set the reference's validation refines its probabilities with
+    (myTool.py:1819-1823): ``addPairwiseGaussian(sxy=3, compat=3)``, ``addPairwiseBilateral(sxy=83, srgb=5, compat=4)``.
+    img (h, w, 3) uint8, probs (labels, h, w) -> Q (labels, h, w) float32 numpy array."""
+    return crf_inference_inf_device(img, probs, t, scale_factor, labels, device).cpu().numpy()
+
+
+def crf_inference_inf_device(img, probs, t=10, scale_factor=1, labels=21, device="cuda"):
+    """``crf_inference_inf`` with Q left on the device.  ``probs`` may also be a contiguous (labels, h, w) float32 tensor that
+    already sits on the GPU (what ``segval.predict`` accumulated): it is then read in place, with no host round trip, and the
+    result has the bits the same values give as a numpy array."""
+    return _mean_field(img, probs, t, labels, device, (3 / scale_factor, 3), (83 / scale_factor, 5, 4))
+
+
+def _mean_field(img, probs, t, labels, device, gaussian, bilateral):
+    """The loop all parameter sets share: unary_from_softmax, a Gaussian kernel ``(sxy, compat)`` and a bilateral kernel
+    ``(sxy, srgb, compat)``, ``t`` iterations -> Q (labels, h, w) float32 on ``device``."""
     lib = L.load()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -103,13 +124,21 @@ def crf_inference_device(img, probs, t=10, scale_factor=1, labels=21, device="cu
     img = np.ascontiguousarray(img)
     h, w = img.shape[:2]
     n = h * w
-    p = torch.as_tensor(np.ascontiguousarray(probs, dtype=np.float32)).reshape(labels, n).to(dev)
+    if torch.is_tensor(probs):
+        L.require_gpu(probs)
+        if probs.dtype != torch.float32 or tuple(probs.shape) != (labels, h, w) or not probs.is_contiguous():
+            raise ValueError("probs on the device must be a contiguous (%d, %d, %d) float32 tensor, got %s %s"
+                             % (labels, h, w, probs.dtype, tuple(probs.shape)))
+        dev = probs.device
+        p = probs.reshape(labels, n)
+    else:
+        p = torch.as_tensor(np.ascontiguousarray(probs, dtype=np.float32)).reshape(labels, n).to(dev)
     unary = torch.empty_like(p)
     q = torch.empty_like(p)
     with torch.cuda.device(dev):
         L.check(lib.acr_crf_unary(L.ptr(p), L.ptr(unary), labels * n, 1e-5, L.stream_ptr()), "acr_crf_unary")
-        kernels = [_Kernel(PermutohedralLattice(h, w, 3 / scale_factor, device=dev), 3),
-                   _Kernel(PermutohedralLattice(h, w, 80 / scale_factor, rgb=img, srgb=13, device=dev), 10)]
+        kernels = [_Kernel(PermutohedralLattice(h, w, gaussian[0], device=dev), gaussian[1]),
+                   _Kernel(PermutohedralLattice(h, w, bilateral[0], rgb=img, srgb=bilateral[1], device=dev), bilateral[2])]
         L.check(lib.acr_crf_update(L.ptr(unary), None, None, L.ptr(q), n, labels, L.stream_ptr()), "acr_crf_update")
         msg = [torch.empty_like(p), torch.empty_like(p)]
         for _ in range(t):

@@ -752,6 +752,30 @@ int acr_relu_bwd_f32(const float* y, const float* dy, int64_t n, float* dx, void
 int acr_upsample2x_fwd(const float* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* y, void* stream);
 int acr_upsample2x_bwd(const float* dy, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* dx, void* stream);
 
+/* ---- segmentation prediction (myTool.py:1826-1895 validation: the resize of the logits to the image's own size :1881, the softmax
+ * :1883 and the argmax :1891, or the probabilities _crf_with_alpha_2 :1819-1823 hands to the CRF) in one pass ----
+ * logits (B, K, h, w) fp32 contiguous; label (B, H, W) uint8, nullable; probs (B, K, H, W) fp32, nullable; at least one output.
+ * Requires 1 <= B <= 65535, 2 <= K <= 128, h, w, H, W >= 1, K * h * w < 2^31, K * H * W < 2^31; anything else returns
+ * ACR_ERR_INVALID.  Inputs are finite: NaN is outside the contract.
+ * Interpolation: per output pixel (Y, X), v_k = the bilinear interpolation of plane k by torch's align_corners=False rule in fp32
+ *   (the rule of acr_bilinear_resize and acr_segloss_fwd), for any h, w, H, W -- enlarging, shrinking, the identity, h = w = 1.
+ *   Per axis (aten/src/ATen/native/UpSample.h), computed once per pixel and used for all K planes:
+ *       scale = in / out,  src = max(scale * (dst + 0.5) - 0.5, 0),  i0 = min((int)src, in - 1),
+ *       lambda = src - i0,  i1 = i0 + (i0 < in - 1)
+ *   rows outside, columns inside, with hy = 1 - ly, hx = 1 - lx and no fused multiply-add:
+ *       v = hy * (hx * p[y0][x0] + lx * p[y0][x1]) + ly * (hx * p[y1][x0] + lx * p[y1][x1])
+ * Flip: hflip != 0 says the pass ran on the mirrored image: columns x0, x1 are read at w - 1 - x0, w - 1 - x1 with the same
+ *   weights, so the result equals, bit for bit, that of hflip = 0 on the logits flipped along w.
+ * Softmax: m = max_k v_k;  p_k = exp(v_k - m) / sum_j exp(v_j - m), in fp32, the sum in ascending j.
+ * accumulate == 0: probs, if given, is WRITTEN with p; label, if given, is the smallest k among the maxima of v (the argmax of the
+ *   logits, :1891; the first-maximum convention of acr_pseudo_label_f32).
+ * accumulate != 0 (probs required): probs += p, one fp32 add per value; label, if given, is the smallest k among the maxima of the
+ *   UPDATED probs -- test-time augmentation over scales and flips: the last pass leaves the final label map, with no extra launch.
+ * No atomics, a fixed order, nothing outside the tensors is read or written: bit-identical run to run.  The entry point allocates
+ * nothing and does not synchronise; it captures into a hipGraph. */
+int acr_segpred_f32(const float* logits, int32_t B, int32_t K, int32_t h, int32_t w, int32_t H, int32_t W, int32_t hflip,
+                    int32_t accumulate, float* probs, uint8_t* label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
