@@ -162,6 +162,8 @@ SIGNATURES = {
     "acr_subsample2_bwd_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "acr_preprocess_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
                                        c_int32, c_void_p, c_void_p]),
+    "acr_preprocess_seg_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.POINTER(c_float),
+                                           ctypes.POINTER(c_float), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "acr_lattice_ws_bytes": (c_int64, [c_int32, c_int32]),
     "acr_lattice_build": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_int64, c_void_p]),
     "acr_lattice_info": (c_int32, [c_void_p, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32), c_void_p]),

@@ -15,6 +15,11 @@ and returns the same contract as the reference: images (B,3,S,S) + labels (B,C) 
 (voc12/make_cls_labels.py:18-22).  The draws follow the reference's order (np.random.uniform for the flip, then
 random.randint / random.randrange) from SEEDABLE generators (the reference's are the unseeded globals, train_acr.py:23).
 There is no CPU path: tensors land on the GPU through the HIP kernel or the call raises.
+
+Segmentation training (myTool.py:1257-1310 `get_data_from_chunk_v4`: image + target map; :1202-1253 `_v3`: image + saliency map)
+puts a single-channel uint8 map through the image's own resize (nearest) / flip / crop: `preprocess_seg_batch`, `SegTrainBatcher`
+and `ChunkLoader.get_data_from_chunk_v4 / _v3` give images, the de-normalised uint8 `ori_images`, the `croppings` masks and the map
+from ONE launch (`acr_preprocess_seg_batch`), on the device and shaped for `segloss.joint_loss`.
 """
 import concurrent.futures
 import ctypes
@@ -142,6 +147,119 @@ def val_batch(images_uint8, crop_size, device="cuda", dtype=torch.float32):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Segmentation training: image + companion map through one geometry (myTool.py:1202-1253 v3, :1257-1310 v4)
+# ------------------------------------------------------------------------------------------------------------------
+def _check_seg_inputs(images_uint8, maps_uint8, records, S):
+    """Everything acr_preprocess_seg_batch trusts, judged on the host before any device is asked for."""
+    if len(images_uint8) == 0 or len(images_uint8) != len(maps_uint8) or len(records) != len(images_uint8):
+        raise ValueError("need one map and one record per image (got %d images, %d maps, %d records)"
+                         % (len(images_uint8), len(maps_uint8), len(records)))
+    if not 0 < int(S) <= 32768:
+        raise ValueError("crop size %r outside 1..32768" % (S,))
+    for i, (a, m, rec) in enumerate(zip(images_uint8, maps_uint8, records)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise ValueError("image %d must be a (h, w, 3) uint8 RGB array, got %s %s" % (i, getattr(a, "dtype", type(a)), getattr(a, "shape", "")))
+        if not isinstance(m, np.ndarray) or m.dtype != np.uint8:
+            raise ValueError("map %d must be a uint8 array, got %s" % (i, getattr(m, "dtype", type(m))))
+        if m.ndim != 2:
+            raise ValueError("map %d must be 2-D (h, w), got shape %s" % (i, m.shape))
+        if m.shape != a.shape[:2]:
+            raise ValueError("map %d is %s, its image %s" % (i, m.shape, a.shape[:2]))
+        ok = (rec["h"] == a.shape[0] and rec["w"] == a.shape[1] and rec["rh"] > 0 and rec["rw"] > 0
+              and 0 <= rec["cont_top"] and rec["cont_top"] + rec["ch"] <= S and 0 <= rec["cont_left"] and rec["cont_left"] + rec["cw"] <= S
+              and 0 <= rec["img_top"] and rec["img_top"] + rec["ch"] <= rec["rh"] and 0 <= rec["img_left"]
+              and rec["img_left"] + rec["cw"] <= rec["rw"] and rec["ch"] >= 0 and rec["cw"] >= 0 and rec["flip"] in (0, 1)
+              and 2 * int(rec["rh"]) * int(rec["h"]) < 2 ** 31 and 2 * int(rec["rw"]) * int(rec["w"]) < 2 ** 31)     # the kernel's int32 sample positions
+        if not ok:
+            raise L.AcrHipError("acr_preprocess_seg_batch: inconsistent geometry record %s for a %s image" % (rec, a.shape))
+
+
+def preprocess_seg_batch(images_uint8, maps_uint8, records, S, device, dtype=torch.float32, map_fill=0, with_ori=True, *,
+                         with_croppings=True, with_map=True):
+    """Run acr_preprocess_seg_batch (include/acr_hip.h): ``images_uint8`` = list of (h,w,3) uint8 RGB arrays, ``maps_uint8`` = list of
+    (h,w) uint8 maps, one per image and of its size, ``records`` = PRE_IMAGE array with everything but ``offset`` filled in.  Images
+    and maps share one pinned staging buffer: one H2D copy, one launch.  Returns device tensors
+    ``(images (B,3,S,S) dtype, ori_images (B,3,S,S) uint8, croppings (B,S,S) float32, maps (B,S,S) uint8)``; an output that was not
+    asked for is None.  ``map_fill`` is what the map holds outside the crop box: 0 as in the reference (myTool.py:982), or 255 (this
+    project's extension) so that a cross-entropy with ignore skips the padding."""
+    _check_seg_inputs(images_uint8, maps_uint8, records, S)
+    if not 0 <= int(map_fill) <= 255:
+        raise ValueError("map_fill=%r outside 0..255" % (map_fill,))
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dtype must be float32 or bfloat16, got %s" % (dtype,))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.AcrHipError("acr_wsss_amd.data runs on the GPU only (acr_preprocess_seg_batch); there is no CPU path")
+    B = len(images_uint8)
+    arrays = list(images_uint8) + list(maps_uint8)
+    sizes = [int(a.size) for a in arrays]
+    offs = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])       # 16-byte aligned images and maps
+    stage = torch.empty(int(offs[-1]), dtype=torch.uint8).pin_memory()
+    sn = stage.numpy()
+    for a, o, s in zip(arrays, offs[:-1], sizes):
+        sn[o:o + s] = np.ascontiguousarray(a).reshape(-1)
+    records = records.copy()
+    records["offset"] = offs[:B]
+    packed = stage.to(device, non_blocking=True)
+    # the record table and, right behind it, the int64 map offsets: one pinned buffer, one copy
+    raw = np.concatenate([records.view(np.uint8).reshape(-1), offs[B:2 * B].astype("<i8").view(np.uint8)])
+    table_host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)
+    table_host.numpy()[:] = raw
+    table = table_host.to(device, non_blocking=True)
+    map_offs = table[B * PRE_IMAGE.itemsize:]
+    images = torch.empty((B, 3, S, S), dtype=dtype, device=device)
+    ori = torch.empty((B, 3, S, S), dtype=torch.uint8, device=device) if with_ori else None
+    crop = torch.empty((B, S, S), dtype=torch.float32, device=device) if with_croppings else None
+    maps = torch.empty((B, S, S), dtype=torch.uint8, device=device) if with_map else None
+    mean = (ctypes.c_float * 3)(*MEAN)
+    std = (ctypes.c_float * 3)(*STD)
+    with torch.cuda.device(device):
+        L.check(L.load().acr_preprocess_seg_batch(L.ptr(packed), L.ptr(table), L.ptr(map_offs), B, S, mean, std,
+                                                  L.ACR_BF16 if dtype == torch.bfloat16 else L.ACR_F32, int(map_fill), L.ptr(images),
+                                                  L.ptr(ori), L.ptr(crop), L.ptr(maps), L.stream_ptr()), "acr_preprocess_seg_batch")
+    images._acr_keep = (stage, packed, table)               # the staging buffers must outlive the asynchronous copies
+    return images, ori, crop, maps
+
+
+class SegTrainBatcher(TrainBatcher):
+    """get_data_from_chunk_v4 / _v3 (myTool.py:1257-1310, :1202-1253) for a chunk of decoded images and their maps.  The draws
+    follow the reference's order: per chunk the unused ``scale`` (:1260), then per image flip_p (:1275), ``randint(lo, hi)`` of
+    RandomResizeLong2 (:1011) and the RandomCrop2 draws, w before h (:967-979).  ``long_range`` = (lo, hi): None means (S, S), which is
+    v4 (:1284; ``randint(S, S)`` still consumes a draw); v3 uses ``(int(0.9 * S), int(S / 0.875))`` (:1228).  ``map_fill``: see
+    ``preprocess_seg_batch``."""
+
+    def __init__(self, crop_size, device="cuda", seed=None, dtype=torch.float32, long_range=None, map_fill=0):
+        super().__init__(crop_size, device, seed, dtype)
+        lo, hi = (crop_size, crop_size) if long_range is None else (int(long_range[0]), int(long_range[1]))
+        if not 0 < lo <= hi:
+            raise ValueError("long_range %r must be 0 < lo <= hi" % (long_range,))
+        self.long_range, self.map_fill = (lo, hi), map_fill
+
+    def draw(self, h, w):
+        flip_p = self.nprandom.uniform(0, 1)
+        target_long = self.pyrandom.randint(*self.long_range)
+        nh, nw = resize_long_target(h, w, target_long)
+        ct, cl, it, il, ch, cw = random_crop_boxes(nh, nw, self.S, self.pyrandom)
+        return (0, h, w, nh, nw, int(flip_p > 0.5), ct, cl, it, il, ch, cw, 0)
+
+    def __call__(self, images_uint8, maps_uint8, labels, with_ori=True):
+        """images_uint8: list of (h,w,3) uint8 RGB arrays; maps_uint8: list of (h,w) uint8 maps; labels: (B,C) tensor.  Returns
+        ``(images, ori_images, labels, croppings, target)`` on the device, shaped for ``segloss.joint_loss``: ori_images (B,3,S,S)
+        uint8, croppings the (S,S,B) view of a contiguous (B,S,S) float32 buffer (the reference's layout, :1267; joint_loss permutes
+        it back without a copy), target (B,S,S) uint8 (the reference returns float: ``target.float()`` gives that)."""
+        for a, m in zip(images_uint8, maps_uint8):           # before any draw: a refused chunk leaves the generators alone
+            if getattr(a, "ndim", 0) != 3 or getattr(m, "shape", None) != a.shape[:2]:
+                raise ValueError("every map must be (h, w) like its (h, w, 3) image, got %s for %s" % (getattr(m, "shape", None), getattr(a, "shape", None)))
+        self.nprandom.uniform(0.7, 1.3)                     # :1260 / :1205: `scale`, drawn once per chunk and never used
+        rec = np.zeros(len(images_uint8), PRE_IMAGE)
+        for i, a in enumerate(images_uint8):
+            rec[i] = self.draw(int(a.shape[0]), int(a.shape[1]))
+        self.last_records = rec
+        images, ori, crop, target = preprocess_seg_batch(images_uint8, maps_uint8, rec, self.S, self.device, self.dtype, self.map_fill, with_ori)
+        return images, ori, labels.to(self.device, non_blocking=True), crop.permute(1, 2, 0), target
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # The reference's own call contract: names in, tensors out (myTool.py:1158-1199, :1364-1403)
 # ------------------------------------------------------------------------------------------------------------------
 def decode_rgb(path):
@@ -150,6 +268,14 @@ def decode_rgb(path):
     from PIL import Image
     with Image.open(path) as im:
         return np.asarray(im.convert("RGB"))
+
+
+def decode_map(path):
+    """One single-channel map file -> (h, w) uint8 (myTool.py:1224-1225, :1279-1280: ``np.asarray(PIL.Image.open(path))``).  A palette
+    PNG yields its indices, which is what ``pseudo.save_label_png`` writes."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im)
 
 
 class ChunkLoader:
@@ -162,11 +288,18 @@ class ChunkLoader:
         for images, ori_images, labels, names in loader.iterate(chunks, train=True):    # decode of chunk i+1 overlaps step i
 
     `cls_labels`: the `voc12/cls_labels.npy` dict {name: float32 (C,)} (myTool.py:916-920) or its path.  `ori_images`
-    (de-normalised uint8 crops, :1186-1190, which no caller of the training loop reads) is None unless `with_ori=True`."""
+    (de-normalised uint8 crops, :1186-1190, which no caller of the training loop reads) is None unless `with_ori=True`.
+
+    With `map_dir` (and `map_ext`, default ".png") the loader also serves segmentation training:
+        images, ori_images, labels, croppings, names, target = loader.get_data_from_chunk_v4(chunk)    # or _v3: saliency maps
+        for batch in loader.iterate(chunks, kind="v4"): ...
+    where the map of image <name> is <map_dir>/<name><map_ext> and `map_fill` is what the map holds outside the crop box."""
 
     def __init__(self, img_dir, cls_labels, crop_size, device="cuda", seed=None, workers=8, dtype=torch.float32, ext=".jpg",
-                 with_ori=False):
+                 with_ori=False, map_dir=None, map_ext=".png", map_fill=0):
         self.img_dir, self.S, self.ext, self.with_ori = img_dir, crop_size, ext, with_ori
+        self.map_dir, self.map_ext, self.map_fill = map_dir, map_ext, map_fill
+        self._seg_batchers = {}
         self.device, self.dtype = torch.device(device), dtype
         if isinstance(cls_labels, (str, os.PathLike)):
             cls_labels = np.load(cls_labels, allow_pickle=True).item()
@@ -208,16 +341,62 @@ class ChunkLoader:
         """myTool.py:1364-1403: plain resize to S x S + normalise."""
         return self._finish(chunk, self._submit(chunk), False)
 
-    def iterate(self, chunks, train=True, depth=2):
+    # ---- segmentation training: image + map (myTool.py:1257-1310 v4, :1202-1253 v3) ----
+    def _seg_batcher(self, kind):
+        """One SegTrainBatcher per kind, all drawing from this loader's two generators (the reference's are the process globals)."""
+        if kind not in ("v3", "v4"):
+            raise ValueError("kind must be 'v2', 'v3' or 'v4', got %r" % (kind,))
+        if self.map_dir is None:
+            raise ValueError("get_data_from_chunk_%s needs ChunkLoader(map_dir=...)" % kind)
+        b = self._seg_batchers.get(kind)
+        if b is None:
+            S = self.S
+            b = SegTrainBatcher(S, self.device, None, self.dtype, None if kind == "v4" else (int(S * 0.9), int(S / 0.875)), self.map_fill)
+            b.pyrandom, b.nprandom = self.batcher.pyrandom, self.batcher.nprandom
+            self._seg_batchers[kind] = b
+        return b
+
+    def _submit_seg(self, chunk):
+        return (self._submit(chunk), [self.pool.submit(decode_map, os.path.join(self.map_dir, name + self.map_ext)) for name in chunk])
+
+    def _finish_seg(self, chunk, futures, kind):
+        decoded = [f.result() for f in futures[0]]
+        maps = [f.result() for f in futures[1]]
+        images, ori, labels, croppings, target = self._seg_batcher(kind)(decoded, maps, self._labels(chunk))
+        return images, ori, labels, croppings, list(chunk), target
+
+    def get_data_from_chunk_v4(self, chunk):
+        """myTool.py:1257-1310 -> (images (B,3,S,S), ori_images (B,3,S,S) uint8, labels (B,C), croppings (S,S,B) float32, name_list,
+        target (B,S,S) uint8), all tensors on the device and shaped for ``segloss.joint_loss`` (see ``SegTrainBatcher.__call__``;
+        the reference's target is float: ``target.float()``).  The map of image <name> is ``<map_dir>/<name><map_ext>`` (the
+        reference hard-codes its directory, :1278); the long side is resized to exactly S (:1284)."""
+        self._seg_batcher("v4")
+        return self._finish_seg(chunk, self._submit_seg(chunk), "v4")
+
+    def get_data_from_chunk_v3(self, chunk):
+        """myTool.py:1202-1253: the same tuple with the saliency map of ``map_dir`` as the last element and the long side drawn from
+        [int(0.9 * S), int(S / 0.875)] (:1228)."""
+        self._seg_batcher("v3")
+        return self._finish_seg(chunk, self._submit_seg(chunk), "v3")
+
+    def iterate(self, chunks, train=True, depth=2, kind="v2"):
         """Yield the batches of `chunks` in order while the pool already decodes the next `depth` chunks (the previous step's
-        GPU work and this thread's Python run meanwhile; the RNG draws stay in chunk order because they happen here)."""
+        GPU work and this thread's Python run meanwhile; the RNG draws stay in chunk order because they happen here).  ``kind``:
+        "v2" (classification: get_data_from_chunk_v2 / _val) or "v3" / "v4" (the segmentation tuples; training only)."""
         chunks = list(chunks)
-        pending = [self._submit(c) for c in chunks[:depth]]
+        if kind == "v2":
+            submit, finish = self._submit, lambda c, f: self._finish(c, f, train)
+        else:
+            self._seg_batcher(kind)
+            if not train:
+                raise ValueError("kind=%r has no validation form; use train=True" % (kind,))
+            submit, finish = self._submit_seg, lambda c, f: self._finish_seg(c, f, kind)
+        pending = [submit(c) for c in chunks[:depth]]
         for i, chunk in enumerate(chunks):
             futures = pending.pop(0)
             if i + depth < len(chunks):
-                pending.append(self._submit(chunks[i + depth]))
-            yield self._finish(chunk, futures, train)
+                pending.append(submit(chunks[i + depth]))
+            yield finish(chunk, futures)
 
 
 def chunker(seq, size):

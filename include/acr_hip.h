@@ -548,6 +548,33 @@ typedef struct acr_pre_image {
 int acr_preprocess_batch(const void* packed_u8, const void* table, int32_t batch, int32_t S, const float* mean3,
                          const float* std3, int32_t out_dtype, void* out, void* stream);
 
+/* ---- segmentation-training loaders (myTool.py:1257-1310 get_data_from_chunk_v4: image + target map; :1202-1253
+ * get_data_from_chunk_v3: image + saliency map, the same code with another resize range; both on RandomResizeLong2 :1010-1023,
+ * flip2 :901-905 and RandomCrop2 :957-993) ----
+ * A sibling of acr_preprocess_batch: ONE launch writes the four tensors a chunk yields, all from the image's acr_pre_image
+ * record.  packed_u8 holds the RGB images AND the single-channel uint8 maps (one H2D copy); map_offsets[b] is the byte offset of
+ * image b's (h, w) map inside packed_u8 (a device array next to `table`; read only when map_u8 is given).  With (y, x) an output
+ * pixel, "inside" means cont_top <= y < cont_top + ch and cont_left <= x < cont_left + cw; an inside pixel is pixel
+ * (ry, rx) = (img_top + y - cont_top, img_left + x - cont_left) of the resized and flipped image, i.e. column rw - 1 - rx of the
+ * resized one when flip is set.
+ *   images    (B,3,S,S) out_dtype: exactly what acr_preprocess_batch writes for the same table -- same integer sample positions,
+ *             same arithmetic, bit for bit (0 outside).
+ *   ori_u8    (B,3,S,S) uint8 (:1293-1297): a pure function of the fp32 value x computed for `images` (before any bf16 rounding),
+ *             trunc((x * std_c + mean_c) * 255) evaluated as fp32 multiply, add, multiply WITHOUT contraction (numpy on the
+ *             reference's float32 container) and clamped to 0..255 before the conversion.  Outside: (123, 116, 103).
+ *   croppings (B,S,S) fp32 (:984,991): 1 inside, 0 outside.
+ *   map_u8    (B,S,S) uint8: the map through resize-nearest -> flip -> crop with the image's geometry.  Resized pixel (ry, rx)
+ *             reads source (min(ry * h / rh, h - 1), min(rx * w / rw, w - 1)) in integer division: OpenCV's published
+ *             INTER_NEAREST rule floor(d * src / dst).  cv2 is not part of the reference tree, so this step is UNPINNED in the
+ *             same sense as the bilinear rule above; OpenCV evaluates the product d * (src / dst) in double, which can differ from
+ *             the exact quotient where d * src / dst is an integer.  Outside the crop box the map holds map_fill (0..255): 0 is
+ *             the reference's zero container (:982); 255, the cross-entropy's ignore value, is this project's extension.
+ * ori_u8, croppings and map_u8 may each be NULL and are then skipped.  With S % 4 == 0 every output is written with 4-pixel
+ * vector stores, so all four buffers must be 16-byte aligned.  The kernel trusts table and map_offsets: the caller validates them. */
+int acr_preprocess_seg_batch(const void* packed_u8, const void* table, const int64_t* map_offsets, int32_t batch, int32_t S,
+                             const float* mean3, const float* std3, int32_t out_dtype, int32_t map_fill, void* images,
+                             void* ori_u8, void* croppings, void* map_u8, void* stream);
+
 /* ---- dense-CRF refinement of CAMs (tool/imutils.py:345-362 crf_inference = pydensecrf DenseCRF2D with
  * addPairwiseGaussian + addPairwiseBilateral + inference(t), called by infer_cam.py:27-40,218-225) ----
  * The permutohedral lattice follows wrapper/bilateralfilter/permutohedral.cpp:112-283 (init) and :441-520 (compute).
