@@ -194,6 +194,10 @@ SIGNATURES = {
     "acr_pseudo_label_f32": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_pseudo_compose": (c_int32, [c_void_p, ctypes.POINTER(c_int32), c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                      ctypes.c_double, c_float, ctypes.c_double, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_sal_pseudo_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "acr_sal_pseudo_compose": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_double, ctypes.c_double,
+                                         c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "acr_morph_open_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_segloss_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "acr_segloss_fwd": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -10,11 +10,9 @@
 // per class then picks the bin that holds the wanted rank and extends the prefix.  The first pass rides in the per-pixel kernel
 // that also writes the combined label map, so uncertainty costs 1 + 3 + 4 + 1 further small launches, none of them data dependent.
 #include "acr_common.h"
+#include "pseudo_select.h"                   // the radix selection shared with pseudo_sal.hip
 
 #define PSEUDO_MAX_LABELS 128            // C + 1 <= 128: labels and plane indices travel as bytes
-#define PSEUDO_MAX_BLOCKS 512
-#define PSEUDO_BINS 256
-#define PSEUDO_PASSES 4
 #define PSEUDO_SEL_NONE 255              // sel map: the pixel is in no selection set and can never be sure
 #define PSEUDO_SEL_BG 254                // sel map: M == 0 and bg > bg_sure (sure iff label 0 occurs in L_la)
 // workspace, in 32-bit words: OCC (128: label l occurs in L_la) | PREFIX (128: bits of v per plane) | RANK (128) |
@@ -22,8 +20,6 @@
 #define PSEUDO_O_PREFIX 128
 #define PSEUDO_O_RANK 256
 #define PSEUDO_O_HIST 384
-#define PSEUDO_EMPTY 0xffffffffu         // RANK of a plane whose selection set is empty
-#define PSEUDO_INF_BITS 0x7f800000u      // its v: +inf, above which no value lies
 
 struct pseudo_classes {
     int32_t first_absent;                // 1 + the smallest class index without a plane, 0: every class has one
@@ -146,10 +142,7 @@ __global__ __launch_bounds__(256) void pseudo_pixel_kernel(const float* __restri
     }
     if (UNC) {
         __syncthreads();
-        for (int i = tid; i < K * PSEUDO_BINS; i += 256) {
-            const uint32_t v = hist[i];
-            if (v) atomicAdd(&ws[PSEUDO_O_HIST + i], v);
-        }
+        pseudo_hist_merge(hist, ws + PSEUDO_O_HIST, K * PSEUDO_BINS);
         if (tid < PSEUDO_MAX_LABELS && occ[tid]) atomicOr(&ws[tid], 1u);
     }
 }
@@ -171,48 +164,16 @@ __global__ __launch_bounds__(256) void pseudo_hist_kernel(const float* __restric
         }
     }
     __syncthreads();
-    uint32_t* g = ws + PSEUDO_O_HIST + (size_t)pass * K * PSEUDO_BINS;
-    for (int i = tid; i < K * PSEUDO_BINS; i += 256) {
-        const uint32_t v = hist[i];
-        if (v) atomicAdd(&g[i], v);
-    }
+    pseudo_hist_merge(hist, ws + PSEUDO_O_HIST + (size_t)pass * K * PSEUDO_BINS, K * PSEUDO_BINS);
 }
 
 // one workgroup per class plane, one thread per bin: the bin of this pass that holds the wanted rank.  Pass 0 knows n = |S| and
 // sets the rank int(n * fg_quantile), the product in double (:719); an empty S gets v = +inf.
 __global__ __launch_bounds__(256) void pseudo_pick_kernel(uint32_t* __restrict__ ws, int K, int pass, double fg_quantile) {
     __shared__ uint32_t incl[PSEUDO_BINS];
-    const int tid = threadIdx.x, j = blockIdx.x;
-    const int shift = 24 - 8 * pass;
-    const uint32_t c = ws[PSEUDO_O_HIST + ((size_t)pass * K + j) * PSEUDO_BINS + tid];
-    uint32_t k = pass ? ws[PSEUDO_O_RANK + j] : 0u;
-    const uint32_t prefix = pass ? ws[PSEUDO_O_PREFIX + j] : 0u;
-    incl[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < PSEUDO_BINS; d <<= 1) {          // inclusive prefix sum over the 256 bins
-        const uint32_t add = tid >= d ? incl[tid - d] : 0u;
-        __syncthreads();
-        incl[tid] += add;
-        __syncthreads();
-    }
-    const uint32_t n = incl[PSEUDO_BINS - 1];
-    if (pass == 0) {
-        if (n == 0) {
-            if (tid == 0) {
-                ws[PSEUDO_O_PREFIX + j] = PSEUDO_INF_BITS;
-                ws[PSEUDO_O_RANK + j] = PSEUDO_EMPTY;
-            }
-            return;
-        }
-        k = (uint32_t)((double)n * fg_quantile);         // < n: 0 <= fg_quantile < 1
-    } else if (k == PSEUDO_EMPTY) {
-        return;
-    }
-    const uint32_t hi = incl[tid], lo = hi - c;
-    if (lo <= k && k < hi) {                             // exactly one bin: 0 <= k < n
-        ws[PSEUDO_O_PREFIX + j] = prefix | ((uint32_t)tid << shift);
-        ws[PSEUDO_O_RANK + j] = k - lo;
-    }
+    const int j = blockIdx.x;
+    pseudo_pick_bin(ws + PSEUDO_O_HIST + ((size_t)pass * K + j) * PSEUDO_BINS, ws + PSEUDO_O_PREFIX + j, ws + PSEUDO_O_RANK + j, pass,
+                    fg_quantile, false, incl);
 }
 
 // :721-722,730,735,737: a pixel that is not sure becomes 255
@@ -238,11 +199,6 @@ __global__ __launch_bounds__(256) void pseudo_finish_kernel(const float* __restr
 // nodes only
 __global__ __launch_bounds__(256) void pseudo_clear_kernel(uint32_t* __restrict__ ws, int64_t words) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) ws[i] = 0u;
-}
-
-static unsigned pseudo_blocks(int64_t pixels) {
-    const int64_t b = (pixels + 255) / 256;
-    return (unsigned)(b < PSEUDO_MAX_BLOCKS ? b : PSEUDO_MAX_BLOCKS);
 }
 
 // shared argument checks; fills cls

@@ -5,7 +5,12 @@ All of it runs in csrc/pseudo.hip behind the C ABI (``acr_pseudo_label_f32``, ``
 include/acr_hip.h states the rule in full); there is no CPU path -- without the HIP library and a GPU these raise.  The result is
 an exact function of the inputs: uint8 labels 0..C and 255 (ignore), identical bits run to run.  One definition beyond the
 reference: a label of the low-alpha map whose class never wins the CAM argmax above ``cam_floor`` has no sure pixel (the reference
-raises IndexError there).  Only this rule is covered; the reference's saliency variants are not."""
+raises IndexError there).
+
+``seg_label_saliency`` is the saliency-guided rule the reference marks "# use this" (``compute_seg_label_3``, myTool.py:188-264;
+``bg_alpha=32`` gives the label ``compute_seg_label_two_step`` composes, :313-367): a whole batch at once in csrc/pseudo_sal.hip
+behind ``acr_sal_pseudo_compose``, its 10 x 10 opening also on its own as ``morph_open`` (``acr_morph_open_u8``).  Of the
+reference's saliency variants the CRF-based siblings and the COCO ones are not covered, nor ``two_step``'s resize and PNG writes."""
 import ctypes
 
 import numpy as np
@@ -106,6 +111,93 @@ def seg_label(cams, classes, la, ha, *, ignore_uncertain=False, bg_alpha=36, cam
         L.check(lib.acr_pseudo_compose(L.ptr(cams), arr, k, L.ptr(la), L.ptr(ha), w, h, int(num_classes), 1 if ignore_uncertain else 0,
                                        float(bg_alpha), float(cam_floor), float(fg_quantile), float(bg_sure), float(crf_sure),
                                        L.ptr(ws), nbytes, L.ptr(out), L.stream_ptr()), "acr_pseudo_compose")
+    return out
+
+
+MAX_SAL_CLASSES = 127                     # labels c + 1 next to 255 (include/acr_hip.h)
+OPEN_TILE = 64                            # edge of the opening kernel's output tile (PSAL_TILE, csrc/pseudo_sal.hip)
+MAX_OPEN = 32                             # largest opening box
+
+
+def _bytes_on(a, name, dev, shape=None, ndim=None):
+    """contiguous uint8 (bool counts) on ``dev``; numpy arrays are uploaded"""
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+        if a.dtype not in (np.uint8, np.bool_):
+            raise ValueError("%s must be uint8 or bool, got %s" % (name, a.dtype))
+        a = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev, non_blocking=True)
+    L.require_gpu(a)
+    if a.dtype == torch.bool:
+        a = a.contiguous().view(torch.uint8)
+    if a.dtype != torch.uint8 or not a.is_contiguous():
+        raise ValueError("%s must be a contiguous uint8 tensor, got %s with strides %s" % (name, a.dtype, tuple(a.stride())))
+    if a.device != dev:
+        raise ValueError("%s lies on %s, the other inputs on %s" % (name, a.device, dev))
+    if a.numel() == 0 or (shape is not None and tuple(a.shape) != tuple(shape)) or (ndim is not None and a.dim() != ndim):
+        want = tuple(shape) if shape is not None else "not empty" if ndim is None else "%d-d and not empty" % ndim
+        raise ValueError("%s %s must be %s" % (name, tuple(a.shape), want))
+    return a
+
+
+def seg_label_saliency(cams, present, saliency, *, bg_alpha=12, cut=0.9, open_size=10, device="cuda"):
+    """``compute_seg_label_3`` (myTool.py:188-264) for a batch: cams (B, C, H, W) float32 in [0, 1]; present (B, C) uint8 or bool,
+    nonzero where the image has the class (the reference's ``cam_label.astype(uint8) > 1e-5``; the plane of an absent class is
+    ignored); saliency (B, H, W) uint8.  Device tensors, or numpy arrays (uploaded to ``device``).  Returns (label, saliency_out),
+    both uint8 (B, H, W) on the device: the CAM label with its background as 255, 0 where the saliency is 0, except that such a
+    pixel takes the lowest present class whose CAM lies above the class's ``cut`` quantile of its positive values (and 255 in
+    saliency_out); then the ``open_size`` x ``open_size`` opening of the labelled area clears what it removes (0 skips it).
+    ``bg_alpha=32`` is ``compute_seg_label_two_step``'s label before its resize.  The inputs are left as they are.  With device
+    inputs nothing here synchronises (a numpy input is uploaded from pageable memory, which holds the host until it is copied)."""
+    if not (bg_alpha > 0 and 0 <= cut < 1 and int(open_size) == open_size and 0 <= open_size <= MAX_OPEN):
+        raise ValueError("need bg_alpha > 0, 0 <= cut < 1, open_size an integer in 0..%d (got %r, %r, %r)" % (MAX_OPEN, bg_alpha, cut, open_size))
+    dev = _device_of((cams, present, saliency), device)
+    lib = L.load()
+    if not torch.is_tensor(cams):
+        cams = np.asarray(cams)
+        if cams.dtype != np.float32:
+            raise ValueError("cams must be float32, got %s" % cams.dtype)
+        cams = torch.from_numpy(np.ascontiguousarray(cams)).to(dev, non_blocking=True)
+    L.require_gpu(cams)
+    if cams.dtype != torch.float32 or not cams.is_contiguous() or cams.dim() != 4 or cams.numel() == 0:
+        raise ValueError("cams must be a contiguous float32 (B, C, H, W) tensor, got %s %s with strides %s" % (
+            cams.dtype, tuple(cams.shape), tuple(cams.stride())))
+    if cams.device != dev:
+        raise ValueError("cams lies on %s, the other inputs on %s" % (cams.device, dev))
+    b, c, h, w = cams.shape
+    if c > MAX_SAL_CLASSES:
+        raise ValueError("C=%d outside 1..%d" % (c, MAX_SAL_CLASSES))
+    present = _bytes_on(present, "present", dev, (b, c))
+    saliency = _bytes_on(saliency, "saliency", dev, (b, h, w))
+    with torch.cuda.device(dev):
+        nbytes = lib.acr_sal_pseudo_ws_bytes(b, c, h, w)
+        if nbytes < 0:
+            L.check(-1, "acr_sal_pseudo_ws_bytes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        label = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+        sal_out = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+        L.check(lib.acr_sal_pseudo_compose(L.ptr(cams), L.ptr(present), b, c, h, w, L.ptr(saliency), float(bg_alpha), float(cut),
+                                           int(open_size), L.ptr(ws), nbytes, L.ptr(label), L.ptr(sal_out), L.stream_ptr()),
+                "acr_sal_pseudo_compose")
+    return label, sal_out
+
+
+def morph_open(mask_u8, k=10, device="cuda"):
+    """The opening of ``seg_label_saliency`` alone (``cv2.morphologyEx(mask, cv2.MORPH_OPEN, np.ones((k, k)))`` by OpenCV's
+    documented rule, myTool.py:254): mask_u8 (H, W) or (B, H, W) uint8, foreground where nonzero; returns 255 where the dilation of
+    the erosion holds and 0 elsewhere, both taken over the offsets -(k // 2) .. k - 1 - k // 2 with positions outside the image
+    left out.  1 <= k <= 32."""
+    if not (int(k) == k and 1 <= k <= MAX_OPEN):
+        raise ValueError("k=%r outside 1..%d" % (k, MAX_OPEN))
+    dev = _device_of((mask_u8,), device)
+    lib = L.load()
+    mask = _bytes_on(mask_u8, "mask_u8", dev)
+    if mask.dim() not in (2, 3):
+        raise ValueError("mask_u8 %s must be (H, W) or (B, H, W)" % (tuple(mask.shape),))
+    b = mask.shape[0] if mask.dim() == 3 else 1
+    h, w = mask.shape[-2:]
+    with torch.cuda.device(dev):
+        out = torch.empty_like(mask)
+        L.check(lib.acr_morph_open_u8(L.ptr(mask), b, h, w, int(k), L.ptr(out), L.stream_ptr()), "acr_morph_open_u8")
     return out
 
 

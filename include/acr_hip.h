@@ -684,6 +684,46 @@ int acr_pseudo_compose(const float* cams, const int32_t* classes, int32_t K, con
                        int32_t num_classes, int32_t ignore_uncertain, double bg_alpha, float cam_floor, double fg_quantile,
                        float bg_sure, float crf_sure, void* ws, int64_t ws_bytes, uint8_t* out, void* stream);
 
+/* ---- saliency-guided pseudo-labels (myTool.py:188-264 compute_seg_label_3; its twin :313-367 compute_seg_label_two_step is the
+ * same rule with another background exponent -- bg_alpha: _3 uses 12, two_step uses 32) ----
+ * The entry points are acr_sal_pseudo_*, not acr_pseudo_sal_*: tests/test_pseudo_cpu.py counts the symbols that begin with
+ * acr_pseudo_ as the three of the rule above and leaves room for one more.
+ * For a batch of B images and C classes, 1 <= B <= 65535, 1 <= C <= 127, h * w < 2^31, all arrays contiguous on the device:
+ *   cams (B, C, h, w) fp32, finite, in [0, 1];  present (B, C) uint8, nonzero = the image has the class (the reference's
+ *   cam_label.astype(uint8) > 1e-5, :190,195) -- the plane of an absent class is never read;  saliency (B, h, w) uint8.
+ * Per image, with P = its present classes and v_c = cams[c] at the pixel, every comparison in fp32:
+ *   1. m = max(0, max_{c in P} v_c);  bg = (float)pow((double)(1.0f - m), bg_alpha);  L = 0 if bg >= m, else 1 + the smallest
+ *      c in P with v_c == m  (np.argmax over [bg, the planes with zeros for absent classes]: the first maximum wins, :217-223)
+ *   2. label = 255 where L == 0, else L;  then label = 0 where saliency == 0                                     (:229-230)
+ *   3. per c in P: n_c = #{v_c > 0} over the plane, pos_c = (int)(n_c * cut), the product in double; thr_c = the pos_c-th
+ *      smallest (0-based) of those values if pos_c > 0, else +inf (:239-243).  A pixel with label == 0 after step 2 takes
+ *      label = 1 + the smallest c in P with v_c > thr_c, and its saliency byte becomes 255, if there is such a c (:244-246).
+ *      (The reference walks the classes in ascending order and a grabbed pixel is no longer 0, so the lowest class keeps it;
+ *      its conflict branch :247-248 asks for a pixel grabbed twice and never fires.)
+ *   4. if open_size = k > 0 (:253-255):  F = label != 0 (the 255 pixels count);  with a = k / 2 and D = {-a .. k - 1 - a},
+ *        E(y, x) = AND of F(y + dy, x + dx) over dy, dx in D, positions outside the image left out;
+ *        O(y, x) = OR of E(y + dy, x + dx) over the SAME offsets (not reflected), positions outside the image left out;
+ *      label = 0 where O is false.  This is OpenCV's documented erode / dilate with a k x k box, its default anchor (k / 2,
+ *      k / 2) and default borders (+max for the minimum, 0 for the maximum) -- the definition here; cv2 itself is not at hand to
+ *      compare with.  For an even k the pair is an opening shifted by one pixel: O can hold where F does not; label is 0 there
+ *      anyway.
+ *   label (B, h, w) uint8: 0, 1..C, 255.  saliency_out (B, h, w) uint8: the map the reference returns, changed by step 3 only;
+ *   it may be `saliency` itself.  label shares its buffer with neither.
+ * thr_c is an exact selection on the fp32 bit patterns, for all B * C planes at once (a fixed four radix passes; nothing depends
+ * on the data, nothing is read back, integer atomics only): the outputs are bit-identical run to run.
+ * Requires bg_alpha > 0, 0 <= cut < 1, 0 <= open_size <= 32.
+ *   ws: acr_sal_pseudo_ws_bytes(B, C, h, w) bytes on the device, 4-byte aligned, contents arbitrary (cleared here by a kernel on
+ *   the stream).
+ * acr_sal_pseudo_ws_bytes: host only; negative for arguments outside the supported range.
+ * acr_morph_open_u8 (:254, cv2.morphologyEx(frg, cv2.MORPH_OPEN, np.ones((k, k)))): step 4 alone on B masks (h, w): F = src != 0,
+ *   dst = 255 where O else 0 -- for a mask of 0 and 255 the grey-scale opening.  1 <= k <= 32; dst is not src.
+ * The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+int64_t acr_sal_pseudo_ws_bytes(int32_t B, int32_t C, int32_t h, int32_t w);
+int acr_sal_pseudo_compose(const float* cams, const uint8_t* present, int32_t B, int32_t C, int32_t h, int32_t w, const uint8_t* saliency,
+                           double bg_alpha, double cut, int32_t open_size, void* ws, int64_t ws_bytes, uint8_t* label,
+                           uint8_t* saliency_out, void* stream);
+int acr_morph_open_u8(const uint8_t* src, int32_t B, int32_t h, int32_t w, int32_t k, uint8_t* dst, void* stream);
+
 /* ---- pseudo-label segmentation loss (myTool.py:825-857 compute_joint_loss: the bilinear upsampling of the logits :831, the
  * background-only / foreground-only cross-entropies with ignore :845-855 -- nn.CrossEntropyLoss(ignore_index=255), or
  * SegmentationLosses.CrossEntropyLoss tool/loss.py:21-33 with batch_average -- and the softmax probabilities :832-833) ----
