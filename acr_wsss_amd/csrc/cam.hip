@@ -2,7 +2,7 @@
 // torch-semantics bilinear resize with label mask / h-flip / accumulate fused (infer_cam.py:156-162,
 // 186-196, 201, 208), and the affinity refinement patch_aff @ cam (infer_cam.py:164-165, 183-184).
 // All small and HBM/L2-bound; one wave per output row, lanes along the contiguous axis.
-#include "acr_common.h"
+#include "acr_resample.h"
 
 // out[n][c] = relu(x[n,:] . w[c,:] + bias[c]); one wave per patch n, x row kept in registers.
 template <typename T>
@@ -17,17 +17,16 @@ __global__ __launch_bounds__(256) void patch_cam_kernel(const T* __restrict__ x,
         const T* wr = w + (int64_t)c * D;
         float acc = 0.f;
         for (int d = lane; d < D; d += 64) acc = fmaf(acr_load1<T>(xr + d), acr_load1<T>(wr + d), acc);
+        // acr_wave_sum (acr_reduce.h), spelled in place here and below: the call compiles to another schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
         if (lane == 0) out[(int64_t)n * C + c] = fmaxf(acc + acr_load1<T>(bias + c), 0.f);
     }
 }
 
-// torch upsample_bilinear2d source index (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index)
+// torch upsample_bilinear2d in either mode: the two source-index rules and the interpolation of acr_resample.h
 __device__ __forceinline__ float src_index(float scale, int dst, bool align_corners) {
-    if (align_corners) return scale * (float)dst;
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;
-    return s < 0.f ? 0.f : s;
+    return align_corners ? acr_src_corners(scale, dst) : acr_src_half_pixel(scale, dst);
 }
 
 __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ src, int64_t src_sc, int64_t src_sp,
@@ -47,7 +46,7 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__
         const float* s = src + (int64_t)c * src_sc;
         const float v00 = s[((int64_t)y0 * iw + x0) * src_sp], v01 = s[((int64_t)y0 * iw + x1) * src_sp];
         const float v10 = s[((int64_t)y1 * iw + x0) * src_sp], v11 = s[((int64_t)y1 * iw + x1) * src_sp];
-        float val = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+        float val = acr_bilerp(hy, ly, hx, lx, v00, v01, v10, v11);
         if (chan_mul) val *= chan_mul[c];
         const int xo = hflip ? (ow - 1 - x) : x;
         float* d = dst + ((int64_t)c * oh + y) * ow + xo;

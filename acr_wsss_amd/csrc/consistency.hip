@@ -52,6 +52,7 @@ __global__ __launch_bounds__(CONS_THREADS) void cons_fwd_kernel(
         for (int c = lane; c < N; c += 64) acc += fabsf(r1[c] - r2[flip_index(c, p, inv_p)]);
         if (i == 0) cls += acc; else aff += acc;
     }
+    // acr_wave_sum (acr_reduce.h) for two values at once, kept in place: two calls compile to other code than this interleaving
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         cls += __shfl_xor(cls, off);
@@ -161,6 +162,7 @@ __global__ __launch_bounds__(CONS_THREADS) void cons_fwd_vec_kernel(
         }
         if (i == 0) cls += acc; else aff += acc;
     }
+    // acr_wave_sum (acr_reduce.h) for two values at once, kept in place: two calls compile to other code than this interleaving
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         cls += __shfl_xor(cls, off);

@@ -17,7 +17,8 @@
 // Upsampling: forward one thread per pair of output pixels (8-byte stores: an output row has 2 W floats); backward a GATHER per
 // input pixel over the exact range of output rows / columns whose first tap is i - 1 or i, found with the forward's own fp32
 // source-index function, summed in ascending order in double.
-#include "acr_common.h"
+#include "acr_reduce.h"
+#include "acr_resample.h"
 
 #define BN_MAX_SLABS 64
 
@@ -63,13 +64,10 @@ __device__ __forceinline__ void bn_block_sum(double& a, double& b) {
     const int tid = threadIdx.x;
     rd[tid] = a;
     rd[256 + tid] = b;
-    for (int off = 128; off > 0; off >>= 1) {
-        __syncthreads();
-        if (tid < off) {
-            rd[tid] += rd[tid + off];
-            rd[256 + tid] += rd[256 + tid + off];
-        }
-    }
+    acr_tree_sum256(tid, [&](int i, int j) {
+        rd[i] += rd[j];
+        rd[256 + i] += rd[256 + j];
+    });
     a = rd[0];
     b = rd[256];
 }
@@ -293,7 +291,7 @@ struct up_tap {
 
 __device__ __forceinline__ up_tap up_tap_of(float scale, int dst, int n_in) {
     up_tap t;
-    const float src = scale * (float)dst;
+    const float src = acr_src_corners(scale, dst);
     int i0 = (int)src;
     i0 = i0 < n_in - 1 ? i0 : n_in - 1;
     float l = src - (float)i0;
@@ -306,8 +304,7 @@ __device__ __forceinline__ up_tap up_tap_of(float scale, int dst, int n_in) {
 }
 
 __device__ __forceinline__ float up_interp(const float* __restrict__ p, int W, const up_tap& ty, const up_tap& tx) {
-    return ty.l0 * (tx.l0 * p[ty.i0 * W + tx.i0] + tx.l1 * p[ty.i0 * W + tx.i1]) +
-           ty.l1 * (tx.l0 * p[ty.i1 * W + tx.i0] + tx.l1 * p[ty.i1 * W + tx.i1]);
+    return acr_bilerp(ty.l0, ty.l1, tx.l0, tx.l1, p[ty.i0 * W + tx.i0], p[ty.i0 * W + tx.i1], p[ty.i1 * W + tx.i0], p[ty.i1 * W + tx.i1]);
 }
 
 // one thread per pair of output pixels (Y, 2 xp), (Y, 2 xp + 1)
@@ -328,16 +325,10 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const float* __rest
     }
 }
 
-// the smallest destination index in [0, n_out] whose first tap is >= t; the source index is monotone in the destination
+// the gather range of acr_resample.h for the corners rule: the estimate inverts it
 __device__ __forceinline__ int up_first_dst(int t, int n_out, int n_in, float scale, float inv) {
-    if (t <= 0) return 0;
-    if (t > n_in - 1) return n_out;
-    float e = (float)t * inv;
-    e = e < 0.f ? 0.f : (e > (float)n_out ? (float)n_out : e);
-    int d = (int)e;
-    while (d > 0 && up_tap_of(scale, d - 1, n_in).i0 >= t) --d;
-    while (d < n_out && up_tap_of(scale, d, n_in).i0 < t) ++d;
-    return d;
+    return acr_first_dst(
+        t, n_out, n_in, [&](int tap) { return (float)tap * inv; }, [&](int d) { return up_tap_of(scale, d, n_in).i0; });
 }
 
 // one thread per input pixel, lanes along x

@@ -11,26 +11,12 @@
 // d(gamma), d(beta): per-(sample, channel) partials -- every wave reduces its lanes per channel with a shuffle butterfly
 // (a wave's 64 consecutive vectors span one or two channels) into its own LDS row, the rows are summed in wave order and the
 // caller sums over samples in a fixed order: no atomics, bit-reproducible run to run.
-#include "acr_common.h"
+#include "acr_reduce.h"
 
 typedef __bf16 bf16_t;
 #define GN_MAXV 13
 #define GN_GROUPS 32
 enum { GN_ACT_NONE = 0, GN_ACT_RELU = 1, GN_ACT_ADD_RELU = 2 };
-
-template <int NT>
-__device__ __forceinline__ float gn_block_sum(float v, float* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();                                        // sh may still be read from a previous reduction
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) t += sh[w];           // same fixed order in every thread
-    return t;
-}
 
 template <int NT, int ACT>
 __global__ __launch_bounds__(NT) void gn_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ res,
@@ -54,7 +40,7 @@ __global__ __launch_bounds__(NT) void gn_fwd_kernel(const bf16_t* __restrict__ x
             for (int e = 0; e < 8; ++e) sum += (float)xv[i][e];
         }
     }
-    const float mean = gn_block_sum<NT>(sum, sh) * inv_n;
+    const float mean = acr_block_sum<NT>(sum, sh) * inv_n;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < GN_MAXV; ++i) {
@@ -63,7 +49,7 @@ __global__ __launch_bounds__(NT) void gn_fwd_kernel(const bf16_t* __restrict__ x
             for (int e = 0; e < 8; ++e) { const float d = (float)xv[i][e] - mean; ss = fmaf(d, d, ss); }
         }
     }
-    const float rstd = rsqrtf(gn_block_sum<NT>(ss, sh) * inv_n + eps);
+    const float rstd = rsqrtf(acr_block_sum<NT>(ss, sh) * inv_n + eps);
 #pragma unroll
     for (int i = 0; i < GN_MAXV; ++i) {
         const int v = tid + i * NT;
@@ -149,14 +135,15 @@ __global__ __launch_bounds__(NT) void gn_bwd_kernel(const bf16_t* __restrict__ d
             const int c = __shfl(cl, __ffsll((long long)rem) - 1);
             const bool mine = cl == c;
             float sa = mine ? dgl : 0.f, sb = mine ? dbl : 0.f;
+            // acr_wave_sum (acr_reduce.h) for two values at once, kept in place: two calls compile to other code than this interleaving
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) { sa += __shfl_xor(sa, off); sb += __shfl_xor(sb, off); }
             if (lane == 0) { dgw[wave][c] += sa; dbw[wave][c] += sb; }
             rem &= ~__ballot(mine);
         }
     }
-    const float c1 = gn_block_sum<NT>(s1, sh) * inv_n;
-    const float c2 = gn_block_sum<NT>(s2, sh) * inv_n;
+    const float c1 = acr_block_sum<NT>(s1, sh) * inv_n;
+    const float c2 = acr_block_sum<NT>(s2, sh) * inv_n;
 #pragma unroll
     for (int i = 0; i < GN_MAXV; ++i) {
         const int v = tid + i * NT;
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(NT) void gn_bwd_kernel(const bf16_t* __restrict__ d
             *reinterpret_cast<bf16x8*>(dx + base + (int64_t)v * 8) = o;
         }
     }
-    if (tid < cg) {                                          // gn_block_sum's barriers ordered the waves' LDS rows
+    if (tid < cg) {                                          // acr_block_sum's barriers ordered the waves' LDS rows
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int w = 0; w < NT / 64; ++w) { a += dgw[w][tid]; b += dbw[w][tid]; }

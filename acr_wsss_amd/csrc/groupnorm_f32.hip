@@ -12,7 +12,7 @@
 //             (stock: threshold-backward, internal-gradients, elementwise backward, gamma/beta kernels, the add's backward)
 // Deterministic: every sum is a fixed-order block reduction (no atomics); d(gamma), d(beta) per (sample, channel) are summed
 // over samples in order by a second kernel.  HW must be a multiple of 4 (16-byte vectors inside a channel).
-#include "acr_common.h"
+#include "acr_reduce.h"
 
 #define GNF_GROUPS 32
 // Cache policy of the second (last) pass: nontemporal loads and stores.  The activations are 100-400 MB per tensor -- nothing
@@ -23,20 +23,6 @@
 #define GNF_ST(p, v) __builtin_nontemporal_store(v, &(p))
 enum { GNF_NONE = 0, GNF_RELU = 1, GNF_ADD_RELU = 2 };
 
-template <int NT>
-__device__ __forceinline__ float gnf_block_sum(float v, float* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();                                        // sh may still be read from a previous reduction
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) t += sh[w];           // same fixed order in every thread
-    return t;
-}
-
 // Work decomposition inside a workgroup (round 5).  The first version walked a (sample, group) with all NT threads in lockstep: ONE
 // 16-byte load in flight per thread (`s_waitcnt vmcnt(0)` in every iteration, found in the ISA), the channel of every vector by an
 // integer division, and -- in the backward -- two block reductions (four barriers) per CHANNEL: 3.0 TB/s, half of what the HBM
@@ -45,11 +31,6 @@ __device__ __forceinline__ float gnf_block_sum(float v, float* sh) {
 // wave-uniform scalars, and the per-unit sums meet in LDS once per pass, where they are added in unit order (deterministic).
 #define GNF_MAXU 64                      // units per (sample, group): max(channels per group, waves) <= 64
 struct GnfUnits { int S, segv, units; };                    // segments per channel, vectors per segment, cg * S
-__device__ __forceinline__ float gnf_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 // body(v, a) for every vector v of [v0, v1) of this lane (stride 64), four loads in flight; LD = how the vectors are loaded
 #define GNF_FOR4(xv, v0, v1, lane, LDM, BODY)                                                     \
     {                                                                                              \
@@ -98,8 +79,8 @@ __global__ __launch_bounds__(NT) void gnf_fwd_kernel(const float* __restrict__ x
         GNF_FOR4(xv, v0, v1, lane, GNF_LD1, GNF_B1)
 #undef GNF_B1
     }
-    s1 = gnf_wave_sum(s1);
-    s2 = gnf_wave_sum(s2);
+    s1 = acr_wave_sum(s1);
+    s2 = acr_wave_sum(s2);
     if (lane == 0) { sh[wave] = s1; sh[NW + wave] = s2; }
     __syncthreads();
     float t1 = 0.f, t2 = 0.f;
@@ -212,8 +193,8 @@ __global__ __launch_bounds__(NT) void gnf_bwd_kernel(const float* __restrict__ d
             if (ACT == GNF_ADD_RELU) r0 = ldr(v);
             acc(a0, y0, r0);
         }
-        db = gnf_wave_sum(db);
-        dg = gnf_wave_sum(dg);
+        db = acr_wave_sum(db);
+        dg = acr_wave_sum(dg);
         if (lane == 0) { shu[2 * u] = db; shu[2 * u + 1] = dg; }
     }
     __syncthreads();
@@ -354,8 +335,8 @@ __global__ __launch_bounds__(NT, 4) void gnf_fwd_reg_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) { const float d = xr[i][e] - x0; s1 += d; s2 = fmaf(d, d, s2); }
         }
     }
-    s1 = gnf_wave_sum(s1);
-    s2 = gnf_wave_sum(s2);
+    s1 = acr_wave_sum(s1);
+    s2 = acr_wave_sum(s2);
     if (lane == 0) { sh[wave] = s1; sh[NW + wave] = s2; }
     __syncthreads();
     float t1 = 0.f, t2 = 0.f;
@@ -455,8 +436,8 @@ __global__ __launch_bounds__(NT, 4) void gnf_bwd_reg_kernel(const float* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) { db += gr[i][e]; dg = fmaf(gr[i][e], (xr[i][e] - mean) * rstd, dg); }
         }
-        db = gnf_wave_sum(db);
-        dg = gnf_wave_sum(dg);
+        db = acr_wave_sum(db);
+        dg = acr_wave_sum(dg);
         if (lane == 0) { shp[(wave * RV + i) * 2] = db; shp[(wave * RV + i) * 2 + 1] = dg; }
     }
     __syncthreads();
@@ -534,8 +515,8 @@ __global__ __launch_bounds__(256) void gnf_part_kernel(const float* __restrict__
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const float d = a[e] - x0; s1 += d; s2 = fmaf(d, d, s2); }
     }
-    s1 = gnf_block_sum<256>(s1, sh);
-    s2 = gnf_block_sum<256>(s2, sh);
+    s1 = acr_block_sum<256>(s1, sh);
+    s2 = acr_block_sum<256>(s2, sh);
     if (threadIdx.x == 0) { parts[2 * blockIdx.x] = s1; parts[2 * blockIdx.x + 1] = s2; }
 }
 template <int ACT>

@@ -5,17 +5,12 @@
 //   backward: ONE pass reads x and dy and writes dx while the wave accumulates its rows' contributions to dgamma/dbeta
 //             in registers; per-wave partials are summed in wave order by a second kernel (deterministic).  The stock
 //             path reads x and dy twice (grad-input kernel + two gamma/beta kernels).
+#include "acr_reduce.h"
 #include "acr_split.h"
 
 typedef __bf16 bf16_t;
 #define LN_MAXV 4                     // up to 4 vectors of 4 elements per lane -> C <= 1024
 #define LN_WAVES 4
-
-__device__ __forceinline__ float ln_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 template <int NV, typename T>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ gamma,
@@ -39,13 +34,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
             xv[i] = acr_load4<T>(xr + (i * 64 + lane) * 4);
             s += xv[i][0] + xv[i][1] + xv[i][2] + xv[i][3];
         }
-        const float mean = ln_wave_sum(s) * inv_c;
+        const float mean = acr_wave_sum(s) * inv_c;
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float d = xv[i][e] - mean; ss = fmaf(d, d, ss); }
-        const float rstd = rsqrtf(ln_wave_sum(ss) * inv_c + eps);
+        const float rstd = rsqrtf(acr_wave_sum(ss) * inv_c + eps);
         T* yr = y + (int64_t)row * C;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -91,7 +86,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                 db[i][e] += dv[e];
             }
         }
-        const float c1 = ln_wave_sum(s1) * inv_c, c2 = ln_wave_sum(s2) * inv_c;
+        const float c1 = acr_wave_sum(s1) * inv_c, c2 = acr_wave_sum(s2) * inv_c;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             f32x4 o;

@@ -25,6 +25,7 @@ __global__ __launch_bounds__(256) void mlsm_fwd_kernel(const float* __restrict__
     }
     sh[threadIdx.x] = acc;
     __syncthreads();
+    // acr_tree_sum256's order with the barrier after the add instead of before it: kept in place, this kernel is in the training step
     for (int off = 128; off > 0; off >>= 1) {
         if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
         __syncthreads();

@@ -20,6 +20,30 @@ struct PreImg {            // mirrors acr_pre_image (include/acr_hip.h)
     int32_t cont_top, cont_left, img_top, img_left, ch, cw;   // RandomCrop boxes (myTool.py:923-955)
 };
 
+// The normalised image value at pixel (ry, rx) of the resized image: cv2.resize's float INTER_LINEAR sample, then (v / 255 - mean) /
+// std.  Not the fp32 rule of acr_resample.h: the sample position (d + 0.5) * in/out - 0.5 = ((2d + 1) * in - out) / (2 * out) is
+// taken in exact integer arithmetic, because the reference computes it in float64, and an fp32 product loses ~3e-5 of a pixel at
+// x ~ 500, i.e. 2e-4 of the output.  Both kernels below take their image from here, so their images agree bit for bit.
+struct PreRgb { float r0, r1, r2; };
+__device__ __forceinline__ PreRgb pre_sample(const uint8_t* __restrict__ p, const PreImg& im, int ry, int rx, float m0, float m1,
+                                             float m2, float s0, float s1, float s2) {
+    const int ny = (2 * ry + 1) * im.h - im.rh, dy = 2 * im.rh;
+    const int nx = (2 * rx + 1) * im.w - im.rw, dx = 2 * im.rw;
+    const int y0 = ny < 0 ? 0 : min(ny / dy, im.h - 1), x0 = nx < 0 ? 0 : min(nx / dx, im.w - 1);
+    const int y1 = min(y0 + 1, im.h - 1), x1 = min(x0 + 1, im.w - 1);
+    const float ly = (ny < 0 || y0 >= im.h - 1) ? 0.f : (float)(ny - y0 * dy) / (float)dy;
+    const float lx = (nx < 0 || x0 >= im.w - 1) ? 0.f : (float)(nx - x0 * dx) / (float)dx;
+    const uint8_t* p00 = p + ((int64_t)y0 * im.w + x0) * 3;
+    const uint8_t* p01 = p + ((int64_t)y0 * im.w + x1) * 3;
+    const uint8_t* p10 = p + ((int64_t)y1 * im.w + x0) * 3;
+    const uint8_t* p11 = p + ((int64_t)y1 * im.w + x1) * 3;
+    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+    const float v0 = w00 * p00[0] + w01 * p01[0] + w10 * p10[0] + w11 * p11[0];
+    const float v1 = w00 * p00[1] + w01 * p01[1] + w10 * p10[1] + w11 * p11[1];
+    const float v2 = w00 * p00[2] + w01 * p01[2] + w10 * p10[2] + w11 * p11[2];
+    return {(v0 / 255.f - m0) / s0, (v1 / 255.f - m1) / s1, (v2 / 255.f - m2) / s2};
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ packed, const PreImg* __restrict__ tab,
                                                          T* __restrict__ out, int S, float m0, float m1, float m2, float s0,
@@ -35,26 +59,10 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
         const int ry = im.img_top + cy;                       // pixel of the resized (and flipped) image
         int rx = im.img_left + cx;
         if (im.flip) rx = im.rw - 1 - rx;
-        // sample position (d + 0.5) * in/out - 0.5 = ((2d + 1) * in - out) / (2 * out), in exact integer arithmetic: the
-        // reference computes it in float64, and an fp32 product loses ~3e-5 of a pixel at x ~ 500, i.e. 2e-4 of the output
-        const int ny = (2 * ry + 1) * im.h - im.rh, dy = 2 * im.rh;
-        const int nx = (2 * rx + 1) * im.w - im.rw, dx = 2 * im.rw;
-        const int y0 = ny < 0 ? 0 : min(ny / dy, im.h - 1), x0 = nx < 0 ? 0 : min(nx / dx, im.w - 1);
-        const int y1 = min(y0 + 1, im.h - 1), x1 = min(x0 + 1, im.w - 1);
-        const float ly = (ny < 0 || y0 >= im.h - 1) ? 0.f : (float)(ny - y0 * dy) / (float)dy;
-        const float lx = (nx < 0 || x0 >= im.w - 1) ? 0.f : (float)(nx - x0 * dx) / (float)dx;
-        const uint8_t* p = packed + im.offset;
-        const uint8_t* p00 = p + ((int64_t)y0 * im.w + x0) * 3;
-        const uint8_t* p01 = p + ((int64_t)y0 * im.w + x1) * 3;
-        const uint8_t* p10 = p + ((int64_t)y1 * im.w + x0) * 3;
-        const uint8_t* p11 = p + ((int64_t)y1 * im.w + x1) * 3;
-        const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-        const float v0 = w00 * p00[0] + w01 * p01[0] + w10 * p10[0] + w11 * p11[0];
-        const float v1 = w00 * p00[1] + w01 * p01[1] + w10 * p10[1] + w11 * p11[1];
-        const float v2 = w00 * p00[2] + w01 * p01[2] + w10 * p10[2] + w11 * p11[2];
-        r0 = (v0 / 255.f - m0) / s0;
-        r1 = (v1 / 255.f - m1) / s1;
-        r2 = (v2 / 255.f - m2) / s2;
+        const PreRgb q = pre_sample(packed + im.offset, im, ry, rx, m0, m1, m2, s0, s1, s2);
+        r0 = q.r0;
+        r1 = q.r1;
+        r2 = q.r2;
     }
     T* o = out + (int64_t)b * 3 * S * S + pix;
     acr_store1<T>(o, r0);
@@ -84,8 +92,8 @@ extern "C" int acr_preprocess_batch(const void* packed_u8, const void* table, in
 // ---- segmentation-training loaders: myTool.py:1257-1310 get_data_from_chunk_v4 (image + target map) and :1202-1253
 // get_data_from_chunk_v3 (image + saliency map) on RandomResizeLong2 (:1010-1023), flip2 (:901-905), RandomCrop2 (:957-993) ----
 // One launch writes the four outputs of a chunk from the same geometry record (include/acr_hip.h states the rule in full).  The
-// image value is the arithmetic of preprocess_kernel above, statement for statement (the build has -ffp-contract=off), so
-// `images` equals acr_preprocess_batch's output bit for bit.  A bandwidth-bound gather, ~20 bytes written per output pixel: with
+// image value is pre_sample's, as in preprocess_kernel above (the build has -ffp-contract=off), so `images` equals
+// acr_preprocess_batch's output bit for bit.  A bandwidth-bound gather, ~20 bytes written per output pixel: with
 // S % 4 == 0 a thread owns 4 consecutive x of one row and stores 16 bytes (fp32 planes, croppings), 8 (bf16) or 4 (the uint8
 // planes) at a time; any other S takes one pixel per thread.  No atomics, no LDS.
 __device__ __forceinline__ uint8_t seg_ori_byte(float x, float sd, float mn) {
@@ -122,23 +130,10 @@ __global__ __launch_bounds__(256) void preprocess_seg_kernel(const uint8_t* __re
         if (inside) {
             int rx = im.img_left + cx;
             if (im.flip) rx = im.rw - 1 - rx;
-            const int ny = (2 * ry + 1) * im.h - im.rh, dy = 2 * im.rh;
-            const int nx = (2 * rx + 1) * im.w - im.rw, dx = 2 * im.rw;
-            const int y0 = ny < 0 ? 0 : min(ny / dy, im.h - 1), x0 = nx < 0 ? 0 : min(nx / dx, im.w - 1);
-            const int y1 = min(y0 + 1, im.h - 1), x1 = min(x0 + 1, im.w - 1);
-            const float ly = (ny < 0 || y0 >= im.h - 1) ? 0.f : (float)(ny - y0 * dy) / (float)dy;
-            const float lx = (nx < 0 || x0 >= im.w - 1) ? 0.f : (float)(nx - x0 * dx) / (float)dx;
-            const uint8_t* p00 = p + ((int64_t)y0 * im.w + x0) * 3;
-            const uint8_t* p01 = p + ((int64_t)y0 * im.w + x1) * 3;
-            const uint8_t* p10 = p + ((int64_t)y1 * im.w + x0) * 3;
-            const uint8_t* p11 = p + ((int64_t)y1 * im.w + x1) * 3;
-            const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-            const float v0 = w00 * p00[0] + w01 * p01[0] + w10 * p10[0] + w11 * p11[0];
-            const float v1 = w00 * p00[1] + w01 * p01[1] + w10 * p10[1] + w11 * p11[1];
-            const float v2 = w00 * p00[2] + w01 * p01[2] + w10 * p10[2] + w11 * p11[2];
-            r0 = (v0 / 255.f - m0) / s0;
-            r1 = (v1 / 255.f - m1) / s1;
-            r2 = (v2 / 255.f - m2) / s2;
+            const PreRgb q = pre_sample(p, im, ry, rx, m0, m1, m2, s0, s1, s2);
+            r0 = q.r0;
+            r1 = q.r1;
+            r2 = q.r2;
             if (mp) {
                 const int mx = min((int)((int64_t)rx * im.w / im.rw), im.w - 1);
                 mval = mp[(int64_t)my * im.w + mx];

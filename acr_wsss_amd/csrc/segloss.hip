@@ -11,7 +11,8 @@
 // (b, k, y, x), walks the label-size pixels whose footprint touches it in ascending order, recomputes p_k from the two saved row
 // statistics (max, sum) and adds weight * d pred -- no scatter, no float atomics, bit-identical run to run.
 // Every sum over pixels runs in double in a fixed order (thread, then an LDS tree, then the blocks in a finish kernel).
-#include "acr_common.h"
+#include "acr_reduce.h"
+#include "acr_resample.h"
 
 #define SEGLOSS_MAX_K 128
 #define SEGLOSS_MAX_BLOCKS 256            // partial-sum workgroups per image (and of one energy dot)
@@ -23,45 +24,6 @@ struct segloss_part {                     // one workgroup's share of an image
     int64_t n_bg, n_fg;
 };
 
-// torch upsample_bilinear2d, align_corners=False (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index): the rule
-// acr_bilinear_resize states, in fp32
-__device__ __forceinline__ float segloss_src(float scale, int dst) {
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;
-    return s < 0.f ? 0.f : s;
-}
-
-struct segloss_taps {
-    int y0, y1, x0, x1;                   // the four source texels ...
-    int o00, o01, o10, o11;               // ... and their offsets into a (h, w) plane
-    float hy, ly, hx, lx;
-};
-
-__device__ __forceinline__ segloss_taps segloss_taps_of(int Y, int X, int h, int w, float sh, float sw) {
-    segloss_taps t;
-    const float fy = segloss_src(sh, Y), fx = segloss_src(sw, X);
-    int y0 = (int)fy, x0 = (int)fx;
-    y0 = y0 < h - 1 ? y0 : h - 1;         // fy < h always; the clamp keeps a rounding at the edge inside the plane
-    x0 = x0 < w - 1 ? x0 : w - 1;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    t.ly = fy - (float)y0;
-    t.lx = fx - (float)x0;
-    t.hy = 1.f - t.ly;
-    t.hx = 1.f - t.lx;
-    t.y0 = y0;
-    t.y1 = y1;
-    t.x0 = x0;
-    t.x1 = x1;
-    t.o00 = y0 * w + x0;
-    t.o01 = y0 * w + x1;
-    t.o10 = y1 * w + x0;
-    t.o11 = y1 * w + x1;
-    return t;
-}
-
-__device__ __forceinline__ float segloss_interp(const float* __restrict__ p, const segloss_taps& t) {
-    return t.hy * (t.hx * p[t.o00] + t.lx * p[t.o01]) + t.ly * (t.hx * p[t.o10] + t.lx * p[t.o11]);
-}
-
 // sum the four per-thread numbers over the workgroup in a fixed order; the result is valid in thread 0
 __device__ __forceinline__ void segloss_block_sum(void* smem, double& a, double& b, int& na, int& nb) {
     double* rd = reinterpret_cast<double*>(smem);
@@ -72,15 +34,12 @@ __device__ __forceinline__ void segloss_block_sum(void* smem, double& a, double&
     rd[256 + tid] = b;
     ri[tid] = na;
     ri[256 + tid] = nb;
-    for (int off = 128; off > 0; off >>= 1) {
-        __syncthreads();
-        if (tid < off) {
-            rd[tid] += rd[tid + off];
-            rd[256 + tid] += rd[256 + tid + off];
-            ri[tid] += ri[tid + off];
-            ri[256 + tid] += ri[256 + tid + off];
-        }
-    }
+    acr_tree_sum256(tid, [&](int i, int j) {
+        rd[i] += rd[j];
+        rd[256 + i] += rd[256 + j];
+        ri[i] += ri[j];
+        ri[256 + i] += ri[256 + j];
+    });
     a = rd[0];
     b = rd[256];
     na = ri[0];
@@ -101,11 +60,11 @@ __global__ __launch_bounds__(256) void segloss_fwd_kernel(const float* __restric
     double sum_bg = 0.0, sum_fg = 0.0;
     int n_bg = 0, n_fg = 0;
     for (int64_t pix = (int64_t)blk * 256 + threadIdx.x; pix < WH; pix += (int64_t)nblk * 256) {
-        const segloss_taps t = segloss_taps_of((int)(pix / H), (int)(pix % H), h, w, sh, sw);
+        const acr_taps t = acr_taps_of((int)(pix / H), (int)(pix % H), h, w, sh, sw);
         const int lab = label[(int64_t)b * WH + pix];
         float m = -INFINITY, xl = 0.f;
         for (int k = 0; k < K; ++k) {
-            const float v = segloss_interp(lg + (int64_t)k * hw, t);
+            const float v = acr_interp(lg + (int64_t)k * hw, t);
             col[k * 256] = v;
             m = fmaxf(m, v);
             xl = k == lab ? v : xl;
@@ -155,15 +114,12 @@ __global__ __launch_bounds__(256) void segloss_finish_kernel(const segloss_part*
             rd[tid] = rd[256 + tid] = 0.0;
             rn[tid] = rn[256 + tid] = 0;
         }
-        for (int off = 128; off > 0; off >>= 1) {
-            __syncthreads();
-            if (tid < off) {
-                rd[tid] += rd[tid + off];
-                rd[256 + tid] += rd[256 + tid + off];
-                rn[tid] += rn[tid + off];
-                rn[256 + tid] += rn[256 + tid + off];
-            }
-        }
+        acr_tree_sum256(tid, [&](int i, int j) {
+            rd[i] += rd[j];
+            rd[256 + i] += rd[256 + j];
+            rn[i] += rn[j];
+            rn[256 + i] += rn[256 + j];
+        });
         if (tid == 0) {
             sums[2 * b] = (float)rd[0];
             sums[2 * b + 1] = (float)rd[256];
@@ -203,16 +159,11 @@ __global__ __launch_bounds__(256) void segloss_pdot_kernel(const float* __restri
     }
 }
 
-// the smallest destination index in [0, n_out] whose first source tap (int)src is >= t; src is monotone in the destination
+// the gather range of acr_resample.h for the half-pixel rule: the estimate inverts it, the first tap is clamped like acr_taps_of's
 __device__ __forceinline__ int segloss_first_dst(int t, int n_out, int n_in, float scale, float inv) {
-    if (t <= 0) return 0;
-    if (t > n_in - 1) return n_out;                      // the first tap never passes n_in - 1
-    float e = ((float)t + 0.5f) * inv - 0.5f;
-    e = e < 0.f ? 0.f : (e > (float)n_out ? (float)n_out : e);
-    int d = (int)e;
-    while (d > 0 && min((int)segloss_src(scale, d - 1), n_in - 1) >= t) --d;
-    while (d < n_out && min((int)segloss_src(scale, d), n_in - 1) < t) ++d;
-    return d;
+    return acr_first_dst(
+        t, n_out, n_in, [&](int tap) { return ((float)tap + 0.5f) * inv - 0.5f; },
+        [&](int d) { return min((int)acr_src_half_pixel(scale, d), n_in - 1); });
 }
 
 // backward: one thread per low-resolution logit (b, k, y, x), lanes along x.  g (3): the gradients of celoss, bg, fg.
@@ -240,13 +191,13 @@ __global__ __launch_bounds__(256) void segloss_bwd_kernel(const float* __restric
         double acc = 0.0;
         for (int Y = Ya; Y < Yb; ++Y) {
             for (int X = Xa; X < Xb; ++X) {
-                const segloss_taps t = segloss_taps_of(Y, X, h, w, sh, sw);
+                const acr_taps t = acr_taps_of(Y, X, h, w, sh, sw);
                 const float wy = (t.y0 == y ? t.hy : 0.f) + (t.y1 == y ? t.ly : 0.f);
                 const float wx = (t.x0 == x ? t.hx : 0.f) + (t.x1 == x ? t.lx : 0.f);
                 const int64_t pix = (int64_t)Y * H + X;
                 const int lab = label[(int64_t)b * WH + pix];
                 const float2 ms = rowstat[(int64_t)b * WH + pix];
-                const float p = expf(segloss_interp(plane, t) - ms.x) / ms.y;
+                const float p = expf(acr_interp(plane, t) - ms.x) / ms.y;
                 float dpred = 0.f;
                 if (lab == 0)
                     dpred = c_bg * (p - (k == 0 ? 1.f : 0.f));
@@ -272,10 +223,7 @@ __global__ __launch_bounds__(256) void energy_dot_kernel(const float* __restrict
         if (grad) grad[i] = scale * a;
     }
     rd[tid] = acc;
-    for (int off = 128; off > 0; off >>= 1) {
-        __syncthreads();
-        if (tid < off) rd[tid] += rd[tid + off];
-    }
+    acr_tree_sum256(tid, [&](int i, int j) { rd[i] += rd[j]; });
     if (tid == 0) part[blockIdx.x] = rd[0];
 }
 
@@ -283,10 +231,7 @@ __global__ __launch_bounds__(256) void energy_finish_kernel(const double* __rest
     __shared__ double rd[256];
     const int tid = threadIdx.x;
     rd[tid] = tid < nblk ? part[tid] : 0.0;
-    for (int off = 128; off > 0; off >>= 1) {
-        __syncthreads();
-        if (tid < off) rd[tid] += rd[tid + off];
-    }
+    acr_tree_sum256(tid, [&](int i, int j) { rd[i] += rd[j]; });
     if (tid == 0) out[0] = (float)rd[0];
 }
 

@@ -11,48 +11,13 @@
 // segloss_fwd_kernel), so the maximum, the sum and the quotients read them without touching the source again; the exponentials
 // overwrite the column, so each is evaluated once.  No thread reads another thread's column: no barrier, no atomics, nothing
 // depends on the launch geometry -- bit-identical run to run.
-#include "acr_common.h"
+#include "acr_resample.h"
 
 #define SEGPRED_MAX_K 128
 #define SEGPRED_MAX_B 65535
 #define SEGPRED_UNROLL 8                  // planes whose texels are in flight together (K = 21: three batches)
 
 enum { SEGPRED_LABEL = 0, SEGPRED_PROBS = 1, SEGPRED_ACCUM = 2 };
-
-// torch upsample_bilinear2d, align_corners=False (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index): the rule
-// acr_bilinear_resize and acr_segloss_fwd state, in fp32
-__device__ __forceinline__ float segpred_src(float scale, int dst) {
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;
-    return s < 0.f ? 0.f : s;
-}
-
-struct segpred_taps {
-    int o00, o01, o10, o11;               // offsets of the four source texels into an (h, w) plane
-    float hy, ly, hx, lx;
-};
-
-__device__ __forceinline__ segpred_taps segpred_taps_of(int Y, int X, int h, int w, float sh, float sw, int hflip) {
-    segpred_taps t;
-    const float fy = segpred_src(sh, Y), fx = segpred_src(sw, X);
-    int y0 = (int)fy, x0 = (int)fx;
-    y0 = y0 < h - 1 ? y0 : h - 1;         // fy < h always; the clamp keeps a rounding at the edge inside the plane
-    x0 = x0 < w - 1 ? x0 : w - 1;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0);
-    int x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    t.ly = fy - (float)y0;
-    t.lx = fx - (float)x0;
-    t.hy = 1.f - t.ly;
-    t.hx = 1.f - t.lx;
-    if (hflip) {                          // the pass ran on the mirrored image: column x of the logits is column w - 1 - x of the scene
-        x0 = w - 1 - x0;
-        x1 = w - 1 - x1;
-    }
-    t.o00 = y0 * w + x0;
-    t.o01 = y0 * w + x1;
-    t.o10 = y1 * w + x0;
-    t.o11 = y1 * w + x1;
-    return t;
-}
 
 // grid = (ceil(H * W / 256), B); K * h * w and K * H * W are below 2^31, so offsets inside one image are int
 template <int MODE>
@@ -63,7 +28,8 @@ __global__ __launch_bounds__(256) void segpred_kernel(const float* __restrict__ 
     const int pix = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (pix >= HW) return;                               // no barrier below: a thread past the image simply leaves
     const int b = blockIdx.y;
-    const segpred_taps t = segpred_taps_of(pix / W, pix % W, h, w, sh, sw, hflip);
+    // the taps of acr_resample.h, which acr_segloss_fwd takes too (and acr_bilinear_resize's source index)
+    const acr_taps t = acr_taps_of<true>(pix / W, pix % W, h, w, sh, sw, hflip);
     const float* lg = logits + (int64_t)b * K * hw;
     float* col = segpred_smem + threadIdx.x;             // v_k, then exp(v_k - m), of this thread's pixel at col[k * 256]
     float m = -INFINITY;
@@ -90,7 +56,7 @@ __global__ __launch_bounds__(256) void segpred_kernel(const float* __restrict__ 
         }
 #pragma unroll
         for (int u = 0; u < SEGPRED_UNROLL; ++u)
-            if (k + u < K) take(k + u, t.hy * (t.hx * tex[u][0] + t.lx * tex[u][1]) + t.ly * (t.hx * tex[u][2] + t.lx * tex[u][3]));
+            if (k + u < K) take(k + u, acr_bilerp(t.hy, t.ly, t.hx, t.lx, tex[u][0], tex[u][1], tex[u][2], tex[u][3]));
     }
     if (MODE != SEGPRED_LABEL) {
         float s = 0.f;

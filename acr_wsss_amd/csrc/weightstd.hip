@@ -15,6 +15,7 @@ struct WStdDesc {
     int32_t cout, n, ch_start, pad;
 };
 
+// not acr_block_sum<256>: the same order, but without its leading `0.f +`, which would turn the -0 of an all -0 row into +0
 __device__ __forceinline__ float wstd_block_sum(float v, float* sh) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

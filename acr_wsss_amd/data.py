@@ -69,33 +69,62 @@ def random_crop_boxes(h, w, crop, rng):
     return cont_top, cont_left, img_top, img_left, ch, cw
 
 
-def preprocess_batch(images_uint8, records, S, device, dtype=torch.float32):
-    """Run acr_preprocess_batch: ``images_uint8`` = list of (h,w,3) uint8 RGB arrays, ``records`` = PRE_IMAGE array with
-    everything but ``offset`` filled in.  One pinned staging buffer, one H2D copy, one launch."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise L.AcrHipError("acr_wsss_amd.data runs on the GPU only (acr_preprocess_batch); there is no CPU path")
-    sizes = [int(a.shape[0]) * int(a.shape[1]) * 3 for a in images_uint8]
-    offs = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])       # 16-byte aligned images
-    stage = torch.empty(int(offs[-1]), dtype=torch.uint8).pin_memory()
-    sn = stage.numpy()
-    for a, o, s in zip(images_uint8, offs[:-1], sizes):
-        assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3, "decoded images must be (h, w, 3) uint8 RGB"
-        sn[o:o + s] = np.ascontiguousarray(a).reshape(-1)
-    records = records.copy()
-    records["offset"] = offs[:-1]
-    for rec, a in zip(records, images_uint8):               # the kernel trusts the table: validate it here
+def _check_images(who, images_uint8, records, S):
+    """Everything the preprocess kernels trust about the images and their geometry records, judged on the host before any device
+    is asked for: the kernels index the packed pixels by the table alone."""
+    if len(images_uint8) == 0 or len(records) != len(images_uint8):
+        raise ValueError("need one record per image (got %d images, %d records)" % (len(images_uint8), len(records)))
+    if not 0 < int(S) <= 32768:
+        raise ValueError("crop size %r outside 1..32768" % (S,))
+    for i, (a, rec) in enumerate(zip(images_uint8, records)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise ValueError("image %d must be a (h, w, 3) uint8 RGB array, got %s %s" % (i, getattr(a, "dtype", type(a)), getattr(a, "shape", "")))
         ok = (rec["h"] == a.shape[0] and rec["w"] == a.shape[1] and rec["rh"] > 0 and rec["rw"] > 0
               and 0 <= rec["cont_top"] and rec["cont_top"] + rec["ch"] <= S and 0 <= rec["cont_left"] and rec["cont_left"] + rec["cw"] <= S
               and 0 <= rec["img_top"] and rec["img_top"] + rec["ch"] <= rec["rh"] and 0 <= rec["img_left"]
-              and rec["img_left"] + rec["cw"] <= rec["rw"])
+              and rec["img_left"] + rec["cw"] <= rec["rw"] and rec["ch"] >= 0 and rec["cw"] >= 0 and rec["flip"] in (0, 1)
+              and 2 * int(rec["rh"]) * int(rec["h"]) < 2 ** 31 and 2 * int(rec["rw"]) * int(rec["w"]) < 2 ** 31)     # the kernel's int32 sample positions
         if not ok:
-            raise L.AcrHipError("acr_preprocess_batch: inconsistent geometry record %s for a %s image" % (rec, a.shape))
-    packed = stage.to(device, non_blocking=True)
-    raw = records.view(np.uint8).reshape(-1)
-    table_host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)    # pinned: a pageable source would make the
-    table_host.numpy()[:] = raw                                                # "asynchronous" copy drain the stream on the host
-    table = table_host.to(device, non_blocking=True)
+            raise L.AcrHipError("%s: inconsistent geometry record %s for a %s image" % (who, rec, a.shape))
+
+
+def _cuda_device(who, device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.AcrHipError("acr_wsss_amd.data runs on the GPU only (%s); there is no CPU path" % who)
+    return device
+
+
+def _upload_packed(arrays, device):
+    """The uint8 arrays back to back, each at a 16-byte aligned offset of ONE pinned staging buffer, and its one H2D copy.
+    Returns (offsets, staging buffer, device buffer); the staging buffer must outlive the asynchronous copy."""
+    sizes = [int(a.size) for a in arrays]
+    offs = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])
+    stage = torch.empty(int(offs[-1]), dtype=torch.uint8).pin_memory()
+    sn = stage.numpy()
+    for a, o, s in zip(arrays, offs[:-1], sizes):
+        sn[o:o + s] = np.ascontiguousarray(a).reshape(-1)
+    return offs[:-1], stage, stage.to(device, non_blocking=True)
+
+
+def _upload_table(records, offsets, device, extra=()):
+    """The record table with its ``offset`` column filled in and, right behind it, the int64 values ``extra``: one pinned buffer (a
+    pageable source would make the "asynchronous" copy drain the stream on the host), one copy."""
+    records = records.copy()
+    records["offset"] = offsets
+    raw = np.concatenate([records.view(np.uint8).reshape(-1), np.asarray(extra, dtype="<i8").view(np.uint8)])
+    table_host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)
+    table_host.numpy()[:] = raw
+    return table_host.to(device, non_blocking=True)
+
+
+def preprocess_batch(images_uint8, records, S, device, dtype=torch.float32):
+    """Run acr_preprocess_batch: ``images_uint8`` = list of (h,w,3) uint8 RGB arrays, ``records`` = PRE_IMAGE array with
+    everything but ``offset`` filled in.  One pinned staging buffer, one H2D copy, one launch."""
+    _check_images("acr_preprocess_batch", images_uint8, records, S)
+    device = _cuda_device("acr_preprocess_batch", device)
+    offs, stage, packed = _upload_packed(images_uint8, device)
+    table = _upload_table(records, offs, device)
     out = torch.empty((len(images_uint8), 3, S, S), dtype=dtype, device=device)
     mean = (ctypes.c_float * 3)(*MEAN)
     std = (ctypes.c_float * 3)(*STD)
@@ -151,27 +180,16 @@ def val_batch(images_uint8, crop_size, device="cuda", dtype=torch.float32):
 # ------------------------------------------------------------------------------------------------------------------
 def _check_seg_inputs(images_uint8, maps_uint8, records, S):
     """Everything acr_preprocess_seg_batch trusts, judged on the host before any device is asked for."""
-    if len(images_uint8) == 0 or len(images_uint8) != len(maps_uint8) or len(records) != len(images_uint8):
-        raise ValueError("need one map and one record per image (got %d images, %d maps, %d records)"
-                         % (len(images_uint8), len(maps_uint8), len(records)))
-    if not 0 < int(S) <= 32768:
-        raise ValueError("crop size %r outside 1..32768" % (S,))
-    for i, (a, m, rec) in enumerate(zip(images_uint8, maps_uint8, records)):
-        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
-            raise ValueError("image %d must be a (h, w, 3) uint8 RGB array, got %s %s" % (i, getattr(a, "dtype", type(a)), getattr(a, "shape", "")))
+    if len(images_uint8) != len(maps_uint8):
+        raise ValueError("need one map per image (got %d images, %d maps)" % (len(images_uint8), len(maps_uint8)))
+    _check_images("acr_preprocess_seg_batch", images_uint8, records, S)
+    for i, (a, m) in enumerate(zip(images_uint8, maps_uint8)):
         if not isinstance(m, np.ndarray) or m.dtype != np.uint8:
             raise ValueError("map %d must be a uint8 array, got %s" % (i, getattr(m, "dtype", type(m))))
         if m.ndim != 2:
             raise ValueError("map %d must be 2-D (h, w), got shape %s" % (i, m.shape))
         if m.shape != a.shape[:2]:
             raise ValueError("map %d is %s, its image %s" % (i, m.shape, a.shape[:2]))
-        ok = (rec["h"] == a.shape[0] and rec["w"] == a.shape[1] and rec["rh"] > 0 and rec["rw"] > 0
-              and 0 <= rec["cont_top"] and rec["cont_top"] + rec["ch"] <= S and 0 <= rec["cont_left"] and rec["cont_left"] + rec["cw"] <= S
-              and 0 <= rec["img_top"] and rec["img_top"] + rec["ch"] <= rec["rh"] and 0 <= rec["img_left"]
-              and rec["img_left"] + rec["cw"] <= rec["rw"] and rec["ch"] >= 0 and rec["cw"] >= 0 and rec["flip"] in (0, 1)
-              and 2 * int(rec["rh"]) * int(rec["h"]) < 2 ** 31 and 2 * int(rec["rw"]) * int(rec["w"]) < 2 ** 31)     # the kernel's int32 sample positions
-        if not ok:
-            raise L.AcrHipError("acr_preprocess_seg_batch: inconsistent geometry record %s for a %s image" % (rec, a.shape))
 
 
 def preprocess_seg_batch(images_uint8, maps_uint8, records, S, device, dtype=torch.float32, map_fill=0, with_ori=True, *,
@@ -187,25 +205,10 @@ def preprocess_seg_batch(images_uint8, maps_uint8, records, S, device, dtype=tor
         raise ValueError("map_fill=%r outside 0..255" % (map_fill,))
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("dtype must be float32 or bfloat16, got %s" % (dtype,))
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise L.AcrHipError("acr_wsss_amd.data runs on the GPU only (acr_preprocess_seg_batch); there is no CPU path")
+    device = _cuda_device("acr_preprocess_seg_batch", device)
     B = len(images_uint8)
-    arrays = list(images_uint8) + list(maps_uint8)
-    sizes = [int(a.size) for a in arrays]
-    offs = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])       # 16-byte aligned images and maps
-    stage = torch.empty(int(offs[-1]), dtype=torch.uint8).pin_memory()
-    sn = stage.numpy()
-    for a, o, s in zip(arrays, offs[:-1], sizes):
-        sn[o:o + s] = np.ascontiguousarray(a).reshape(-1)
-    records = records.copy()
-    records["offset"] = offs[:B]
-    packed = stage.to(device, non_blocking=True)
-    # the record table and, right behind it, the int64 map offsets: one pinned buffer, one copy
-    raw = np.concatenate([records.view(np.uint8).reshape(-1), offs[B:2 * B].astype("<i8").view(np.uint8)])
-    table_host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)
-    table_host.numpy()[:] = raw
-    table = table_host.to(device, non_blocking=True)
+    offs, stage, packed = _upload_packed(list(images_uint8) + list(maps_uint8), device)      # images and maps share the buffer
+    table = _upload_table(records, offs[:B], device, extra=offs[B:])                        # ... and the map offsets the table's
     map_offs = table[B * PRE_IMAGE.itemsize:]
     images = torch.empty((B, 3, S, S), dtype=dtype, device=device)
     ori = torch.empty((B, 3, S, S), dtype=torch.uint8, device=device) if with_ori else None

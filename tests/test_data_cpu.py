@@ -87,6 +87,37 @@ def test_no_cpu_path():
         data.val_batch([np.zeros((8, 8, 3), np.uint8)], 16, device="cpu")
 
 
+def test_host_validation_needs_no_gpu():
+    """preprocess_batch judges its arguments on the host, before any device, by the rules of the segmentation path
+    (test_segdata_cpu.py::test_host_validation_needs_no_gpu): the same bad records, the same errors."""
+    from acr_wsss_amd._lib import AcrHipError
+    img = np.zeros((30, 40, 3), np.uint8)
+    rec = np.zeros(1, data.PRE_IMAGE)
+    rec[0] = (0, 30, 40, 24, 32, 1, 4, 0, 0, 0, 24, 32, 0)      # 24 x 32 resized image at rows 4..27 of a 32 x 32 container
+    for bad_img in (img.astype(np.float32), img[:, :, :2], img[:, :, 0]):
+        with pytest.raises(ValueError):
+            data.preprocess_batch([bad_img], rec, 32, "cuda")
+    with pytest.raises(ValueError):
+        data.preprocess_batch([img, img], rec, 32, "cuda")
+    with pytest.raises(ValueError):
+        data.preprocess_batch([img], rec, 0, "cuda")
+    for field, value in (("img_top", 1),                         # rows 1..24 of a 24-row image
+                         ("img_left", 1), ("cont_top", 9),       # rows 9..32 of a 32-row container
+                         ("cont_left", 1), ("ch", 25), ("cw", 33), ("h", 31), ("w", 39), ("rh", 0), ("cont_top", -1), ("flip", 2),
+                         ("ch", -1), ("cw", -1)):
+        bad = rec.copy()
+        bad[field] = value
+        with pytest.raises(AcrHipError, match="acr_preprocess_batch: inconsistent geometry"):
+            data.preprocess_batch([img], bad, 32, "cuda")
+    big = np.zeros(1, data.PRE_IMAGE)                            # 2 * rw * w = 2^31: past the kernel's int32 sample positions
+    big[0] = (0, 1, 32768, 1, 32768, 0, 0, 0, 0, 0, 1, 32768, 0)
+    with pytest.raises(AcrHipError, match="inconsistent geometry"):
+        data.preprocess_batch([np.zeros((1, 32768, 3), np.uint8)], big, 32768, "cuda")
+    # well-formed arguments, no GPU device: there is no CPU path
+    with pytest.raises(AcrHipError, match="no CPU path"):
+        data.preprocess_batch([img], rec, 32, "cpu")
+
+
 GOLDEN_CHUNKS = ["train_a", "train_b", "train_c", "val_a", "val_b"]
 
 
