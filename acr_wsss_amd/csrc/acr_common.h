@@ -45,6 +45,16 @@ __device__ __forceinline__ void acr_dma_barrier() {
 // The "memory" clobber keeps the compiler from moving memory accesses across it.
 __device__ __forceinline__ void acr_barrier_nofence() { asm volatile("s_barrier" ::: "memory"); }
 
+// ---- LDS reads the compiler must not see ------------------------------------------------------------------------------------
+// hipcc cannot tell an LDS-DMA's LDS write from an LDS load of another slot: behind a global_load_lds it puts s_waitcnt vmcnt(0)
+// in front of the next LDS load builtin.  Reads written as inline asm are invisible to that pass; the caller waits on lgkmcnt (LDS
+// operations of a wave return in order: "at most n outstanding" = "all but my n newest have landed"; operations the compiler adds
+// only make a wait stricter).  Addresses are LDS byte addresses; outputs are early-clobber and the waits name what must have landed.
+#define ACR_LDS_RD128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
+#define ACR_LDS_RD32(dst, addr, OFF) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
+#define ACR_LDS_WAIT4(cnt, a, b, c, d) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+#define ACR_LDS_WAIT1(cnt, a) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(a))
+
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Remap the
 // linear block id so that each XCD walks one contiguous chunk of the work list: neighbouring
 // tiles (same batch/head -> same K/V panels) then hit the same 4 MiB L2.  Bijective for any n.

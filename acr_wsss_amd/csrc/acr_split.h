@@ -100,8 +100,5 @@ __device__ __forceinline__ int planes_chunk_off(int rr, int kh) { return rr * IM
 // LDS byte address of lane (r, h)'s fragment read in a plane copied as is to `base`: row `row` of the block, row & 31 == r
 #define IMG_FRAG_SWZ(r, h) (((h) ^ IMG_ROW_SWZ(r)) * 16)
 #define IMG_FRAG_ADDR(base, row, r, h) ((base) + (row) * IMG_ROW_B + IMG_FRAG_SWZ(r, h))
-// LDS reads the compiler must not see (it waits for every LDS-DMA in flight before a visible one); the caller waits on lgkmcnt
-#define IMG_RD128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
-#define IMG_RD32(dst, addr, OFF) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
 // stage of a weight-image convolution in LDS: the weight's three planes, then the fp32 activation tile
 #define IMG_W_STAGE_B(tile_floats) (3 * IMG_PLANE_B + (tile_floats) * 4)

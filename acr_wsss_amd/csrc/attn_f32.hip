@@ -24,6 +24,7 @@
 // On this fp32 path the MFMA pipe is the bound (64 cycles per 32x32x2); LDS and VALU hide under it.
 #include "acr_common.h"
 #include "attn_f32.h"
+#include "attn_f32_scores.h"
 
 #define LDP 68                     // LDS row pitch (floats): 64 + 4 -> conflict-free b128 row reads
 #define TILE_FLOATS (32 * LDP)
@@ -583,6 +584,12 @@ extern "C" int acr_attn_fwd(const acr_attn_desc* d, const void* q, const void* k
     return attn_fwd_t<__bf16>(d, q, k, v, o, lse2, pmean, pmean_sb, pmean_st, (hipStream_t)stream);
 }
 
+// the gradient of the head mean: rows of at least T floats, samples at least T rows apart
+static int check_gmean(const acr_attn_desc* d, const char* who, const float* gmean, int64_t gmean_sb, int64_t gmean_st) {
+    ACR_CHECK_ARG(!gmean || (gmean_st >= d->T && gmean_sb >= (int64_t)d->T * gmean_st), "%s: gmean row pitch < T or batch stride < T*pitch", who);
+    return ACR_OK;
+}
+
 template <typename T>
 static int attn_bwd_t(const acr_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
                       const void* d_o, const float* lse2, const float* gm, int64_t gm_sb, int64_t gm_st, void* dq,
@@ -605,8 +612,8 @@ extern "C" int acr_attn_bwd(const acr_attn_desc* d, const void* q, const void* k
     int rc = check_desc(d, "acr_attn_bwd");
     if (rc) return rc;
     ACR_CHECK_ARG(q && k && v && o && d_o && lse2 && dq && dk && dv && delta_ws, "acr_attn_bwd: null pointer");
-    ACR_CHECK_ARG(!gmean || (gmean_st >= d->T && gmean_sb >= (int64_t)d->T * gmean_st),
-                  "acr_attn_bwd: gmean row pitch < T or batch stride < T*pitch");
+    rc = check_gmean(d, "acr_attn_bwd", gmean, gmean_sb, gmean_st);
+    if (rc) return rc;
     const bool f32 = d->dtype == ACR_F32;
     ACR_CHECK_ARG(f32 ? (aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o) && aligned16(d_o))
                       : (aligned8(q) && aligned8(k) && aligned8(v) && aligned8(o) && aligned8(d_o)),
@@ -632,8 +639,7 @@ extern "C" int acr_attn_bwd(const acr_attn_desc* d, const void* q, const void* k
 extern "C" int64_t acr_attn_scores_floats(const acr_attn_desc* d) {
     if (d == nullptr || d->B <= 0 || d->H <= 0 || d->T <= 0) return 0;
     if (d->dtype == ACR_F32_BF16X3) return acr_attn_x3_scores_floats(geom(d));
-    const int64_t nb = (d->T + 31) / 32;
-    return (int64_t)d->B * d->H * nb * nb * 1024;
+    return attn_score_floats(d->B, d->H, d->T);
 }
 
 extern "C" int64_t acr_attn_bwd_ws_floats(const acr_attn_desc* d) {
@@ -650,6 +656,17 @@ static int check_x3(const acr_attn_desc* d, const char* who) {
     return ACR_OK;
 }
 
+// pointer, alignment and pmean-pitch checks of the two resident-score forwards (o_image: only acr_attn_fwd_scores_oimg has one)
+static int check_fwd_scores(const acr_attn_desc* d, const char* who, const void* q, const void* k, const void* v, const void* o,
+                            const float* lse2, const float* scores, const float* pmean, int64_t pmean_sb, int64_t pmean_st,
+                            bool has_image, const float* o_image) {
+    ACR_CHECK_ARG(q && k && v && o && lse2 && scores && (!has_image || o_image), "%s: null pointer", who);
+    ACR_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o) && aligned16(scores) && aligned16(o_image),
+                  "%s: q/k/v/o/scores%s must be 16-byte aligned", who, has_image ? "/o_image" : "");
+    ACR_CHECK_ARG(!pmean || (pmean_st >= d->T && pmean_sb >= (int64_t)d->T * pmean_st), "%s: pmean row pitch < T or batch stride < T*pitch", who);
+    return ACR_OK;
+}
+
 extern "C" int acr_attn_fwd_scores(const acr_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse2,
                                    float* scores, float* pmean, int64_t pmean_sb, int64_t pmean_st, void* stream) {
     int rc = check_desc(d, "acr_attn_fwd_scores");
@@ -658,11 +675,8 @@ extern "C" int acr_attn_fwd_scores(const acr_attn_desc* d, const void* q, const 
         acr_set_error("acr_attn_fwd_scores: fp32 tensors only (the bf16 kernels recompute the logits)");
         return ACR_ERR_UNSUPPORTED;
     }
-    ACR_CHECK_ARG(q && k && v && o && lse2 && scores, "acr_attn_fwd_scores: null pointer");
-    ACR_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o) && aligned16(scores),
-                  "acr_attn_fwd_scores: q/k/v/o/scores must be 16-byte aligned");
-    ACR_CHECK_ARG(!pmean || (pmean_st >= d->T && pmean_sb >= (int64_t)d->T * pmean_st),
-                  "acr_attn_fwd_scores: pmean row pitch < T or batch stride < T*pitch");
+    rc = check_fwd_scores(d, "acr_attn_fwd_scores", q, k, v, o, lse2, scores, pmean, pmean_sb, pmean_st, false, nullptr);
+    if (rc) return rc;
     if (d->dtype == ACR_F32_BF16X3) {
         rc = check_x3(d, "acr_attn_fwd_scores");
         if (rc) return rc;
@@ -685,11 +699,8 @@ extern "C" int acr_attn_fwd_scores_oimg(const acr_attn_desc* d, const void* q, c
         acr_set_error("acr_attn_fwd_scores_oimg: ACR_F32_BF16X3 only (the image is the split-product operand form)");
         return ACR_ERR_UNSUPPORTED;
     }
-    ACR_CHECK_ARG(q && k && v && o && lse2 && scores && o_image, "acr_attn_fwd_scores_oimg: null pointer");
-    ACR_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o) && aligned16(scores) && aligned16(o_image),
-                  "acr_attn_fwd_scores_oimg: q/k/v/o/scores/o_image must be 16-byte aligned");
-    ACR_CHECK_ARG(!pmean || (pmean_st >= d->T && pmean_sb >= (int64_t)d->T * pmean_st),
-                  "acr_attn_fwd_scores_oimg: pmean row pitch < T or batch stride < T*pitch");
+    rc = check_fwd_scores(d, "acr_attn_fwd_scores_oimg", q, k, v, o, lse2, scores, pmean, pmean_sb, pmean_st, true, o_image);
+    if (rc) return rc;
     ACR_CHECK_ARG(d->o_sh == 64 && d->o_st == (int64_t)d->H * 64 && d->o_sb == (int64_t)d->T * d->o_st,
                   "acr_attn_fwd_scores_oimg: o must be the dense (B, T, H*64) activation (its image is that of the (B*T) x (H*64) matrix)");
     rc = check_x3(d, "acr_attn_fwd_scores_oimg");
@@ -718,8 +729,8 @@ extern "C" int acr_attn_bwd_scores(const acr_attn_desc* d, const void* q, const 
     ACR_CHECK_ARG(q && k && v && o && d_o && lse2 && scores && dq && dk && dv && delta_ws, "acr_attn_bwd_scores: null pointer");
     ACR_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o) && aligned16(d_o) && aligned16(scores),
                   "acr_attn_bwd_scores: inputs must be 16-byte aligned");
-    ACR_CHECK_ARG(!gmean || (gmean_st >= d->T && gmean_sb >= (int64_t)d->T * gmean_st),
-                  "acr_attn_bwd_scores: gmean row pitch < T or batch stride < T*pitch");
+    rc = check_gmean(d, "acr_attn_bwd_scores", gmean, gmean_sb, gmean_st);
+    if (rc) return rc;
     ACR_CHECK_ARG(!gmean || ((gmean_st & 3) == 0 && (gmean_sb & 3) == 0 && aligned16(gmean)),
                   "acr_attn_bwd_scores: gmean must be 16-byte aligned with pitch and batch stride multiples of 4 floats");
     if (d->dtype == ACR_F32_BF16X3) {                        // q, k, v are read from the planes the forward left behind the scores

@@ -29,6 +29,7 @@
 #include "acr_common.h"
 #include "attn_f32.h"
 #include "attn_f32_tiles.h"
+#include "attn_f32_scores.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -83,31 +84,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(AttnGeom g, const 
         f32x16 s = {0};
         rowop_i<KOFF>(s, sm, lb, qreg);                    // s[reg] = S2[key = k0 + krow][query = q0 + r]
         __builtin_amdgcn_s_setprio(2);
-        if (k0 + 32 > g.T) {                               // only the last key tile has keys beyond T (uniform branch)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (k0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
-        float mx = s[0];
-#pragma unroll
-        for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, s[reg]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        // Deferred rescale: the running reference m moves only when some row's maximum has grown by more than 2^8 since
-        // it was set (p then stays below 2^8: no overflow, full fp32 precision); most steps skip the 32 multiplies of O and
-        // the exp2 of alpha.  exp2 = one v_exp_f32.
-        if (__any(mx > m + 8.f)) {
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);
-            l *= alpha;
-            o0 *= alpha; o1 *= alpha;
-            m = mn;
-        }
-        float rs = 0.f;
+        ATTN_MASK_ROWS(s, k0, g.T, h);
         f32x16 p;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) { p[reg] = __builtin_amdgcn_exp2f(s[reg] - m); rs += p[reg]; }
-        rs += __shfl_xor(rs, 32);
-        l += rs;
+        ATTN_SOFTMAX_STEP(s, m, l, o0, o1, p);             // deferred rescale: attn_f32_scores.h
         __builtin_amdgcn_s_setprio(0);
         accop_b_i<VOFF, 0>(o0, p, sm, lb);                 // o[reg] = O^T[d = 32*blk + krow][query = r]
         accop_b_i<VOFF, 1>(o1, p, sm, lb);
@@ -118,15 +97,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(AttnGeom g, const 
     }
     if (live && q0 + r < g.T) {
         const float inv = 1.f / l;
-        float* ob = o + (int64_t)b * g.osb + (int64_t)(q0 + r) * g.ost + (int64_t)hd * g.osh;
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-            f32x4 a = {o0[4 * grp] * inv, o0[4 * grp + 1] * inv, o0[4 * grp + 2] * inv, o0[4 * grp + 3] * inv};
-            f32x4 c = {o1[4 * grp] * inv, o1[4 * grp + 1] * inv, o1[4 * grp + 2] * inv, o1[4 * grp + 3] * inv};
-            *reinterpret_cast<f32x4*>(ob + 8 * grp + 4 * h) = a;
-            *reinterpret_cast<f32x4*>(ob + 32 + 8 * grp + 4 * h) = c;
-        }
-        if (h == 0) lse2[((int64_t)b * g.H + hd) * g.T + q0 + r] = m + log2f(l);
+        ATTN_FWD_FINISH(g, o, lse2, b, hd, q0, r, h, o0, o1, m, l, inv);
     }
 }
 
@@ -382,11 +353,7 @@ __device__ __forceinline__ void attn_dq_body(float* smem, int bid, int nblk, con
         rowop(s, kt, qreg, r, h);                           // S2^T[key = krow][query = r]
         rowop(dp, vt, doreg, r, h);                         // dP^T[key][query]
         f32x16 ds;
-        if (k0 + 32 > g.T) {                               // last key tile: keys beyond T contribute nothing (uniform branch)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (k0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
+        ATTN_MASK_ROWS(s, k0, g.T, h);                     // last key tile: keys beyond T contribute nothing
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) ds[reg] = __builtin_amdgcn_exp2f(s[reg] - l2q) * (dp[reg] + gv[reg] - dl);
         accop_a(dq0, ds, kt, 0, r, h);                      // dQ[query = krow][d = 32*blk + r]
@@ -463,11 +430,7 @@ __device__ __forceinline__ void attn_dkdv_body(float* smem, float* rc, int bid, 
         rowop(s, qtile, kreg, r, h);                        // S2[query = krow][key = r]
         rowop(dp, dotile, vreg, r, h);                      // dP[query][key]
         f32x16 p, ds;
-        if (q0 + 32 > g.T) {                               // last query tile holds clamped copies of row T-1 beyond T: p = 0 there
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (q0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
+        ATTN_MASK_ROWS(s, q0, g.T, h);                     // last query tile holds clamped copies of row T-1 beyond T: p = 0 there
         if (!kok) {                                         // keys beyond T (lanes of the last wave only)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) s[reg] = -INFINITY;

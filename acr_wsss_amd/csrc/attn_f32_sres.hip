@@ -26,6 +26,7 @@
 #include "acr_common.h"
 #include "attn_f32.h"
 #include "attn_f32_tiles.h"
+#include "attn_f32_scores.h"
 #include "attn_f32_sres_tails.h"
 
 
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_sres_kernel
     const LaneBasesA lb = lane_bases_a(r, h, smem);
     int doff[(8 + NW - 1) / NW];
     dma_offsets32_nw<NW>(doff, g.st, wave, lane);
-    float* sblk = sres + sres_block(g, NB, b, hd, min(q0 >> 5, NB - 1), 0) + lane * 4;
+    float* sblk = sres + attn_score_block(g.H, NB, b, hd, min(q0 >> 5, NB - 1), 0) + lane * 4;
     auto step = [&](int k0, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
         constexpr int KOFF = SLOT * 2 * DT_FLOATS * 4, VOFF = KOFF + DT_FLOATS * 4;
@@ -85,34 +86,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_sres_kernel
         f32x16 s = {0};
         rowop_x<KOFF>(s, lb, qreg);                        // s[reg] = S2[key = k0 + krow][query = q0 + r]
         __builtin_amdgcn_s_setprio(2);
-        if (k0 + 32 > g.T) {                               // only the last key tile has keys beyond T (uniform branch)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (k0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
-        float* sp = sblk + (int64_t)(k0 >> 5) * SB_FLOATS;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const f32x4 t = {s[4 * gq], s[4 * gq + 1], s[4 * gq + 2], s[4 * gq + 3]};
-            SRES_STORE(sp + gq * 256, t);
-        }
-        float mx = s[0];
-#pragma unroll
-        for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, s[reg]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        if (__any(mx > m + 8.f)) {                         // deferred rescale (see attn_fwd_dma_kernel)
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);
-            l *= alpha;
-            o0 *= alpha; o1 *= alpha;
-            m = mn;
-        }
-        float rs = 0.f;
+        ATTN_MASK_ROWS(s, k0, g.T, h);
+        attn_store_scores(sblk + (int64_t)(k0 >> 5) * SB_FLOATS, s);
         f32x16 p;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) { p[reg] = __builtin_amdgcn_exp2f(s[reg] - m); rs += p[reg]; }
-        rs += __shfl_xor(rs, 32);
-        l += rs;
+        ATTN_SOFTMAX_STEP(s, m, l, o0, o1, p);
         __builtin_amdgcn_s_setprio(0);
         accop_x<VOFF, 0, false>(o0, p, lb);                // o[reg] = O^T[d = 32*blk + krow][query = r]
         accop_x<VOFF, 1, false>(o1, p, lb);
@@ -123,15 +100,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_sres_kernel
     }
     if (live && q0 + r < g.T) {
         const float inv = 1.f / l;
-        float* ob = o + (int64_t)b * g.osb + (int64_t)(q0 + r) * g.ost + (int64_t)hd * g.osh;
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-            f32x4 a = {o0[4 * grp] * inv, o0[4 * grp + 1] * inv, o0[4 * grp + 2] * inv, o0[4 * grp + 3] * inv};
-            f32x4 c = {o1[4 * grp] * inv, o1[4 * grp + 1] * inv, o1[4 * grp + 2] * inv, o1[4 * grp + 3] * inv};
-            *reinterpret_cast<f32x4*>(ob + 8 * grp + 4 * h) = a;
-            *reinterpret_cast<f32x4*>(ob + 32 + 8 * grp + 4 * h) = c;
-        }
-        if (h == 0) lse2[((int64_t)b * g.H + hd) * g.T + q0 + r] = m + log2f(l);
+        ATTN_FWD_FINISH(g, o, lse2, b, hd, q0, r, h, o0, o1, m, l, inv);
     }
 }
 
@@ -178,7 +147,7 @@ template <int NW> __global__ __launch_bounds__(64 * NW, DELTA4_MINB) void attn_d
     }
     part += __shfl_xor(part, 32);
     const float l2q = qok ? lse2[((int64_t)b * g.H + hd) * g.T + qrow] : INFINITY;
-    const float* sp = sres + sres_block(g, NB, b, hd, qb, 0) + lane * 4;
+    const float* sp = sres + attn_score_block(g.H, NB, b, hd, qb, 0) + lane * 4;
     const bool loader = tid < 256;                         // the first four waves fetch the gm blocks
     const int lrow = (tid & 255) >> 3, lc = (tid & 7) * 4;  // this thread's float4 of a gm block: row lrow, columns lc ..
     const float* gl = gm + (int64_t)b * gm_sb + (int64_t)min(qb * 32 + lrow, g.T - 1) * gm_st + lc;
@@ -251,7 +220,7 @@ __global__ __launch_bounds__(256) void attn_pmean_sres_kernel(AttnGeom g, int NB
     const int t = id / NB;
     const int qb = t % NB, b = t / NB;
     const int qrow = qb * 32 + theta;
-    const float* sp = sres + sres_block(g, NB, b, 0, qb, kb) + lane * 4;
+    const float* sp = sres + attn_score_block(g.H, NB, b, 0, qb, kb) + lane * 4;
     const int64_t hstride = (int64_t)NB * NB * SB_FLOATS;
     const float* lp = lse2 + (int64_t)b * g.H * g.T + min(qrow, g.T - 1);
     f32x16 pm = {0};
@@ -329,7 +298,7 @@ __global__ __launch_bounds__(256) void attn_delta_sres_kernel(AttnGeom g, int NB
     float rho = 0.f;
     if (gm != nullptr) {                                    // uniform over the launch
         const float l2q = qok ? lse2[((int64_t)b * g.H + hd) * g.T + qrow] : INFINITY;
-        const float* sp = sres + sres_block(g, NB, b, hd, qb, 0) + lane * 4;
+        const float* sp = sres + attn_score_block(g.H, NB, b, hd, qb, 0) + lane * 4;
         const float* gr = gm + (int64_t)b * gm_sb + (int64_t)qc * gm_st;
         const int nfull = g.T >> 5;                        // key blocks entirely inside [0, T)
 #pragma unroll 4
@@ -361,19 +330,8 @@ __global__ __launch_bounds__(256) void attn_delta_sres_kernel(AttnGeom g, int NB
     if (hh == 0 && qok) delta[((int64_t)b * g.H + hd) * g.T + qrow] = part + rho * (1.f / (float)g.H);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Counted waits (round 4).  A step's tile DMA must have landed at the step's barrier, but the private streams of a wave -- its
-// score blocks (two steps ahead) and its G block (one step) -- are YOUNGER vector-memory operations and may stay in flight:
-// vmcnt retires in issue order, so "at most n outstanding" with n = the number of younger operations is exactly "the tile has
-// landed".  n is wave-uniform; every stream is LDS-DMA (register prefetch rings turn into loop-carried copies that hipcc
-// waits for right behind the loads -- found in this file's round-3 ISA).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sres_wait_vm(int n) {
-    if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-#define SRES_FENCE() asm volatile("" ::: "memory")
+// counted waits of the two sweeps below (attn_f32_scores.h): their steps ask for 8, 4 or 0 younger operations
+__device__ __forceinline__ void sres_wait_vm(int n) { attn_wait_vm<true, 8, 4>(n); }
 
 // ---------------------------------------------------------------------------------------------
 // dQ: workgroup = (b, h, 128 queries); dO rows of the wave's 32 queries in registers; K/V tiles stream through the LDS ring;
@@ -400,32 +358,7 @@ __device__ __forceinline__ void attn_dq_sres_body(float* smem, float* ssm, float
     const int64_t obase = (int64_t)b * g.osb + (int64_t)hd * g.osh;
     const float* kb = k + base;
     const float* vb = v + base;
-    // private streams of this wave: score blocks (qb = q0 / 32, kb = step) copied as stored, G block rows = its queries with
-    // 16-byte chunk c of row q in slot c ^ ((q >> 1) & 7) (the lane's row reads are then bank-conflict free)
-    const float* srow = sres + sres_block(g, NB, b, hd, min(q0 >> 5, NB - 1), 0) + lane * 4;
-    float* sw = ssm + wave * 2 * SB_FLOATS;
-    auto dma_scores = [&](int kblk, int slot) {
-        const float* src = srow + (int64_t)kblk * SB_FLOATS;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            __builtin_amdgcn_global_load_lds((glb_vp)(src + gq * 256), (lds_vp)(sw + slot * SB_FLOATS + gq * 256), 16, 0, SRES_DMA_AUX);
-    };
-    const float* gb0 = gm ? gm + (int64_t)b * gm_sb : nullptr;          // uniform
-    float* gw = gsm + wave * SB_FLOATS;
-    const float* grow[4];
-    int gchunk[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int row = 8 * p + (lane >> 3);
-        grow[p] = gb0 ? gb0 + (int64_t)min(q0 + row, g.T - 1) * gm_st : nullptr;
-        gchunk[p] = 4 * ((lane & 7) ^ ((row >> 1) & 7));
-    }
-    auto dma_g = [&](int k0) {
-        if (gb0 == nullptr) return;
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-            __builtin_amdgcn_global_load_lds((glb_vp)(grow[p] + min(k0 + gchunk[p], (int)gm_st - 4)), (lds_vp)(gw + p * 256), 16, 0, 0);
-    };
+    ATTN_QLANE_STREAMS(sres, g.H, NB, g.T, b, hd, q0, wave, lane, ssm, gsm, gm, gm_sb, gm_st);      // this wave's private streams
     dma_tile32(smem, kb, g.st, 0, g.T, wave, lane);
     dma_tile32(smem + DT_FLOATS, vb, g.st, 0, g.T, wave, lane);
     if (live) {
@@ -443,10 +376,7 @@ __device__ __forceinline__ void attn_dq_sres_body(float* smem, float* ssm, float
     const LaneBasesA lb = lane_bases_a(r, h, smem);
     int doff[2];
     dma_offsets32(doff, g.st, wave, lane);
-    const uint32_t saddr = lds_addr_of(sw) + lane * 16;                                 // + slot * 4096 + gq * 1024
-    uint32_t gaddr[4];                                                                  // quad gq = keys 8 gq + 4 h .. + 3 of row r
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) gaddr[gq] = lds_addr_of(gw) + r * 128 + (((2 * gq + h) ^ ((r >> 1) & 7)) << 4);
+    ATTN_QLANE_ADDRS(lane, r, h);
     auto step = [&](int k0, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
         constexpr int KOFF = SLOT * 2 * DT_FLOATS * 4, VOFF = KOFF + DT_FLOATS * 4;
@@ -461,41 +391,22 @@ __device__ __forceinline__ void attn_dq_sres_body(float* smem, float* ssm, float
             dma_tile32(smem + (SLOT ^ 1) * 2 * DT_FLOATS, kb, g.st, k0 + 32, g.T, wave, lane);
             dma_tile32(smem + (SLOT ^ 1) * 2 * DT_FLOATS + DT_FLOATS, vb, g.st, k0 + 32, g.T, wave, lane);
         }
-        SRES_FENCE();
+        ATTN_FENCE();
         if (!live) return;
         f32x16 dp = {0};
         rowop_x<VOFF>(dp, lb, doreg);                      // dP^T[key = krow][query = r]
         // G(t) must have landed in this wave's tile: behind it are scores(t+1) [4] and this step's tile(t+1) [4]
         if (k0 > 0) sres_wait_vm(k0 + 32 < g.T ? 8 : 0);
         f32x4 s4[4], g4[4];
-        ACR_LDS_RD128(s4[0], saddr, SLOT * 4096); ACR_LDS_RD128(s4[1], saddr, SLOT * 4096 + 1024);
-        ACR_LDS_RD128(s4[2], saddr, SLOT * 4096 + 2048); ACR_LDS_RD128(s4[3], saddr, SLOT * 4096 + 3072);
-        if (gb0 != nullptr) {
-            ACR_LDS_RD128(g4[0], gaddr[0], 0); ACR_LDS_RD128(g4[1], gaddr[1], 0);
-            ACR_LDS_RD128(g4[2], gaddr[2], 0); ACR_LDS_RD128(g4[3], gaddr[3], 0);
-            ACR_LDS_WAIT4(0, g4[0], g4[1], g4[2], g4[3]);
-            if (k0 + 32 > g.T) {                           // keys beyond T: their columns hold whatever the row pitch holds
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (k0 + 8 * gq + 4 * h + e >= g.T) g4[gq][e] = 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) g4[gq] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        ACR_LDS_WAIT4(0, s4[0], s4[1], s4[2], s4[3]);
+        ATTN_QLANE_READ(SLOT, s4, g4, k0, g.T, h);
         f32x16 ds;
         __builtin_amdgcn_s_setprio(2);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg)
-            ds[reg] = __builtin_amdgcn_exp2f(s4[reg >> 2][reg & 3] - l2q) * (dp[reg] + g4[reg >> 2][reg & 3] * invH - dl);
+        attn_ds_qlane(ds, s4, g4, dp, l2q, dl, invH);
         __builtin_amdgcn_s_setprio(0);
         // the private tiles have been read: refill G for the next step and the score slot for the step AFTER next
         if (k0 + 32 < g.T) dma_g(k0 + 32);
         if (k0 + 64 < g.T) dma_scores((k0 >> 5) + 2, SLOT);
-        SRES_FENCE();
+        ATTN_FENCE();
         accop_x<KOFF, 0, true>(dq0, ds, lb);               // dQ[query = krow][d = 32*blk + r]
         accop_x<KOFF, 1, true>(dq1, ds, lb);
     };
@@ -545,32 +456,7 @@ __device__ __forceinline__ void attn_dkdv_sres_body(float* smem, float* ssm, flo
     const float* dob = d_o + obase;
     const float* lrow = lse2 + ((int64_t)b * g.H + hd) * g.T;
     const float* drow = delta + ((int64_t)b * g.H + hd) * g.T;
-    // score blocks of this wave: (qb = step, kb = key0 / 32); lane c of DMA piece gq fetches global chunk c ^ (2 gq + (c >> 5))
-    const float* scol = sres + sres_block(g, NB, b, hd, 0, min(key0 >> 5, NB - 1));
-    const int64_t sstep = (int64_t)NB * SB_FLOATS;
-    int soff[4];
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) soff[gq] = gq * 256 + 4 * (lane ^ (2 * gq + (lane >> 5)));
-    float* sw = ssm + wave * 2 * SB_FLOATS;
-    auto dma_scores = [&](int qblk, int slot) {
-        const float* src = scol + (int64_t)qblk * sstep;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            __builtin_amdgcn_global_load_lds((glb_vp)(src + soff[gq]), (lds_vp)(sw + slot * SB_FLOATS + gq * 256), 16, 0, SRES_DMA_AUX);
-    };
-    // G block of the step: rows = the 32 queries, 128 bytes = this wave's 32 keys; columns clamped into the row (the last key
-    // block reaches beyond T: those lanes' P is exactly 0 and whatever they compute never leaves their own accumulator row)
-    const float* gb0 = gm ? gm + (int64_t)b * gm_sb : nullptr;          // uniform
-    float* gw = gsm + wave * SB_FLOATS;
-    const int gcol = min(key0 + 4 * (lane & 7), (int)gm_st - 4);
-    auto dma_g = [&](int q0) {
-        if (gb0 == nullptr) return;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const float* src = gb0 + (int64_t)min(q0 + 8 * p + (lane >> 3), g.T - 1) * gm_st + gcol;
-            __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)(gw + p * 256), 16, 0, 0);
-        }
-    };
+    ATTN_KLANE_STREAMS(sres, g.H, NB, g.T, b, hd, key0, wave, lane, ssm, gsm, gm, gm_sb, gm_st);   // this wave's private streams
     dma_tile32(smem, qb, g.st, 0, g.T, wave, lane);
     dma_tile32(smem + DT_FLOATS, dob, g.ost, 0, g.T, wave, lane);
     if (live) {
@@ -586,15 +472,7 @@ __device__ __forceinline__ void attn_dkdv_sres_body(float* smem, float* ssm, flo
     int qoff[2], dooff[2];                                   // lane parts of the Q / dO tile DMA source addresses (interior tiles)
     dma_offsets32(qoff, g.st, wave, lane);
     dma_offsets32(dooff, g.ost, wave, lane);
-    // transposed score reads: lane (kappa = r, h): LDS byte address = tb[reg & 3] + slot*4096 + 128*(reg >> 2)
-    uint32_t tb[4];
-    {
-        const int gk = r >> 3, hk = (r >> 2) & 1, ek = r & 3, mm = 2 * gk + hk;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            tb[j] = lds_addr_of(ssm) + ((wave * 2 * SB_FLOATS) + gk * 256 + 128 * hk + ek + 4 * ((j + 4 * h) ^ mm)) * 4;
-    }
-    const uint32_t gaddr = lds_addr_of(gsm) + (wave * SB_FLOATS + 4 * h * 32 + r) * 4;      // + 128 * c_reg per register
+    ATTN_KLANE_ADDRS(ssm, gsm, wave, r, h);
     auto step = [&](int q0, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
         constexpr int QOFF = SLOT * 2 * DT_FLOATS * 4, DOOFF = QOFF + DT_FLOATS * 4;
@@ -609,7 +487,7 @@ __device__ __forceinline__ void attn_dkdv_sres_body(float* smem, float* ssm, flo
             dma_tile32(smem + (SLOT ^ 1) * 2 * DT_FLOATS, qb, g.st, q0 + 32, g.T, wave, lane);
             dma_tile32(smem + (SLOT ^ 1) * 2 * DT_FLOATS + DT_FLOATS, dob, g.ost, q0 + 32, g.T, wave, lane);
         }
-        SRES_FENCE();
+        ATTN_FENCE();
         if (!live) return;
         const int qi = min(q0 + r, g.T - 1);
         const float lq_lane = lrow[qi], dq_lane = drow[qi];         // this step's lse2 / delta, one query per lane
@@ -619,28 +497,11 @@ __device__ __forceinline__ void attn_dkdv_sres_body(float* smem, float* ssm, flo
         // loads above, if they are still in flight: 8 is the stricter count)
         if (q0 > 0) sres_wait_vm(q0 + 32 < g.T ? 8 : 0);
         float s[16], gv[16];
-#define SRES_RDS(REG) ACR_LDS_RD32(s[REG], tb[(REG) & 3], SLOT * SB_FLOATS * 4 + 128 * ((REG) >> 2))
-#define SRES_RDG(REG) ACR_LDS_RD32(gv[REG], gaddr, 128 * (((REG) & 3) + 8 * ((REG) >> 2)))
-        SRES_RDS(0); SRES_RDS(1); SRES_RDS(2); SRES_RDS(3); SRES_RDS(4); SRES_RDS(5); SRES_RDS(6); SRES_RDS(7);
-        SRES_RDS(8); SRES_RDS(9); SRES_RDS(10); SRES_RDS(11); SRES_RDS(12); SRES_RDS(13); SRES_RDS(14); SRES_RDS(15);
-        if (gb0 != nullptr) {
-            SRES_RDG(0); SRES_RDG(1); SRES_RDG(2); SRES_RDG(3); SRES_RDG(4); SRES_RDG(5); SRES_RDG(6); SRES_RDG(7);
-            SRES_RDG(8); SRES_RDG(9); SRES_RDG(10); SRES_RDG(11); SRES_RDG(12); SRES_RDG(13); SRES_RDG(14); SRES_RDG(15);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(gv[0]), "+v"(gv[1]), "+v"(gv[2]), "+v"(gv[3]), "+v"(gv[4]), "+v"(gv[5]), "+v"(gv[6]),
-                         "+v"(gv[7]), "+v"(gv[8]), "+v"(gv[9]), "+v"(gv[10]), "+v"(gv[11]), "+v"(gv[12]), "+v"(gv[13]), "+v"(gv[14]), "+v"(gv[15]));
-        } else {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) gv[reg] = 0.f;
-        }
-#undef SRES_RDS
-#undef SRES_RDG
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]),
-                     "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15]));
-        if (q0 + 32 > g.T) {                               // last query block: rows beyond T are junk, P = 0 there
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (q0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
+        ATTN_16(ATTN_RDS, s, SLOT);
+        ATTN_READ_G(gv)
+        asm volatile("s_waitcnt lgkmcnt(0)" : ATTN_V16(s));
+        ATTN_MASK_ROWS(s, q0, g.T, h);                     // last query block: rows beyond T are junk, P = 0 there
+        // P / dS stay this body's own: lse2 / delta sit one query per lane and are spread with __shfl (attn_f32_x3.hip reads an LDS row)
         f32x16 p, ds;
         __builtin_amdgcn_s_setprio(2);
 #pragma unroll
@@ -656,7 +517,7 @@ __device__ __forceinline__ void attn_dkdv_sres_body(float* smem, float* ssm, flo
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (q0 + 32 < g.T) dma_g(q0 + 32);
         if (q0 + 64 < g.T) dma_scores((q0 >> 5) + 2, SLOT);
-        SRES_FENCE();
+        ATTN_FENCE();
         accop_x<DOOFF, 0, true>(dv0, p, lb);               // dV[key = krow][d = 32*blk + r]
         accop_x<DOOFF, 1, true>(dv1, p, lb);
         accop_x<QOFF, 0, true>(dk0, ds, lb);
@@ -707,16 +568,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_sres_kernel(AttnGeom g, const
 // ---------------------------------------------------------------------------------------------
 // launchers (called from attn_f32.hip)
 // ---------------------------------------------------------------------------------------------
-// one leftover 32-row block per (b, h) and enough full workgroups for the split to pay (see "Split tail" above)
-static bool split_tail(int NB) { return (NB & 3) == 1 && NB >= 5; }
-
 void acr_attn_fwd_f32_sres(const AttnGeom& g, const float* q, const float* k, const float* v, float* o, float* lse2, float* scores,
                            float* pmean, int64_t pmean_sb, int64_t pmean_st, hipStream_t st) {
     const int NB = (g.T + 31) / 32;
     // waves (32-query blocks) per workgroup: 4.  T = 785 is 25 blocks = 5 x 5 exactly, but five-wave workgroups measured 0.86 ms
     // against 0.64 ms at B = 32, H = 12 (160 VGPRs allow 12 wave slots per CU, i.e. only two 5-wave workgroups against three
     // 4-wave ones): the leftover block goes to a split-tail workgroup instead (attn_f32_sres_tails.h)
-    const int ntail = split_tail(NB) ? g.B * g.H : 0;
+    const int ntail = attn_split_tail(NB, 4) ? g.B * g.H : 0;
     const int nmain = g.B * g.H * (ntail ? NB / 4 : (NB + 3) / 4);
     hipLaunchKernelGGL(attn_fwd_sres_kernel<4>, dim3(nmain + ntail), dim3(256), 0, st, g, q, k, v, o, lse2, scores, ntail);
     if (pmean) acr_attn_pmean_sres(g, scores, lse2, pmean, pmean_sb, pmean_st, st);
@@ -750,7 +608,7 @@ void acr_attn_bwd_f32_sres(const AttnGeom& g, const float* q, const float* k, co
                            float* dk, float* dv, float* delta, hipStream_t st) {
     const int nt = (g.T + 127) / 128, NB = (g.T + 31) / 32;
     acr_attn_delta_sres(g, scores, o, d_o, lse2, gm, gm_sb, gm_st, delta, st);
-    const int ntail = split_tail(NB) ? g.B * g.H : 0;
+    const int ntail = attn_split_tail(NB, 4) ? g.B * g.H : 0;
     const int nmain = g.B * g.H * (ntail ? NB / 4 : nt);
     hipLaunchKernelGGL(attn_bwd_sres_kernel, dim3(2 * nmain + 2 * ntail), dim3(256), 0, st, g, q, k, v, d_o, lse2, (const float*)delta,
                        scores, gm, gm_sb, gm_st, dq, dk, dv, ntail);

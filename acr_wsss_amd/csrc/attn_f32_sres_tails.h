@@ -9,22 +9,8 @@
 #include "acr_common.h"
 #include "attn_f32.h"
 #include "attn_f32_tiles.h"
+#include "attn_f32_scores.h"
 
-#define SB_FLOATS 1024
-// Cache policy of the score stream.  Every byte of `scores` is written once and read once per consumer, 983 MB per layer
-// against 4 MB of L2 per XCD and 256 MB of Infinity Cache.  Measured per kernel (scripts/lab/attn_gen.py with lab builds):
-// nontemporal loads take the head-mean stream from 235 to 183 us and the dQ body's loads the backward from 1549 to 1535 us;
-// nontemporal stores the forward from 580 to 567 us; the row-term stream gets 5 % SLOWER with them (its G rows want to stay
-// cached beside the scores) and the dK/dV body's LDS-DMA with the nt policy (aux = 2) is within noise: both keep the default.
-#define SRES_LOAD_NT(p) __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p))
-#define SRES_LOAD(p) (*reinterpret_cast<const f32x4*>(p))
-#define SRES_STORE(p, v) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p))
-#define SRES_LOAD_DQ(p) SRES_LOAD_NT(p)
-#define SRES_DMA_AUX 0
-
-__device__ __forceinline__ int64_t sres_block(const AttnGeom& g, int NB, int b, int hd, int qb, int kb) {
-    return ((((int64_t)b * g.H + hd) * NB + qb) * NB + kb) * SB_FLOATS;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Split tail (all three MFMA sweeps).  T = 785 is 25 blocks of 32 rows = 6 workgroups of 4 blocks + ONE block: as a seventh
@@ -58,43 +44,19 @@ __device__ __forceinline__ void attn_fwd_tail_body(float* smem, float* mlsh, con
     f32x16 o0 = {0}, o1 = {0};
     const LaneBases lb = lane_bases_at(r, h, wave * DT_FLOATS * 4);
     const char* sm = reinterpret_cast<const char*>(smem);
-    float* sblk = sres + sres_block(g, NB, b, hd, NB - 1, 0) + lane * 4;
+    float* sblk = sres + attn_score_block(g.H, NB, b, hd, NB - 1, 0) + lane * 4;
     for (int kt = wave; kt < NB; kt += NW) {
         const int k0 = kt * 32;
         dma_tile32_one(tl, kb, g.st, k0, g.T, lane);
         wave_wait_dma();
         f32x16 s = {0};
         rowop_i<0>(s, sm, lb, qreg);
-        if (k0 + 32 > g.T) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (k0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
+        ATTN_MASK_ROWS(s, k0, g.T, h);
         wave_wait_lds();                                   // the K image has been read: V may overwrite it
         dma_tile32_one(tl, vb, g.st, k0, g.T, lane);
-        float* sp = sblk + (int64_t)kt * SB_FLOATS;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const f32x4 t = {s[4 * gq], s[4 * gq + 1], s[4 * gq + 2], s[4 * gq + 3]};
-            SRES_STORE(sp + gq * 256, t);
-        }
-        float mx = s[0];
-#pragma unroll
-        for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, s[reg]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        if (__any(mx > m + 8.f)) {
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);
-            l *= alpha;
-            o0 *= alpha; o1 *= alpha;
-            m = mn;
-        }
-        float rs = 0.f;
+        attn_store_scores(sblk + (int64_t)kt * SB_FLOATS, s);
         f32x16 p;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) { p[reg] = __builtin_amdgcn_exp2f(s[reg] - m); rs += p[reg]; }
-        rs += __shfl_xor(rs, 32);
-        l += rs;
+        ATTN_SOFTMAX_STEP(s, m, l, o0, o1, p);
         wave_wait_dma();
         accop_b_i<0, 0>(o0, p, sm, lb);
         accop_b_i<0, 1>(o1, p, sm, lb);
@@ -122,22 +84,15 @@ __device__ __forceinline__ void attn_fwd_tail_body(float* smem, float* mlsh, con
     }
     if (q0 + r < g.T) {
         const float inv = 1.f / L;
-        float* ob = o + (int64_t)b * g.osb + (int64_t)(q0 + r) * g.ost + (int64_t)hd * g.osh;
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-            f32x4 a = {a0[4 * grp] * inv, a0[4 * grp + 1] * inv, a0[4 * grp + 2] * inv, a0[4 * grp + 3] * inv};
-            f32x4 c = {a1[4 * grp] * inv, a1[4 * grp + 1] * inv, a1[4 * grp + 2] * inv, a1[4 * grp + 3] * inv};
-            *reinterpret_cast<f32x4*>(ob + 8 * grp + 4 * h) = a;
-            *reinterpret_cast<f32x4*>(ob + 32 + 8 * grp + 4 * h) = c;
-        }
-        if (h == 0) lse2[((int64_t)b * g.H + hd) * g.T + q0 + r] = M + log2f(L);
+        ATTN_FWD_FINISH(g, o, lse2, b, hd, q0, r, h, a0, a1, M, L, inv);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // split-tail workgroups of the backward sweeps (see "Split tail" at the top): the last query block's dQ with the key tiles
 // dealt over the four waves, the last key block's dK / dV with the query tiles dealt over the four waves; private tile
-// images, no barriers inside the loops, partial sums merged through LDS in wave order.
+// images, no barriers inside the loops, partial sums merged through LDS in wave order.  Scores and G come through registers and plain
+// LDS loads here, not through the private rings of attn_f32_scores.h: apart from the row mask these bodies keep their own text.
 // ---------------------------------------------------------------------------------------------
 template <int NW>
 __device__ __forceinline__ void attn_dq_tail_body(float* smem, const AttnGeom& g, const float* __restrict__ k,
@@ -163,7 +118,7 @@ __device__ __forceinline__ void attn_dq_tail_body(float* smem, const AttnGeom& g
     const float dl = qok ? delta[((int64_t)b * g.H + hd) * g.T + q0 + r] : 0.f;
     const float invH = 1.f / (float)g.H;
     const float* grow = gm ? gm + (int64_t)b * gm_sb + (int64_t)min(q0 + r, g.T - 1) * gm_st : nullptr;
-    const float* sblk = sres + sres_block(g, NB, b, hd, NB - 1, 0) + lane * 4;
+    const float* sblk = sres + attn_score_block(g.H, NB, b, hd, NB - 1, 0) + lane * 4;
     f32x16 dq0 = {0}, dq1 = {0};
     const LaneBases lb = lane_bases_at(r, h, wave * DT_FLOATS * 4);
     const char* sm = reinterpret_cast<const char*>(smem);
@@ -242,7 +197,7 @@ __device__ __forceinline__ void attn_dkdv_tail_body(float* smem, float* ssm, con
     const float* dob = d_o + obase;
     const float* lrow = lse2 + ((int64_t)b * g.H + hd) * g.T;
     const float* drow = delta + ((int64_t)b * g.H + hd) * g.T;
-    const float* scol = sres + sres_block(g, NB, b, hd, 0, NB - 1);
+    const float* scol = sres + attn_score_block(g.H, NB, b, hd, 0, NB - 1);
     const int64_t sstep = (int64_t)NB * SB_FLOATS;
     float* tl = smem + wave * DT_FLOATS;                   // dO tile, then Q tile
     float* sw = ssm + wave * 2 * SB_FLOATS;                // [score block | lse2 x 32, delta x 32]
@@ -284,11 +239,7 @@ __device__ __forceinline__ void attn_dkdv_tail_body(float* smem, float* ssm, con
         f32x16 s;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) s[reg] = *reinterpret_cast<const float*>(ssb + tb[reg & 3] + 128 * (reg >> 2));
-        if (q0 + 32 > g.T) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (q0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
+        ATTN_MASK_ROWS(s, q0, g.T, h);
         f32x16 p, ds;
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {

@@ -209,8 +209,7 @@ __device__ __forceinline__ LaneBases lane_bases_at(int r, int h, int byte_off) {
 // in front of the next LDS load builtin -- in every step of the sweeps the wave then waited for the tile it had just sent for
 // (found in the ISA while building attn_f32_x3.hip; the resident-score sweeps had carried it since round 3: their "DMA issue +
 // loads" phase, profiles/r03_attn_bwd_phases.txt).  Reads written as inline asm are invisible to that pass; each carries its own
-// counted lgkmcnt wait (LDS operations of a wave return in order: "at most n outstanding" = "all but my n newest have landed";
-// operations the compiler adds only make a wait stricter).  Addresses are LDS byte addresses (tile base included).
+// counted lgkmcnt wait (ACR_LDS_RD128 / ACR_LDS_WAIT4 ..., acr_common.h).  Addresses are LDS byte addresses (tile base included).
 struct LaneBasesA { uint32_t rowb[8]; uint32_t colb[4]; };
 __device__ __forceinline__ uint32_t lds_addr_of(const void* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
@@ -225,10 +224,6 @@ __device__ __forceinline__ LaneBasesA lane_bases_a(int r, int h, const void* sm)
     for (int c = 0; c < 4; ++c) la.colb[c] = b + lb.colb[c];
     return la;
 }
-#define ACR_LDS_RD128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
-#define ACR_LDS_RD32(dst, addr, OFF) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "i"(OFF))
-#define ACR_LDS_WAIT4(cnt, a, b, c, d) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-#define ACR_LDS_WAIT1(cnt, a) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(a))
 
 // acc[reg] += sum_d tile[krow(reg,h)][d] * Y[l&31][d]: four 16-byte reads in flight ahead of the MFMAs that consume them
 template <int TILE_OFF>

@@ -26,40 +26,18 @@
 
 #include "acr_split.h"
 #include "attn_f32.h"
+#include "attn_f32_scores.h"
 #include "attn_f32_sres_tails.h"
 
 typedef __bf16 bf16_t;
-typedef __attribute__((address_space(3))) void* x3_lds_vp;
-typedef const __attribute__((address_space(1))) void* x3_glb_vp;
 
 #define X3_PLANE_B (32 * 64 * 2)           // bytes of one plane image of a 32-row x 64-column tile
 #define X3_TILE_B (3 * X3_PLANE_B)         // one operand tile: three planes
 #define X3_SLOT_B (2 * X3_TILE_B)          // one ring slot: two operand tiles
-#define X3_SB_FLOATS 1024                  // one 32 x 32 score block (layout: attn_f32_sres.hip)
-
-#define X3_STORE_NT(p, v) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p))
-#define X3_LOAD_NT(p) __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p))
 
 
-// ---- counted waits ------------------------------------------------------------------------------------------------------------
-// A step's tile DMA must have landed at the step's barrier, but the streams that run further ahead (score blocks two steps
-// ahead, G one step, the forward's score stores) are YOUNGER vector-memory operations and may stay in flight: vmcnt retires in
-// issue order, so "at most n outstanding" with n = the number of younger operations is exactly "the tile has landed".  n is
-// wave-uniform; a count that is not listed waits for the next smaller one (stricter, never wrong).
-template <int N>
-__device__ __forceinline__ void x3_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void x3_wait_vm(int n) {
-    if (n >= 9) x3_vmcnt<9>();
-    else if (n >= 8) x3_vmcnt<8>();
-    else if (n >= 7) x3_vmcnt<7>();
-    else if (n >= 5) x3_vmcnt<5>();
-    else if (n >= 4) x3_vmcnt<4>();
-    else if (n >= 1) x3_vmcnt<1>();
-    else x3_vmcnt<0>();
-}
-// compiler-only fence: vector-memory operations written after it are issued after the ones before it (the counts above rely
-// on the issue order; loads from global memory and LDS-DMA writes do not alias, so nothing else orders them for the compiler)
-#define X3_FENCE() asm volatile("" ::: "memory")
+// counted waits (attn_f32_scores.h): the steps of this file ask for these counts of younger operations
+__device__ __forceinline__ void x3_wait_vm(int n) { attn_wait_vm<false, 9, 8, 7, 5, 4, 1>(n); }
 // acr_barrier_nofence (acr_common.h): __syncthreads()'s release fence made hipcc drain every outstanding DMA in front of the
 // barrier of every second step (`s_waitcnt vmcnt(0)`, found in the ISA) -- the counted wait above it is the synchronisation
 __device__ __forceinline__ void x3_barrier(int n_younger) {
@@ -135,7 +113,7 @@ __device__ __forceinline__ int x3_dma_off(int D, int wave, int lane) {         /
 __device__ __forceinline__ void x3_dma_tile_i(char* lds, const bf16_t* __restrict__ row0ptr, int64_t plane, int off, int wave) {
 #pragma unroll
     for (int p = 0; p < 3; ++p)
-        __builtin_amdgcn_global_load_lds((x3_glb_vp)(row0ptr + p * plane + off), (x3_lds_vp)(lds + p * X3_PLANE_B + wave * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_vp)(row0ptr + p * plane + off), (lds_vp)(lds + p * X3_PLANE_B + wave * 1024), 16, 0, 0);
 }
 // edge form: rows clamped to Tn - 1 (rows past the end alias the last valid one: finite, and every consumer masks them)
 __device__ __forceinline__ void x3_dma_tile(char* lds, const bf16_t* __restrict__ base, int64_t plane, int D, int row0, int Tn, int wave,
@@ -144,17 +122,14 @@ __device__ __forceinline__ void x3_dma_tile(char* lds, const bf16_t* __restrict_
     const bf16_t* src = base + (int64_t)min(row0 + row, Tn - 1) * D + (((lane & 7) ^ x3_swz(row)) << 3);
 #pragma unroll
     for (int p = 0; p < 3; ++p)
-        __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + p * plane), (x3_lds_vp)(lds + p * X3_PLANE_B + wave * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_vp)(src + p * plane), (lds_vp)(lds + p * X3_PLANE_B + wave * 1024), 16, 0, 0);
 }
 
 // ---- fragment addresses (LDS byte addresses of plane 0 of the tile at ring offset 0; lane-dependent part, computed once) -------
 struct X3Lane { uint32_t rowb[4]; uint32_t trb[2][2]; };
-__device__ __forceinline__ uint32_t x3_lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 __device__ __forceinline__ X3Lane x3_lane(int lane, const char* smem) {
     X3Lane lb;
-    const uint32_t lds0 = x3_lds_addr(smem);
+    const uint32_t lds0 = lds_addr_of(smem);
     const int r = lane & 31, h = lane >> 5;
     const int fr = x3_swz(r);
 #pragma unroll
@@ -183,7 +158,7 @@ __device__ __forceinline__ X3Lane x3_lane(int lane, const char* smem) {
     asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(h_[0]), "+v"(h_[1]), "+v"(h_[2]))
 // rows of the tile as an MFMA operand: element j of lane (r, h) = tile[r][16 S + 8 h + j], planes 0..2
 #define X3_ROWFRAG(a, lb, TOFF, S) \
-    { IMG_RD128(a[0], lb.rowb[S], TOFF); IMG_RD128(a[1], lb.rowb[S], (TOFF) + X3_PLANE_B); IMG_RD128(a[2], lb.rowb[S], (TOFF) + 2 * X3_PLANE_B); }
+    { ACR_LDS_RD128(a[0], lb.rowb[S], TOFF); ACR_LDS_RD128(a[1], lb.rowb[S], (TOFF) + X3_PLANE_B); ACR_LDS_RD128(a[2], lb.rowb[S], (TOFF) + 2 * X3_PLANE_B); }
 // the tile transposed: element j of lane (r, h) = tile[16 S + 8 (j >> 2) + 4 h + (j & 3)][32 BLK + r] (lo: j < 4, hi: j >= 4)
 #define X3_TRFRAG(l, h_, lb, TOFF, S, BLK)                                                      \
     { X3_RDTR(l[0], h_[0], lb.trb[0][BLK], lb.trb[1][BLK], (TOFF) + (S) * 2048);                 \
@@ -279,10 +254,6 @@ __device__ __forceinline__ void x3_rows_from_global(bf16x8 (&y)[3][4], const bf1
         for (int s = 0; s < 4; ++s) y[p][s] = *reinterpret_cast<const bf16x8*>(p0 + p * plane + 16 * s);
 }
 
-__device__ __forceinline__ int64_t x3_block(int H, int NB, int b, int hd, int qb, int kb) {
-    return ((((int64_t)b * H + hd) * NB + qb) * NB + kb) * X3_SB_FLOATS;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // forward: workgroup = (b, h, 128 queries), wave = 32 queries; K / V tile planes stream through a two-slot LDS ring; every
 // 32 x 32 logit tile is written to `sres` (scaled base-2 logits, keys >= T = -inf) before the softmax consumes it
@@ -325,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
     const X3Lane lb = x3_lane(lane, smem);
     const int doff = x3_dma_off(g.D, wave, lane);
     const float c2 = g.scale * ACR_LOG2E;
-    float* sblk = sres + x3_block(g.H, NB, b, hd, min(q0 >> 5, NB - 1), 0) + lane * 4;
+    float* sblk = sres + attn_score_block(g.H, NB, b, hd, min(q0 >> 5, NB - 1), 0) + lane * 4;
     auto step = [&](int k0, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
         constexpr int KOFF = SLOT * X3_SLOT_B, VOFF = KOFF + X3_TILE_B;
@@ -334,7 +305,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
         auto dma_next = [&](const bf16_t* base, int toff) {
             if (k0 + 64 <= g.T) x3_dma_tile_i(smem + (SLOT ^ 1) * X3_SLOT_B + toff, base + (int64_t)(k0 + 32) * g.D, g.plane, doff, wave);
             else if (k0 + 32 < g.T) x3_dma_tile(smem + (SLOT ^ 1) * X3_SLOT_B + toff, base, g.plane, g.D, k0 + 32, g.T, wave, lane);
-            X3_FENCE();
+            ATTN_FENCE();
         };
         if (!live) {                                       // waves past the end only help with the DMA
             dma_next(kb, 0);
@@ -345,34 +316,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
         x3_rowop<KOFF>(s, lb, qf, [&] { dma_next(kb, 0); }, [&] { dma_next(vb, X3_TILE_B); });      // s[reg] = q.k of key k0 + krow, query q0 + r
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) s[reg] *= c2;   // scaled base-2 logits
-        if (k0 + 32 > g.T) {                               // only the last key tile has keys beyond T (uniform branch)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (k0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
-        float* sp = sblk + (int64_t)(k0 >> 5) * X3_SB_FLOATS;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {                   // (kept out of the second product's fillers: 16 more live registers
-            const f32x4 t = {s[4 * gq], s[4 * gq + 1], s[4 * gq + 2], s[4 * gq + 3]};      //  cost the third wave per SIMD)
-            X3_STORE_NT(sp + gq * 256, t);
-        }
-        float mx = s[0];
-#pragma unroll
-        for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, s[reg]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        if (__any(mx > m + 8.f)) {                         // deferred rescale (attn_f32_dma.hip)
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);
-            l *= alpha;
-            o0 *= alpha; o1 *= alpha;
-            m = mn;
-        }
-        float rs = 0.f;
+        ATTN_MASK_ROWS(s, k0, g.T, h);
+        // (the score stores are kept out of the second product's fillers: 16 more live registers cost the third wave per SIMD)
+        attn_store_scores(sblk + (int64_t)(k0 >> 5) * SB_FLOATS, s);
         f32x16 p;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) { p[reg] = __builtin_amdgcn_exp2f(s[reg] - m); rs += p[reg]; }
-        rs += __shfl_xor(rs, 32);
-        l += rs;
+        ATTN_SOFTMAX_STEP(s, m, l, o0, o1, p);
         bf16x8 p0[3], p1[3];
         split3_bf16_acc<0>(p, p0);
         x3_accop<VOFF, false>(o0, o1, p0, p1, lb, [&] { split3_bf16_acc<1>(p, p1); });      // o[reg] = O^T[d = 32*blk + krow][query = r]
@@ -383,15 +331,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(X3Geom g, const bf1
     }
     if (live && q0 + r < g.T) {
         const float inv = 1.f / l;
-        float* ob = o + (int64_t)b * g.osb + (int64_t)(q0 + r) * g.ost + (int64_t)hd * g.osh;
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-            f32x4 a = {o0[4 * grp] * inv, o0[4 * grp + 1] * inv, o0[4 * grp + 2] * inv, o0[4 * grp + 3] * inv};
-            f32x4 c = {o1[4 * grp] * inv, o1[4 * grp + 1] * inv, o1[4 * grp + 2] * inv, o1[4 * grp + 3] * inv};
-            *reinterpret_cast<f32x4*>(ob + 8 * grp + 4 * h) = a;
-            *reinterpret_cast<f32x4*>(ob + 32 + 8 * grp + 4 * h) = c;
-        }
-        if (h == 0) lse2[((int64_t)b * g.H + hd) * g.T + q0 + r] = m + log2f(l);
+        ATTN_FWD_FINISH(g, o, lse2, b, hd, q0, r, h, o0, o1, m, l, inv);
         // The output as the NEXT product's split-product image (proj reads o as [token][feature] rows; include/acr_hip.h "split-product
         // images"): row = b T + query of the (B T) x D matrix, this head's 64 features = 8 chunks of 8.  Lane (r, h) holds features
         // 8 grp + 4 h .. + 3 of each quad: the two halves of a chunk sit in lanes (r, 0) and (r, 1), so the pair swaps one quad per two
@@ -477,33 +417,7 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
     const int op = wave >> 2, pc = wave & 3;               // this wave's share of the tile DMA: operand (K | V), 8-row piece
     const bf16_t* tb = (op ? vp : kp) + pbase;
     char* tdst = smem + op * X3_TILE_B;
-    // score blocks of this wave: (qb = q0 / 32, kb = step), copied as stored (lane l of piece gq owns floats gq*256 + 4 l ..)
-    const float* srow = sres + x3_block(g.H, NB, b, hd, min(q0 >> 5, NB - 1), 0) + lane * 4;
-    float* sw = ssm + wave * 2 * X3_SB_FLOATS;
-    auto dma_scores = [&](int kblk, int slot) {
-        const float* src = srow + (int64_t)kblk * X3_SB_FLOATS;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + gq * 256), (x3_lds_vp)(sw + slot * X3_SB_FLOATS + gq * 256), 16, 0, 0);
-    };
-    // G block of the step: rows = this wave's 32 queries (fixed), 128 bytes = the step's 32 keys; 16-byte chunk c of row q is
-    // stored in slot c ^ ((q >> 1) & 7) (the lane's row reads are then bank-conflict free); columns clamped into the row
-    const float* gb0 = gm ? gm + (int64_t)b * gm_sb : nullptr;          // uniform
-    float* gw = gsm + wave * X3_SB_FLOATS;
-    const float* grow[4];
-    int gchunk[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int row = 8 * p + (lane >> 3);
-        grow[p] = gb0 ? gb0 + (int64_t)min(q0 + row, g.T - 1) * gm_st : nullptr;
-        gchunk[p] = 4 * ((lane & 7) ^ ((row >> 1) & 7));
-    }
-    auto dma_g = [&](int k0) {
-        if (gb0 == nullptr) return;
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-            __builtin_amdgcn_global_load_lds((x3_glb_vp)(grow[p] + min(k0 + gchunk[p], (int)gm_st - 4)), (x3_lds_vp)(gw + p * 256), 16, 0, 0);
-    };
+    ATTN_QLANE_STREAMS(sres, g.H, NB, g.T, b, hd, q0, wave, lane, ssm, gsm, gm, gm_sb, gm_st);      // this wave's private streams
     x3_dma_tile(tdst, tb, g.plane, g.D, 0, g.T, pc, lane);
     if (live) {
         dma_g(0);
@@ -519,10 +433,7 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
     f32x16 dq0 = {0}, dq1 = {0};
     const X3Lane lb = x3_lane(lane, smem);
     const int doff = x3_dma_off(g.D, pc, lane);
-    const uint32_t saddr = x3_lds_addr(sw) + lane * 16;                                 // + slot * X3_SB_FLOATS * 4 + gq * 1024
-    uint32_t gaddr[4];                                                                  // quad gq = keys 8 gq + 4 h .. + 3 of row r
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) gaddr[gq] = x3_lds_addr(gw) + r * 128 + (((2 * gq + h) ^ ((r >> 1) & 7)) << 4);
+    ATTN_QLANE_ADDRS(lane, r, h);
     auto step = [&](int k0, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
         constexpr int KOFF = SLOT * X3_SLOT_B, VOFF = KOFF + X3_TILE_B;
@@ -532,7 +443,7 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
         auto dma_next = [&] {                              // this wave's three pieces of tile(t+1)
             if (k0 + 64 <= g.T) x3_dma_tile_i(tdst + (SLOT ^ 1) * X3_SLOT_B, tb + (int64_t)(k0 + 32) * g.D, g.plane, doff, pc);
             else if (k0 + 32 < g.T) x3_dma_tile(tdst + (SLOT ^ 1) * X3_SLOT_B, tb, g.plane, g.D, k0 + 32, g.T, pc, lane);
-            X3_FENCE();
+            ATTN_FENCE();
         };
         if (!live) { dma_next(); return; }
         f32x16 dp = {0};
@@ -541,35 +452,17 @@ __device__ __forceinline__ void attn_dq_x3_body(char* smem, float* ssm, float* g
         // tile(t+1) [3].  The score block (t) is older than it.
         if (k0 > 0) x3_wait_vm(k0 + 32 < g.T ? 7 : 0);
         f32x4 s4[4], g4[4];
-        IMG_RD128(s4[0], saddr, SLOT * X3_SB_FLOATS * 4); IMG_RD128(s4[1], saddr, SLOT * X3_SB_FLOATS * 4 + 1024);
-        IMG_RD128(s4[2], saddr, SLOT * X3_SB_FLOATS * 4 + 2048); IMG_RD128(s4[3], saddr, SLOT * X3_SB_FLOATS * 4 + 3072);
-        if (gb0 != nullptr) {
-            IMG_RD128(g4[0], gaddr[0], 0); IMG_RD128(g4[1], gaddr[1], 0); IMG_RD128(g4[2], gaddr[2], 0); IMG_RD128(g4[3], gaddr[3], 0);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(g4[0]), "+v"(g4[1]), "+v"(g4[2]), "+v"(g4[3]));
-            if (k0 + 32 > g.T) {                           // keys beyond T: their columns hold whatever the row pitch holds
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (k0 + 8 * gq + 4 * h + e >= g.T) g4[gq][e] = 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) g4[gq] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s4[0]), "+v"(s4[1]), "+v"(s4[2]), "+v"(s4[3]));
+        ATTN_QLANE_READ(SLOT, s4, g4, k0, g.T, h);
         f32x16 ds;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg)
-            ds[reg] = __builtin_amdgcn_exp2f(s4[reg >> 2][reg & 3] - l2q) * (dp[reg] + g4[reg >> 2][reg & 3] * invH - dl);
+        attn_ds_qlane(ds, s4, g4, dp, l2q, dl, invH);
         // the private tiles have been read: G is refilled for the next step and the score slot for the step AFTER next -- between
         // the MFMA groups of the second product, like the second half of the split
         bf16x8 z0[3], z1[3];
         split3_bf16_acc<0>(ds, z0);
         x3_accop<KOFF, true>(dq0, dq1, z0, z1, lb,          // dQ[query = krow][d = 32*blk + r]
                              [&] { split3_bf16_acc<1>(ds, z1); },
-                             [&] { if (k0 + 32 < g.T) dma_g(k0 + 32); X3_FENCE(); },
-                             [&] { if (k0 + 64 < g.T) dma_scores((k0 >> 5) + 2, SLOT); X3_FENCE(); });
+                             [&] { if (k0 + 32 < g.T) dma_g(k0 + 32); ATTN_FENCE(); },
+                             [&] { if (k0 + 64 < g.T) dma_scores((k0 >> 5) + 2, SLOT); ATTN_FENCE(); });
     };
     for (int k0 = 0; k0 < g.T; k0 += 64) {
         step(k0, std::integral_constant<int, 0>{});
@@ -617,37 +510,12 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
     char* tdst = smem + op * X3_TILE_B;
     const float* lrow = lse2 + ((int64_t)b * g.H + hd) * g.T;
     const float* drow = delta + ((int64_t)b * g.H + hd) * g.T;
-    // score blocks of this wave: (qb = step, kb = key0 / 32); lane c of DMA piece gq fetches global chunk c ^ (2 gq + (c >> 5))
-    const float* scol = sres + x3_block(g.H, NB, b, hd, 0, min(key0 >> 5, NB - 1));
-    const int64_t sstep = (int64_t)NB * X3_SB_FLOATS;
-    int soff[4];
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) soff[gq] = gq * 256 + 4 * (lane ^ (2 * gq + (lane >> 5)));
-    float* sw = ssm + wave * 2 * X3_SB_FLOATS;
-    auto dma_scores = [&](int qblk, int slot) {
-        const float* src = scol + (int64_t)qblk * sstep;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + soff[gq]), (x3_lds_vp)(sw + slot * X3_SB_FLOATS + gq * 256), 16, 0, 0);
-    };
-    // G block of the step: rows = the 32 queries, 128 bytes = this wave's 32 keys.  Columns are clamped into the row (the last
-    // key block reaches beyond T: those lanes' P is exactly 0 and whatever they compute never leaves their own accumulator row).
-    const float* gb0 = gm ? gm + (int64_t)b * gm_sb : nullptr;          // uniform
-    float* gw = gsm + wave * X3_SB_FLOATS;
-    const int gcol = min(key0 + 4 * (lane & 7), (int)gm_st - 4);
-    auto dma_g = [&](int q0) {
-        if (gb0 == nullptr) return;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const float* src = gb0 + (int64_t)min(q0 + 8 * p + (lane >> 3), g.T - 1) * gm_st + gcol;
-            __builtin_amdgcn_global_load_lds((x3_glb_vp)src, (x3_lds_vp)(gw + p * 256), 16, 0, 0);
-        }
-    };
+    ATTN_KLANE_STREAMS(sres, g.H, NB, g.T, b, hd, key0, wave, lane, ssm, gsm, gm, gm_sb, gm_st);   // this wave's private streams
     // lse2 (lanes 0-31) and delta (lanes 32-63) of the step's 32 queries: one 256-byte DMA into a private LDS row
     float* rcw = rcm + wave * 64;
     auto dma_rc = [&](int q0) {
         const float* src = (lane < 32 ? lrow : drow) + min(q0 + (lane & 31), g.T - 1);
-        __builtin_amdgcn_global_load_lds((x3_glb_vp)src, (x3_lds_vp)rcw, 4, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_vp)src, (lds_vp)rcw, 4, 0, 0);
     };
     x3_dma_tile(tdst, tb, g.plane, g.D, 0, g.T, pc, lane);
     if (live) {
@@ -662,16 +530,8 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
     f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
     const X3Lane lb = x3_lane(lane, smem);
     const int doff = x3_dma_off(g.D, pc, lane);
-    // transposed score reads: lane (kappa = r, h): LDS byte address = tb4[reg & 3] + slot * X3_SB_FLOATS * 4 + 128*(reg >> 2)
-    uint32_t tb4[4];
-    {
-        const int gk = r >> 3, hk = (r >> 2) & 1, ek = r & 3, mm = 2 * gk + hk;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            tb4[j] = x3_lds_addr(ssm) + ((wave * 2 * X3_SB_FLOATS) + gk * 256 + 128 * hk + ek + 4 * ((j + 4 * h) ^ mm)) * 4;
-    }
-    const uint32_t gaddr = x3_lds_addr(gsm) + (wave * X3_SB_FLOATS + 4 * h * 32 + r) * 4;      // + 128 * c_reg per register
-    const uint32_t rcaddr = x3_lds_addr(rcw) + 16 * h;                                          // l4[gq] at + 32 gq, d4[gq] at + 128 + 32 gq
+    ATTN_KLANE_ADDRS(ssm, gsm, wave, r, h);
+    const uint32_t rcaddr = lds_addr_of(rcw) + 16 * h;                                          // l4[gq] at + 32 gq, d4[gq] at + 128 + 32 gq
     auto step = [&](int q0, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
         constexpr int QOFF = SLOT * X3_SLOT_B, DOOFF = QOFF + X3_TILE_B;
@@ -682,7 +542,7 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
         auto dma_next = [&] {                              // this wave's three pieces of tile(t+1)
             if (q0 + 64 <= g.T) x3_dma_tile_i(tdst + (SLOT ^ 1) * X3_SLOT_B, tb + (int64_t)(q0 + 32) * g.D, g.plane, doff, pc);
             else if (q0 + 32 < g.T) x3_dma_tile(tdst + (SLOT ^ 1) * X3_SLOT_B, tb, g.plane, g.D, q0 + 32, g.T, pc, lane);
-            X3_FENCE();
+            ATTN_FENCE();
         };
         if (!live) { dma_next(); return; }
         f32x16 dp = {0};
@@ -690,34 +550,16 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
         // lse2-delta(t) and G(t) (issued in the previous step) must have landed in this wave's private tiles: behind them are
         // scores(t+1) [4] and this step's tile(t+1) [3].  The score block (t) is older than both: it has landed with them.
         if (q0 > 0) x3_wait_vm(q0 + 32 < g.T ? 7 : 0);
-        // this wave's private tiles, read by inline asm (see IMG_RD128): score block transposed, G block, lse2 | delta
+        // this wave's private tiles, read by inline asm (see ACR_LDS_RD128): score block transposed, G block, lse2 | delta
         float s[16], gv[16];
         f32x4 l4[4], d4[4];
-#define X3_RDS(REG) IMG_RD32(s[REG], tb4[(REG) & 3], SLOT * X3_SB_FLOATS * 4 + 128 * ((REG) >> 2))
-#define X3_RDG(REG) IMG_RD32(gv[REG], gaddr, 128 * (((REG) & 3) + 8 * ((REG) >> 2)))
-        X3_RDS(0); X3_RDS(1); X3_RDS(2); X3_RDS(3); X3_RDS(4); X3_RDS(5); X3_RDS(6); X3_RDS(7);
-        X3_RDS(8); X3_RDS(9); X3_RDS(10); X3_RDS(11); X3_RDS(12); X3_RDS(13); X3_RDS(14); X3_RDS(15);
-        IMG_RD128(l4[0], rcaddr, 0); IMG_RD128(l4[1], rcaddr, 32); IMG_RD128(l4[2], rcaddr, 64); IMG_RD128(l4[3], rcaddr, 96);
-        IMG_RD128(d4[0], rcaddr, 128); IMG_RD128(d4[1], rcaddr, 160); IMG_RD128(d4[2], rcaddr, 192); IMG_RD128(d4[3], rcaddr, 224);
-        if (gb0 != nullptr) {
-            X3_RDG(0); X3_RDG(1); X3_RDG(2); X3_RDG(3); X3_RDG(4); X3_RDG(5); X3_RDG(6); X3_RDG(7);
-            X3_RDG(8); X3_RDG(9); X3_RDG(10); X3_RDG(11); X3_RDG(12); X3_RDG(13); X3_RDG(14); X3_RDG(15);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(gv[0]), "+v"(gv[1]), "+v"(gv[2]), "+v"(gv[3]), "+v"(gv[4]), "+v"(gv[5]), "+v"(gv[6]),
-                         "+v"(gv[7]), "+v"(gv[8]), "+v"(gv[9]), "+v"(gv[10]), "+v"(gv[11]), "+v"(gv[12]), "+v"(gv[13]), "+v"(gv[14]), "+v"(gv[15]));
-        } else {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) gv[reg] = 0.f;
-        }
-#undef X3_RDS
-#undef X3_RDG
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]),
-                     "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15]), "+v"(l4[0]),
-                     "+v"(l4[1]), "+v"(l4[2]), "+v"(l4[3]), "+v"(d4[0]), "+v"(d4[1]), "+v"(d4[2]), "+v"(d4[3]));
-        if (q0 + 32 > g.T) {                               // last query block: rows beyond T are junk, P = 0 there
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                if (q0 + acr_krow(reg, h) >= g.T) s[reg] = -INFINITY;
-        }
+        ATTN_16(ATTN_RDS, s, SLOT);
+        ACR_LDS_RD128(l4[0], rcaddr, 0); ACR_LDS_RD128(l4[1], rcaddr, 32); ACR_LDS_RD128(l4[2], rcaddr, 64); ACR_LDS_RD128(l4[3], rcaddr, 96);
+        ACR_LDS_RD128(d4[0], rcaddr, 128); ACR_LDS_RD128(d4[1], rcaddr, 160); ACR_LDS_RD128(d4[2], rcaddr, 192); ACR_LDS_RD128(d4[3], rcaddr, 224);
+        ATTN_READ_G(gv)
+        asm volatile("s_waitcnt lgkmcnt(0)" : ATTN_V16(s), "+v"(l4[0]), "+v"(l4[1]), "+v"(l4[2]), "+v"(l4[3]), "+v"(d4[0]), "+v"(d4[1]), "+v"(d4[2]), "+v"(d4[3]));
+        ATTN_MASK_ROWS(s, q0, g.T, h);                     // last query block: rows beyond T are junk, P = 0 there
+        // P / dS stay this body's own: lse2 / delta come from the DMA'd LDS row as l4 / d4 (attn_f32_sres.hip spreads them with __shfl)
         f32x16 p, ds;
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {                   // krow(4 gq + e, h) = 8 gq + 4 h + e: four consecutive queries
@@ -736,12 +578,12 @@ __device__ __forceinline__ void attn_dkdv_x3_body(char* smem, float* ssm, float*
         split3_bf16_acc<0>(p, z0);
         x3_accop<DOOFF, true>(dv0, dv1, z0, z1, lb,
                               [&] { split3_bf16_acc<1>(p, z1); },
-                              [&] { if (q0 + 32 < g.T) dma_rc(q0 + 32); X3_FENCE(); },
-                              [&] { if (q0 + 32 < g.T) dma_g(q0 + 32); X3_FENCE(); });
+                              [&] { if (q0 + 32 < g.T) dma_rc(q0 + 32); ATTN_FENCE(); },
+                              [&] { if (q0 + 32 < g.T) dma_g(q0 + 32); ATTN_FENCE(); });
         split3_bf16_acc<0>(ds, z0);
         x3_accop<QOFF, true>(dk0, dk1, z0, z1, lb,
                              [&] { split3_bf16_acc<1>(ds, z1); },
-                             [&] { if (q0 + 64 < g.T) dma_scores((q0 >> 5) + 2, SLOT); X3_FENCE(); });
+                             [&] { if (q0 + 64 < g.T) dma_scores((q0 >> 5) + 2, SLOT); ATTN_FENCE(); });
     };
     for (int q0 = 0; q0 < g.T; q0 += 64) {
         step(q0, std::integral_constant<int, 0>{});
@@ -779,11 +621,11 @@ __global__ __launch_bounds__(64 * X3_BW, 2) void attn_bwd_x3_kernel(X3Geom g, co
                                                                    AttnGeom g32, int ntail) {
     // one LDS block, carved: [slot][Q | dO planes] resp. [slot][K | V planes] (48 KB) | [wave][slot] score blocks (64 KB) | [wave] G
     // block (32 KB) | [wave][lse2 x 32 | delta x 32] (2 KB); the split tails use the first 128 KB as 8 tile images + 8 score blocks
-    __shared__ __attribute__((aligned(1024))) char lds[2 * X3_SLOT_B + X3_BW * 3 * X3_SB_FLOATS * 4 + X3_BW * 256];
+    __shared__ __attribute__((aligned(1024))) char lds[2 * X3_SLOT_B + X3_BW * 3 * SB_FLOATS * 4 + X3_BW * 256];
     char* smem = lds;
     float* ssm = reinterpret_cast<float*>(lds + 2 * X3_SLOT_B);
-    float* gsm = ssm + X3_BW * 2 * X3_SB_FLOATS;
-    float* rcm = gsm + X3_BW * X3_SB_FLOATS;
+    float* gsm = ssm + X3_BW * 2 * SB_FLOATS;
+    float* rcm = gsm + X3_BW * SB_FLOATS;
     const int half = ((int)gridDim.x - 2 * ntail) >> 1;
     const int bid = (int)blockIdx.x;
     if (bid < half)
@@ -801,18 +643,12 @@ __global__ __launch_bounds__(64 * X3_BW, 2) void attn_bwd_x3_kernel(X3Geom g, co
 // ---------------------------------------------------------------------------------------------------------------------------------
 // launchers (called from attn_f32.hip)
 // ---------------------------------------------------------------------------------------------------------------------------------
-static int64_t x3_score_floats(const AttnGeom& g) {
-    const int64_t nb = (g.T + 31) / 32;
-    return (int64_t)g.B * g.H * nb * nb * X3_SB_FLOATS;
-}
 int64_t acr_attn_x3_scores_floats(const AttnGeom& g) {                  // score blocks + the 9 planes of q, k, v
-    return x3_score_floats(g) + 9 * ((int64_t)g.B * g.T * g.H * 64) / 2;
+    return attn_score_floats(g.B, g.H, g.T) + 9 * ((int64_t)g.B * g.T * g.H * 64) / 2;
 }
 int64_t acr_attn_x3_bwd_ws_floats(const AttnGeom& g) {                  // delta (rounded to 16 bytes) + the 3 planes of dO
     return (((int64_t)g.B * g.H * g.T + 3) & ~(int64_t)3) + 3 * ((int64_t)g.B * g.T * g.H * 64) / 2;
 }
-// one leftover 32-row block beyond a whole number of workgroups (nw blocks each), and at least one full workgroup
-static bool x3_split_tail(int NB, int nw) { return (NB % nw) == 1 && NB > nw; }
 static X3Geom x3_geom(const AttnGeom& g) {
     X3Geom x;
     x.B = g.B; x.H = g.H; x.T = g.T; x.D = g.H * 64; x.scale = g.scale;
@@ -826,13 +662,13 @@ static X3Geom x3_geom(const AttnGeom& g) {
 // the tail bodies write fp32 o only)
 bool acr_attn_x3_fwd_uses_split_tail(int T) {
     const int NB = (T + 31) / 32;
-    return x3_split_tail(NB, 4) && NB >= 33;
+    return attn_split_tail(NB, 4) && NB >= 33;
 }
 
 void acr_attn_fwd_f32_x3(const AttnGeom& g, const float* q, const float* k, const float* v, float* o, float* lse2, float* scores,
                          float* pmean, int64_t pmean_sb, int64_t pmean_st, hipStream_t st, char* oimg) {
     const X3Geom x = x3_geom(g);
-    bf16_t* planes = reinterpret_cast<bf16_t*>(scores + x3_score_floats(g));
+    bf16_t* planes = reinterpret_cast<bf16_t*>(scores + attn_score_floats(g.B, g.H, g.T));
     X3SplitArgs a;
     a.src[0] = q; a.src[1] = k; a.src[2] = v;
     a.sb = g.sb; a.st = g.st; a.sh = g.sh; a.dst = planes; a.plane = x.plane; a.B = g.B; a.T = g.T; a.H = g.H;
@@ -853,7 +689,7 @@ void acr_attn_bwd_f32_x3(const AttnGeom& g, const float* q, const float* k, cons
                          const float* lse2, const float* scores, const float* gm, int64_t gm_sb, int64_t gm_st, float* dq, float* dk,
                          float* dv, float* delta_ws, hipStream_t st) {
     const X3Geom x = x3_geom(g);
-    const bf16_t* planes = reinterpret_cast<const bf16_t*>(scores + x3_score_floats(g));
+    const bf16_t* planes = reinterpret_cast<const bf16_t*>(scores + attn_score_floats(g.B, g.H, g.T));
     bf16_t* dop = reinterpret_cast<bf16_t*>(delta_ws + (((int64_t)g.B * g.H * g.T + 3) & ~(int64_t)3));
     X3SplitArgs a;
     a.src[0] = d_o; a.src[1] = a.src[2] = nullptr;
@@ -862,7 +698,7 @@ void acr_attn_bwd_f32_x3(const AttnGeom& g, const float* q, const float* k, cons
     hipLaunchKernelGGL(x3_split_kernel, dim3((unsigned)((n8 + 255) / 256), 1), dim3(256), 0, st, a);
     acr_attn_delta_sres(g, scores, o, d_o, lse2, gm, gm_sb, gm_st, delta_ws, st);
     const int NB = (g.T + 31) / 32;
-    const int ntail = x3_split_tail(NB, X3_BW) ? g.B * g.H : 0;
+    const int ntail = attn_split_tail(NB, X3_BW) ? g.B * g.H : 0;
     const int nmain = g.B * g.H * (ntail ? NB / X3_BW : (NB + X3_BW - 1) / X3_BW);
     hipLaunchKernelGGL(attn_bwd_x3_kernel, dim3(2 * nmain + 2 * ntail), dim3(64 * X3_BW), 0, st, x, planes, planes + 3 * x.plane,
                        planes + 6 * x.plane, (const bf16_t*)dop, lse2, (const float*)delta_ws, scores, gm, gm_sb, gm_st, dq, dk, dv, q, k, v, d_o, g,

@@ -74,13 +74,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_wimg_kernel(const GemmF32Args
         // stage st: the B fragments raw (fp32, 8 k of one pixel per lane), the A fragments as planes
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            IMG_RD32(rb[j][0], fbs, 0 * F_BN * 4 + j * 128); IMG_RD32(rb[j][1], fbs, 1 * F_BN * 4 + j * 128); IMG_RD32(rb[j][2], fbs, 2 * F_BN * 4 + j * 128);
-            IMG_RD32(rb[j][3], fbs, 3 * F_BN * 4 + j * 128); IMG_RD32(rb[j][4], fbs, 4 * F_BN * 4 + j * 128); IMG_RD32(rb[j][5], fbs, 5 * F_BN * 4 + j * 128);
-            IMG_RD32(rb[j][6], fbs, 6 * F_BN * 4 + j * 128); IMG_RD32(rb[j][7], fbs, 7 * F_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][0], fbs, 0 * F_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][1], fbs, 1 * F_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][2], fbs, 2 * F_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][3], fbs, 3 * F_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][4], fbs, 4 * F_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][5], fbs, 5 * F_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][6], fbs, 6 * F_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][7], fbs, 7 * F_BN * 4 + j * 128);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            IMG_RD128(ap[SET][i][0], fas, 0 * IMG_PLANE_B + i * 1024); IMG_RD128(ap[SET][i][1], fas, 1 * IMG_PLANE_B + i * 1024); IMG_RD128(ap[SET][i][2], fas, 2 * IMG_PLANE_B + i * 1024);
+            ACR_LDS_RD128(ap[SET][i][0], fas, 0 * IMG_PLANE_B + i * 1024); ACR_LDS_RD128(ap[SET][i][1], fas, 1 * IMG_PLANE_B + i * 1024); ACR_LDS_RD128(ap[SET][i][2], fas, 2 * IMG_PLANE_B + i * 1024);
         }
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]), "+v"(rb[0][4]), "+v"(rb[0][5]), "+v"(rb[0][6]),
                      "+v"(rb[0][7]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3]), "+v"(rb[1][4]), "+v"(rb[1][5]), "+v"(rb[1][6]), "+v"(rb[1][7]));
@@ -179,14 +179,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_wimg64_kernel(const GemmF32Ar
         const uint32_t fas = fa + slot * W64_STAGE_B, fbs = fb + slot * W64_STAGE_B;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            IMG_RD32(rb[j][0], fbs, 0 * W64_BN * 4 + j * 128); IMG_RD32(rb[j][1], fbs, 1 * W64_BN * 4 + j * 128);
-            IMG_RD32(rb[j][2], fbs, 2 * W64_BN * 4 + j * 128); IMG_RD32(rb[j][3], fbs, 3 * W64_BN * 4 + j * 128);
-            IMG_RD32(rb[j][4], fbs, 4 * W64_BN * 4 + j * 128); IMG_RD32(rb[j][5], fbs, 5 * W64_BN * 4 + j * 128);
-            IMG_RD32(rb[j][6], fbs, 6 * W64_BN * 4 + j * 128); IMG_RD32(rb[j][7], fbs, 7 * W64_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][0], fbs, 0 * W64_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][1], fbs, 1 * W64_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][2], fbs, 2 * W64_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][3], fbs, 3 * W64_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][4], fbs, 4 * W64_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][5], fbs, 5 * W64_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][6], fbs, 6 * W64_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][7], fbs, 7 * W64_BN * 4 + j * 128);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            IMG_RD128(ap[SET][i][0], fas, 0 * 2048 + i * 1024); IMG_RD128(ap[SET][i][1], fas, 1 * 2048 + i * 1024); IMG_RD128(ap[SET][i][2], fas, 2 * 2048 + i * 1024);
+            ACR_LDS_RD128(ap[SET][i][0], fas, 0 * 2048 + i * 1024); ACR_LDS_RD128(ap[SET][i][1], fas, 1 * 2048 + i * 1024); ACR_LDS_RD128(ap[SET][i][2], fas, 2 * 2048 + i * 1024);
         }
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]), "+v"(rb[0][4]), "+v"(rb[0][5]), "+v"(rb[0][6]),
                      "+v"(rb[0][7]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3]), "+v"(rb[1][4]), "+v"(rb[1][5]), "+v"(rb[1][6]), "+v"(rb[1][7]));

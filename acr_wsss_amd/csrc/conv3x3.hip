@@ -318,15 +318,15 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg_kerne
         const uint32_t fas = fa + slot * C3W_STAGE_B, fbs = fb + slot * C3W_STAGE_B;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            IMG_RD32(rb[j][0], fbs, 0 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][1], fbs, 1 * C3_BN * 4 + j * 128);
-            IMG_RD32(rb[j][2], fbs, 2 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][3], fbs, 3 * C3_BN * 4 + j * 128);
-            IMG_RD32(rb[j][4], fbs, 4 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][5], fbs, 5 * C3_BN * 4 + j * 128);
-            IMG_RD32(rb[j][6], fbs, 6 * C3_BN * 4 + j * 128); IMG_RD32(rb[j][7], fbs, 7 * C3_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][0], fbs, 0 * C3_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][1], fbs, 1 * C3_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][2], fbs, 2 * C3_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][3], fbs, 3 * C3_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][4], fbs, 4 * C3_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][5], fbs, 5 * C3_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][6], fbs, 6 * C3_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][7], fbs, 7 * C3_BN * 4 + j * 128);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            IMG_RD128(ap[SET][i][0], fas, 0 * IMG_PLANE_B + i * 1024); IMG_RD128(ap[SET][i][1], fas, 1 * IMG_PLANE_B + i * 1024);
-            IMG_RD128(ap[SET][i][2], fas, 2 * IMG_PLANE_B + i * 1024);
+            ACR_LDS_RD128(ap[SET][i][0], fas, 0 * IMG_PLANE_B + i * 1024); ACR_LDS_RD128(ap[SET][i][1], fas, 1 * IMG_PLANE_B + i * 1024);
+            ACR_LDS_RD128(ap[SET][i][2], fas, 2 * IMG_PLANE_B + i * 1024);
         }
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]), "+v"(rb[0][4]), "+v"(rb[0][5]), "+v"(rb[0][6]),
                      "+v"(rb[0][7]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3]), "+v"(rb[1][4]), "+v"(rb[1][5]), "+v"(rb[1][6]), "+v"(rb[1][7]));
@@ -458,15 +458,15 @@ template <bool TAB> __global__ __launch_bounds__(256, 2) void conv3x3_wimg64_ker
         const uint32_t fas = fa + slot * C3N_STAGE_B, fbs = fb + slot * C3N_STAGE_B;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            IMG_RD32(rb[j][0], fbs, 0 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][1], fbs, 1 * C3N_BN * 4 + j * 128);
-            IMG_RD32(rb[j][2], fbs, 2 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][3], fbs, 3 * C3N_BN * 4 + j * 128);
-            IMG_RD32(rb[j][4], fbs, 4 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][5], fbs, 5 * C3N_BN * 4 + j * 128);
-            IMG_RD32(rb[j][6], fbs, 6 * C3N_BN * 4 + j * 128); IMG_RD32(rb[j][7], fbs, 7 * C3N_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][0], fbs, 0 * C3N_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][1], fbs, 1 * C3N_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][2], fbs, 2 * C3N_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][3], fbs, 3 * C3N_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][4], fbs, 4 * C3N_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][5], fbs, 5 * C3N_BN * 4 + j * 128);
+            ACR_LDS_RD32(rb[j][6], fbs, 6 * C3N_BN * 4 + j * 128); ACR_LDS_RD32(rb[j][7], fbs, 7 * C3N_BN * 4 + j * 128);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            IMG_RD128(ap[SET][i][0], fas, 0 * 2048 + i * 1024); IMG_RD128(ap[SET][i][1], fas, 1 * 2048 + i * 1024);
-            IMG_RD128(ap[SET][i][2], fas, 2 * 2048 + i * 1024);
+            ACR_LDS_RD128(ap[SET][i][0], fas, 0 * 2048 + i * 1024); ACR_LDS_RD128(ap[SET][i][1], fas, 1 * 2048 + i * 1024);
+            ACR_LDS_RD128(ap[SET][i][2], fas, 2 * 2048 + i * 1024);
         }
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]), "+v"(rb[0][4]), "+v"(rb[0][5]), "+v"(rb[0][6]),
                      "+v"(rb[0][7]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3]), "+v"(rb[1][4]), "+v"(rb[1][5]), "+v"(rb[1][6]), "+v"(rb[1][7]));

@@ -529,8 +529,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_planes_kernel(const GemmF32Ar
 #define PL_GROUP(K12)                                                                                                   \
         if constexpr ((K12) < NG) {                                                                                     \
             if constexpr (!FIRST) pl_mfmas<FMT, (K12) * NM / NG, ((K12) + 1) * NM / NG>(acc, ap[SET ^ 1], bp[SET ^ 1]);  \
-            if constexpr ((K12) < 2 * NP) IMG_RD128(ap[SET][(K12) / NP][(K12) % NP], fas, ((K12) % NP) * IMG_PLANE_B + ((K12) / NP) * 1024); \
-            else IMG_RD128(bp[SET][((K12) - 2 * NP) / NP][(K12) % NP], fbs, ((K12) % NP) * IMG_PLANE_B + (((K12) - 2 * NP) / NP) * 1024); \
+            if constexpr ((K12) < 2 * NP) ACR_LDS_RD128(ap[SET][(K12) / NP][(K12) % NP], fas, ((K12) % NP) * IMG_PLANE_B + ((K12) / NP) * 1024); \
+            else ACR_LDS_RD128(bp[SET][((K12) - 2 * NP) / NP][(K12) % NP], fbs, ((K12) % NP) * IMG_PLANE_B + (((K12) - 2 * NP) / NP) * 1024); \
             if ((K12) & 1) dma1(rst, rslot, (K12) >> 1);                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                                          \
         }

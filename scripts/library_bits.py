@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """library_bits.py LIB.so: the bits a build of the library computes, one line per output, to be diffed against another build's.
 
-Runs once, in this one process, the entry points whose kernels share acr_resample.h / acr_reduce.h (and preprocess.hip's sample) on
-seeded inputs at the smallest shapes that reach every branch, and prints `entry  case  shape  dtype  sha256` per output.  All of
+Runs once, in this one process, the entry points whose kernels share acr_resample.h / acr_reduce.h (and preprocess.hip's sample)
+and the three generations of fp32 attention (attn_f32_scores.h) on seeded inputs at the smallest shapes that reach every branch, and prints `entry  case  shape  dtype  sha256` per output.  All of
 these kernels are bit-identical run to run, so two builds agree exactly when the two outputs are equal line for line:
     library_bits.py old/libacr_hip.so > a; library_bits.py new/libacr_hip.so > b; diff a b
 The library is picked through ACR_LIB_PATH (acr_wsss_amd/_lib.py).  Needs a GPU; takes seconds."""
@@ -153,9 +153,39 @@ def step_kernels():
         grads("ops.consistency", "B%d L%d p%d" % (b, l, p), [cls + 2 * aff], [a], ["a"])
 
 
+class _Owner:
+    """stands in for the attention module: AttnCoreFn leaves (qkv, lse2, heads) on it"""
+    training, keep_state_in_training = True, True
+
+
+def attention():
+    # T = 33: two blocks, the second with one key; 145 / 273: the smallest split tails of four- and eight-wave workgroups; 785: the bench's
+    for gen, scores, math in (("recompute", False, 0), ("scores", True, 0), ("split", True, 1)):
+        ops.ATTN_F32_SCORES = scores
+        for (T, H) in ((33, 1), (145, 4), (273, 2), (785, 12)):
+            for with_g in (True, False):
+                qkv = rnd(1, T, 3 * H * 64, scale=1.5).requires_grad_(True)
+                d_o, gpm = rnd(1, T, H * 64), rnd(1, T, T)
+                stack, own = ops.MeanStack(1, 1, T, DEV), _Owner()
+                o, pm = ops.attention_core(qkv, H, stack, 0, own, math)
+                case = "%s T%d H%d g%d" % (gen, T, H, with_g)
+                for n, t in (("o", o), ("lse2", own._saved[1]), ("pmean", pm)):
+                    emit("ops.attention_core", case + " " + n, t)
+                (dqkv,) = torch.autograd.grad([o, pm] if with_g else [o], [qkv], [d_o, gpm] if with_g else [d_o])
+                emit("ops.attention_core", case + " dqkv", dqkv)
+    ops.ATTN_F32_SCORES = True
+    qkv = rnd(1, 785, 3 * 12 * 64, scale=1.5).requires_grad_(True)
+    stack, own = ops.MeanStack(1, 1, 785, DEV), _Owner()
+    o, pm, img = ops.attention_core_oimg(qkv, 12, stack, 0, own, 1)
+    for n, t in (("o", o), ("lse2", own._saved[1]), ("pmean", pm), ("o_image", img)):
+        emit("ops.attention_core_oimg", "split T785 H12 " + n, t)
+    (dqkv,) = torch.autograd.grad([o, pm], [qkv], [rnd(1, 785, 12 * 64), rnd(1, 785, 785)])
+    emit("ops.attention_core_oimg", "split T785 H12 dqkv", dqkv)
+
+
 if __name__ == "__main__":
     assert torch.cuda.is_available(), "library_bits.py needs a GPU"
     assert os.path.samefile(L.LIB_PATH, sys.argv[1]), (L.LIB_PATH, sys.argv[1])
-    for part in (segpred, seglosses, resize, decoders, loaders, step_kernels):
+    for part in (segpred, seglosses, resize, decoders, loaders, step_kernels, attention):
         part()
     torch.cuda.synchronize()

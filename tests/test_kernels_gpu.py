@@ -87,7 +87,10 @@ def _consistency_full_size_case(B, p):
 
 
 @pytest.mark.parametrize("B,T,H", [(2, 2, 1), (1, 17, 12), (2, 197, 3), (1, 785, 12), (1, 1025, 2),
-                                   (1, 2305, 3), (1, 3137, 1)])          # multi-scale inference: 768^2 and 896^2
+                                   (1, 2305, 3), (1, 3137, 1),           # multi-scale inference: 768^2 and 896^2
+                                   (1, 145, 4),     # NB = 5: the smallest split tail of four-wave workgroups, last block half full; four-head delta kernel
+                                   (1, 273, 2),     # NB = 9: the smallest split tail of the eight-wave split backward (and 9 % 4 == 1); one-wave delta kernel
+                                   (1, 33, 1)])     # two blocks, the second holding one key: ring slot 1, key / G masks with almost all masked
 @pytest.mark.parametrize("with_g", [True, False])
 @pytest.mark.parametrize("gen", ["scores", "recompute", "split"])
 def test_attention_f32(B, T, H, with_g, gen, monkeypatch):
