@@ -209,6 +209,14 @@ SIGNATURES = {
                                ctypes.c_double, ctypes.c_double, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "acr_bn2d_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_bn2d_moments": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_bn2d_fwd_merged": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                      c_void_p, c_int32, ctypes.c_double, ctypes.c_double, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                      c_void_p]),
+    "acr_bn2d_bwd_sums": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_bn2d_bwd_merged": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "acr_relu_fwd_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
     "acr_relu_bwd_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "acr_upsample2x_fwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

@@ -14,6 +14,11 @@
 // The normalisation itself is one double FMA per value, y = fp32(a_c * x + b_c (+ r1 + r2)), rounded once.
 // The ReLU mask of the backward is recomputed from the saved output (y > 0); no mask bytes are kept.
 //
+// Cross-rank statistics (nn.SyncBatchNorm): each direction is slab sums -> a per-channel kernel that writes a small double row
+// ((C, 3) count / mean / M2 forward, (C, 2) sum g / sum g xhat backward) -> the CALLER's gather of the ranks' rows -> a per-channel
+// kernel that merges the rows in ascending rank order and writes what the apply pass takes.  The slab walk, the block sum and the
+// apply passes are the fused entry points' own; no pass over a tensor is added.
+//
 // Upsampling: forward one thread per pair of output pixels (8-byte stores: an output row has 2 W floats); backward a GATHER per
 // input pixel over the exact range of output rows / columns whose first tap is i - 1 or i, found with the forward's own fp32
 // source-index function, summed in ascending order in double.
@@ -72,6 +77,43 @@ __device__ __forceinline__ void bn_block_sum(double& a, double& b) {
     b = rd[256];
 }
 
+// a channel's slab sums of a pass, added in ascending slab order
+__device__ __forceinline__ void bn_slab_sum(const double* __restrict__ part, int c, int S, double& a, double& b) {
+    a = 0.0;
+    b = 0.0;
+    for (int s = 0; s < S; ++s) {
+        a += part[2 * ((int64_t)c * S + s)];
+        b += part[2 * ((int64_t)c * S + s) + 1];
+    }
+}
+
+// The merge rule of cross-rank statistics, stated once: (n, mean, M2 = sum (x - mean)^2) of a set A takes in those of a disjoint
+// set B by the pairwise update (Chan, Golub, LeVeque 1979).  The spread between the two means enters as delta^2 n_a n_b / n, a
+// sum of non-negative terms: no difference of sums of squares, so the digits the shifted slab sums keep are not lost here.
+__device__ __forceinline__ void bn_merge_moments(double& n, double& mean, double& m2, double nb, double meanb, double m2b) {
+    const double na = n, delta = meanb - mean;
+    n = na + nb;
+    mean = mean + delta * nb / n;
+    m2 = m2 + m2b + delta * delta * na * nb / n;
+}
+
+// what a normalising pass and the backward take from the statistics: stats = (mean, invstd), coef of y = a x + b
+__device__ __forceinline__ void bn_write_coef(int c, double mean, double invstd, const float* __restrict__ gamma,
+                                              const float* __restrict__ beta, double* __restrict__ stats, double* __restrict__ coef) {
+    stats[2 * c] = mean;
+    stats[2 * c + 1] = invstd;
+    const double k = (double)gamma[c] * invstd;
+    coef[2 * c] = k;
+    coef[2 * c + 1] = (double)beta[c] - mean * k;
+}
+
+// the running update of nn.BatchNorm2d: the mean and the UNBIASED variance of the batch
+__device__ __forceinline__ void bn_running_update(int c, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                  double momentum, double mean, double unbiased) {
+    if (running_mean) running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
+    if (running_var) running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+}
+
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int C, int HW, int64_t M, int S,
                                                        double* __restrict__ part) {
     const int c = blockIdx.x / S, s = blockIdx.x % S;
@@ -112,27 +154,53 @@ __global__ __launch_bounds__(256) void bn_fwd_finish_kernel(const float* __restr
     if (c >= C) return;
     double mean, invstd;
     if (training) {
-        double a = 0.0, b = 0.0;
-        for (int s = 0; s < S; ++s) {
-            a += part[2 * ((int64_t)c * S + s)];
-            b += part[2 * ((int64_t)c * S + s) + 1];
-        }
+        double a, b;
+        bn_slab_sum(part, c, S, a, b);
         const double n = (double)M;
         mean = (double)x[(int64_t)c * HW] + a / n;
         double var = (b - a * a / n) / n;
         var = var > 0.0 ? var : 0.0;
         invstd = 1.0 / sqrt(var + eps);
-        if (running_mean) running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-        if (running_var) running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * (var * n / (n - 1.0)));
+        bn_running_update(c, running_mean, running_var, momentum, mean, var * n / (n - 1.0));
     } else {
         mean = (double)running_mean[c];
         invstd = 1.0 / sqrt((double)running_var[c] + eps);
     }
-    stats[2 * c] = mean;
-    stats[2 * c + 1] = invstd;
-    const double k = (double)gamma[c] * invstd;
-    coef[2 * c] = k;
-    coef[2 * c + 1] = (double)beta[c] - mean * k;
+    bn_write_coef(c, mean, invstd, gamma, beta, stats, coef);
+}
+
+// ---- cross-rank statistics: the forward's per-channel kernels on either side of the exchange ----------------------------------
+// moments (C, 3) of the local tensor from its slab sums: count, mean, M2.  One value (n = 1) is legal: M2 = 0.
+__global__ __launch_bounds__(256) void bn_moments_kernel(const float* __restrict__ x, const double* __restrict__ part, int C, int HW,
+                                                         int64_t M, int S, double* __restrict__ moments) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double a, b;
+    bn_slab_sum(part, c, S, a, b);
+    const double n = (double)M;
+    const double m2 = b - a * a / n;
+    moments[3 * c] = n;
+    moments[3 * c + 1] = (double)x[(int64_t)c * HW] + a / n;
+    moments[3 * c + 2] = m2 > 0.0 ? m2 : 0.0;
+}
+
+// one thread per channel: the W ranks' moments merged in ascending rank order, then what bn_fwd_finish_kernel writes; stats is
+// (C, 2) mean / invstd followed by the C merged counts
+__global__ __launch_bounds__(256) void bn_fwd_merge_kernel(const double* __restrict__ gathered, int W, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, float* __restrict__ running_mean,
+                                                           float* __restrict__ running_var, int C, double eps, double momentum,
+                                                           double* __restrict__ stats, double* __restrict__ coef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double n = gathered[3 * c], mean = gathered[3 * c + 1], m2 = gathered[3 * c + 2];
+    for (int r = 1; r < W; ++r) {
+        const double* row = gathered + 3 * ((int64_t)r * C + c);
+        bn_merge_moments(n, mean, m2, row[0], row[1], row[2]);
+    }
+    const double invstd = 1.0 / sqrt(m2 / n + eps);
+    bn_running_update(c, running_mean, running_var, momentum, mean, m2 / (n - 1.0));
+    bn_write_coef(c, mean, invstd, gamma, beta, stats, coef);
+    stats[2 * (int64_t)C + c] = n;
 }
 
 template <bool RELU, int NRES>
@@ -205,16 +273,43 @@ __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __rest
                                                             double* __restrict__ coef) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    double a = 0.0, b = 0.0;
-    for (int s = 0; s < S; ++s) {
-        a += part[2 * ((int64_t)c * S + s)];
-        b += part[2 * ((int64_t)c * S + s) + 1];
-    }
+    double a, b;
+    bn_slab_sum(part, c, S, a, b);
     if (dbeta) dbeta[c] = (float)a;
     if (dgamma) dgamma[c] = (float)b;
     coef[3 * c] = (double)gamma[c] * stats[2 * c + 1];
     coef[3 * c + 1] = training ? a / (double)M : 0.0;
     coef[3 * c + 2] = training ? b / (double)M : 0.0;
+}
+
+// ---- cross-rank statistics: the backward's per-channel kernels on either side of the exchange ---------------------------------
+// sums (C, 2) = (sum g, sum g * xhat) of the local tensor; the parameter gradients are the local sums
+__global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const double* __restrict__ part, int C, int S, double* __restrict__ sums,
+                                                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double a, b;
+    bn_slab_sum(part, c, S, a, b);
+    sums[2 * c] = a;
+    sums[2 * c + 1] = b;
+    if (dbeta) dbeta[c] = (float)a;
+    if (dgamma) dgamma[c] = (float)b;
+}
+
+// the W ranks' sums added in ascending rank order and divided by the merged count: the coef of bn_bwd_apply_kernel
+__global__ __launch_bounds__(256) void bn_bwd_merge_kernel(const double* __restrict__ gathered, int W, const float* __restrict__ gamma,
+                                                           const double* __restrict__ stats, int C, double* __restrict__ coef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int r = 0; r < W; ++r) {
+        a += gathered[2 * ((int64_t)r * C + c)];
+        b += gathered[2 * ((int64_t)r * C + c) + 1];
+    }
+    const double n = stats[2 * (int64_t)C + c];
+    coef[3 * c] = (double)gamma[c] * stats[2 * c + 1];
+    coef[3 * c + 1] = a / n;
+    coef[3 * c + 2] = b / n;
 }
 
 template <bool RELU>
@@ -371,6 +466,39 @@ extern "C" int64_t acr_bn2d_ws_bytes(int32_t N, int32_t C, int32_t HW) {
     return 8 * ((int64_t)C * bn_slabs((int64_t)N * HW, C) * 2 + 3 * (int64_t)C);
 }
 
+// the passes over the tensors, launched for the fused entry points and for the cross-rank ones alike
+static void bn_launch_apply(hipStream_t st, dim3 grid, const float* x, const double* coef, const float* resid, const float* resid2, int C,
+                            int HW, int64_t M, int S, int relu, float* y) {
+#define BN_APPLY(R, K) hipLaunchKernelGGL((bn_apply_kernel<R, K>), grid, dim3(256), 0, st, x, coef, resid, resid2, C, HW, M, S, y)
+    const int nres = resid2 ? 2 : (resid ? 1 : 0);
+    if (relu) {
+        if (nres == 0) BN_APPLY(true, 0);
+        else if (nres == 1) BN_APPLY(true, 1);
+        else BN_APPLY(true, 2);
+    } else {
+        if (nres == 0) BN_APPLY(false, 0);
+        else if (nres == 1) BN_APPLY(false, 1);
+        else BN_APPLY(false, 2);
+    }
+#undef BN_APPLY
+}
+
+static void bn_launch_bwd_reduce(hipStream_t st, dim3 grid, const float* x, const float* y, const float* dy, const double* stats, int C,
+                                 int HW, int64_t M, int S, int relu, double* part) {
+    if (relu)
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(256), 0, st, x, y, dy, stats, C, HW, M, S, part);
+    else
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(256), 0, st, x, y, dy, stats, C, HW, M, S, part);
+}
+
+static void bn_launch_bwd_apply(hipStream_t st, dim3 grid, const float* x, const float* y, const float* dy, const double* stats,
+                                const double* coef, int C, int HW, int64_t M, int S, int relu, float* dx, float* dres) {
+    if (relu)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(256), 0, st, x, y, dy, stats, coef, C, HW, M, S, dx, dres);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(256), 0, st, x, y, dy, stats, coef, C, HW, M, S, dx, dres);
+}
+
 extern "C" int acr_bn2d_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                             const float* resid, const float* resid2, int32_t N, int32_t C, int32_t HW, int32_t training, double eps,
                             double momentum, int32_t relu, void* ws, int64_t ws_bytes, double* stats, float* y, void* stream) {
@@ -396,19 +524,7 @@ extern "C" int acr_bn2d_fwd(const float* x, const float* gamma, const float* bet
     if (training) hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, st, x, C, HW, M, S, part);
     hipLaunchKernelGGL(bn_fwd_finish_kernel, cgrid, dim3(256), 0, st, x, (const double*)part, gamma, beta, running_mean, running_var, C,
                        HW, M, S, training ? 1 : 0, eps, momentum, stats, coef);
-#define BN_APPLY(R, K) \
-    hipLaunchKernelGGL((bn_apply_kernel<R, K>), grid, dim3(256), 0, st, x, (const double*)coef, resid, resid2, C, HW, M, S, y)
-    const int nres = resid2 ? 2 : (resid ? 1 : 0);
-    if (relu) {
-        if (nres == 0) BN_APPLY(true, 0);
-        else if (nres == 1) BN_APPLY(true, 1);
-        else BN_APPLY(true, 2);
-    } else {
-        if (nres == 0) BN_APPLY(false, 0);
-        else if (nres == 1) BN_APPLY(false, 1);
-        else BN_APPLY(false, 2);
-    }
-#undef BN_APPLY
+    bn_launch_apply(st, grid, x, coef, resid, resid2, C, HW, M, S, relu, y);
     return acr_check_launch("acr_bn2d_fwd");
 }
 
@@ -431,19 +547,102 @@ extern "C" int acr_bn2d_bwd(const float* x, const float* y, const float* dy, con
     double* part = reinterpret_cast<double*>(ws);
     double* coef = part + (int64_t)C * S * 2;
     const dim3 grid((unsigned)(C * S)), cgrid((unsigned)((C + 255) / 256));
-    if (relu)
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(256), 0, st, x, y, dy, stats, C, HW, M, S, part);
-    else
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(256), 0, st, x, y, dy, stats, C, HW, M, S, part);
+    bn_launch_bwd_reduce(st, grid, x, y, dy, stats, C, HW, M, S, relu, part);
     hipLaunchKernelGGL(bn_bwd_finish_kernel, cgrid, dim3(256), 0, st, (const double*)part, gamma, stats, C, M, S, training ? 1 : 0, dgamma,
                        dbeta, coef);
-    if (dx || dres) {
-        if (relu)
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(256), 0, st, x, y, dy, stats, (const double*)coef, C, HW, M, S, dx, dres);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(256), 0, st, x, y, dy, stats, (const double*)coef, C, HW, M, S, dx, dres);
-    }
+    if (dx || dres) bn_launch_bwd_apply(st, grid, x, y, dy, stats, coef, C, HW, M, S, relu, dx, dres);
     return acr_check_launch("acr_bn2d_bwd");
+}
+
+// ---- cross-rank statistics (nn.SyncBatchNorm): the two halves of each direction, the caller's gather between them -------------
+#define BN_WORLD_MAX 65536
+
+// the shape, the workspace and the 8-byte alignment of the double buffers, common to the four entry points
+static int bn_sync_check(const char* who, int32_t N, int32_t C, int32_t HW, const void* ws, int64_t ws_bytes, const void* d1,
+                         const void* d2) {
+    const int rc = bn_check(who, N, C, HW);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(ws && d1 && d2, "%s: null pointer", who);
+    ACR_CHECK_ARG((((uintptr_t)ws | (uintptr_t)d1 | (uintptr_t)d2) & 7) == 0, "%s: ws or a double buffer not aligned to 8 bytes", who);
+    ACR_CHECK_ARG(ws_bytes >= acr_bn2d_ws_bytes(N, C, HW), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
+                  (long long)acr_bn2d_ws_bytes(N, C, HW));
+    return ACR_OK;
+}
+
+extern "C" int acr_bn2d_moments(const float* x, int32_t N, int32_t C, int32_t HW, void* ws, int64_t ws_bytes, double* moments,
+                                void* stream) {
+    const int rc = bn_sync_check("acr_bn2d_moments", N, C, HW, ws, ws_bytes, moments, moments);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && BN_ALIGNED(x), "acr_bn2d_moments: x null or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t M = (int64_t)N * HW;
+    const int S = bn_slabs(M, C);
+    double* part = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)(C * S)), dim3(256), 0, st, x, C, HW, M, S, part);
+    hipLaunchKernelGGL(bn_moments_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, x, (const double*)part, C, HW, M, S, moments);
+    return acr_check_launch("acr_bn2d_moments");
+}
+
+extern "C" int acr_bn2d_fwd_merged(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                   const float* resid, const float* resid2, int32_t N, int32_t C, int32_t HW, const double* gathered,
+                                   int32_t W, double eps, double momentum, int32_t relu, void* ws, int64_t ws_bytes, double* stats,
+                                   float* y, void* stream) {
+    const int rc = bn_sync_check("acr_bn2d_fwd_merged", N, C, HW, ws, ws_bytes, gathered, stats);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && gamma && beta && y, "acr_bn2d_fwd_merged: null pointer");
+    ACR_CHECK_ARG(resid || !resid2, "acr_bn2d_fwd_merged: resid2 given without resid");
+    ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(resid) && BN_ALIGNED(resid2),
+                  "acr_bn2d_fwd_merged: a tensor is not 16-byte aligned");
+    ACR_CHECK_ARG(W >= 1 && W <= BN_WORLD_MAX, "acr_bn2d_fwd_merged: W=%d ranks, 1 .. %d", W, BN_WORLD_MAX);
+    ACR_CHECK_ARG(eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0, "acr_bn2d_fwd_merged: eps=%g, momentum=%g", eps, momentum);
+    // every rank holds whole (H, W) planes of the same size, so the merged count is at least N * HW + (W - 1) * HW: known here
+    // without reading the gathered counts back
+    const int64_t M = (int64_t)N * HW;
+    ACR_CHECK_ARG(M + (int64_t)(W - 1) * HW >= 2, "acr_bn2d_fwd_merged: 1 value per channel over all ranks, 2 at least");
+    hipStream_t st = (hipStream_t)stream;
+    const int S = bn_slabs(M, C);
+    double* coef = reinterpret_cast<double*>(ws) + (int64_t)C * S * 2;
+    hipLaunchKernelGGL(bn_fwd_merge_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, gathered, W, gamma, beta, running_mean,
+                       running_var, C, eps, momentum, stats, coef);
+    bn_launch_apply(st, dim3((unsigned)(C * S)), x, coef, resid, resid2, C, HW, M, S, relu, y);
+    return acr_check_launch("acr_bn2d_fwd_merged");
+}
+
+extern "C" int acr_bn2d_bwd_sums(const float* x, const float* y, const float* dy, const double* stats, int32_t N, int32_t C, int32_t HW,
+                                 int32_t relu, void* ws, int64_t ws_bytes, double* sums, float* dgamma, float* dbeta, void* stream) {
+    const int rc = bn_sync_check("acr_bn2d_bwd_sums", N, C, HW, ws, ws_bytes, stats, sums);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && dy, "acr_bn2d_bwd_sums: null pointer");
+    ACR_CHECK_ARG(!relu || y, "acr_bn2d_bwd_sums: a fused ReLU needs the saved output");
+    ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(dy), "acr_bn2d_bwd_sums: a tensor is not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t M = (int64_t)N * HW;
+    const int S = bn_slabs(M, C);
+    double* part = reinterpret_cast<double*>(ws);
+    bn_launch_bwd_reduce(st, dim3((unsigned)(C * S)), x, y, dy, stats, C, HW, M, S, relu, part);
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, (const double*)part, C, S, sums, dgamma,
+                       dbeta);
+    return acr_check_launch("acr_bn2d_bwd_sums");
+}
+
+extern "C" int acr_bn2d_bwd_merged(const float* x, const float* y, const float* dy, const float* gamma, const double* stats,
+                                   const double* gathered_sums, int32_t W, int32_t N, int32_t C, int32_t HW, int32_t relu, void* ws,
+                                   int64_t ws_bytes, float* dx, float* dres, void* stream) {
+    const int rc = bn_sync_check("acr_bn2d_bwd_merged", N, C, HW, ws, ws_bytes, stats, gathered_sums);
+    if (rc != ACR_OK) return rc;
+    ACR_CHECK_ARG(x && dy && gamma, "acr_bn2d_bwd_merged: null pointer");
+    ACR_CHECK_ARG(!relu || y, "acr_bn2d_bwd_merged: a fused ReLU needs the saved output");
+    ACR_CHECK_ARG(relu || !dres, "acr_bn2d_bwd_merged: without a fused ReLU the addends' gradient is dy itself; dres must be null");
+    ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(dy) && BN_ALIGNED(dx) && BN_ALIGNED(dres),
+                  "acr_bn2d_bwd_merged: a tensor is not 16-byte aligned");
+    ACR_CHECK_ARG(W >= 1 && W <= BN_WORLD_MAX, "acr_bn2d_bwd_merged: W=%d ranks, 1 .. %d", W, BN_WORLD_MAX);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t M = (int64_t)N * HW;
+    const int S = bn_slabs(M, C);
+    double* coef = reinterpret_cast<double*>(ws) + (int64_t)C * S * 2;
+    hipLaunchKernelGGL(bn_bwd_merge_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, gathered_sums, W, gamma, stats, C, coef);
+    if (dx || dres) bn_launch_bwd_apply(st, dim3((unsigned)(C * S)), x, y, dy, stats, coef, C, HW, M, S, relu, dx, dres);
+    return acr_check_launch("acr_bn2d_bwd_merged");
 }
 
 static int relu_grid(int64_t n) {

@@ -9,9 +9,20 @@ upsampling and the leading ReLU of a residual unit run in csrc/decoder.hip behin
 There is no CPU path: a CPU tensor raises ``AcrHipError``.  Forward and backward are bit-identical run to run.
 
 Precision: fp32 tensors under ``math="f32"`` and ``math="f32_split"``; bf16 is not built (``decode`` raises).
-Multi-GPU: the reference converts the model to ``SyncBatchNorm`` (train_acr.py:95); here the batch statistics are PER RANK --
-cross-rank statistics are not built."""
+Multi-GPU: ``torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)`` (train_acr.py:95), verbatim, is the switch.  A converted norm
+in training mode, inside an initialised process group of more than one rank, normalises with the statistics of ALL ranks' values
+and its backward uses all ranks' gradient sums.  Per layer and direction one fixed-size double tensor is exchanged -- forward
+(C, 3): count, mean, sum of squared deviations; backward (C, 2): sum g, sum g * xhat -- by a ``torch.distributed.all_gather`` into
+W rows in rank order; the kernels merge the rows in ascending rank order, so every rank computes the same bits whatever algorithm
+the backend picks.  Ranks may hold different batch sizes (the count travels), but every rank must bring at least one image --
+an empty shard, which torch's module accepts, is refused here on that rank before the gather, and the other ranks then wait in
+it until the group's timeout; H * W must agree.  Parameter gradients stay local
+sums: ``dp.GradSync`` averages them like every other parameter's, as ``nn.SyncBatchNorm`` relies on DDP to.  The gathers go to the
+norm's ``process_group`` (None: the default group) from forward and from autograd's backward, in the same order on every rank
+(DESIGN.md says why).  ``nn.BatchNorm2d`` modules never exchange anything.  The gather has run over gloo only (CPU tensors, and
+two ranks sharing one GPU); no RCCL run of it exists yet, and no multi-GPU timing of this path has been measured."""
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -37,6 +48,13 @@ def _c16(t):
     return t.clone() if t.data_ptr() % 16 else t
 
 
+def _ws(lib, n, c, hw, dev):
+    nbytes = lib.acr_bn2d_ws_bytes(n, c, hw)
+    if nbytes < 0:
+        L.check(-1, "acr_bn2d_ws_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd functions over the C ABI
 # ------------------------------------------------------------------------------------------------
@@ -48,10 +66,8 @@ class _BatchNormAct(Function):
         n, c, h, w = x.shape
         dev = x.device
         with torch.cuda.device(dev):
-            nbytes = lib.acr_bn2d_ws_bytes(n, c, h * w)
-            if nbytes < 0:
-                L.check(-1, "acr_bn2d_ws_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _ws(lib, n, c, h * w, dev)
+            nbytes = ws.numel()
             stats = torch.empty((c, 2), dtype=torch.float64, device=dev)
             y = torch.empty_like(x)
             L.check(lib.acr_bn2d_fwd(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
@@ -87,18 +103,95 @@ class _BatchNormAct(Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None, d1, d2
 
 
+def gather_rows(t, group=None):
+    """The exchange of the cross-rank norm: ``t`` (C, k) float64, the same shape on every rank -> (W, C, k), row r rank r's ``t``,
+    the same on every rank.  One ``all_gather`` on ``group`` (None: the default group) straight into the rows of the result (the
+    output list is views of one buffer: exercised over gloo; not yet run over RCCL)."""
+    t = t.contiguous()
+    buf = torch.empty((dist.get_world_size(group),) + tuple(t.shape), dtype=t.dtype, device=t.device)
+    dist.all_gather(list(buf.unbind(0)), t, group=group)
+    return buf
+
+
+class _SyncBatchNormAct(Function):
+    """``_BatchNormAct`` in training mode with the statistics of every rank of ``group``: moments -> gather -> merged forward, and
+    sums -> gather -> merged backward"""
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, resid, resid2, group):
+        lib = L.load()
+        x, resid, resid2 = _c16(x), _c16(resid), _c16(resid2)
+        n, c, h, w = x.shape
+        dev = x.device
+        with torch.cuda.device(dev):
+            ws = _ws(lib, n, c, h * w, dev)
+            moments = torch.empty((c, 3), dtype=torch.float64, device=dev)
+            L.check(lib.acr_bn2d_moments(L.ptr(x), n, c, h * w, L.ptr(ws), ws.numel(), L.ptr(moments), L.stream_ptr()), "acr_bn2d_moments")
+            gathered = gather_rows(moments, group)
+            stats = torch.empty(3 * c, dtype=torch.float64, device=dev)          # (C, 2) mean / invstd, then the C merged counts
+            y = torch.empty_like(x)
+            L.check(lib.acr_bn2d_fwd_merged(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
+                                            L.ptr(resid2), n, c, h * w, L.ptr(gathered), gathered.shape[0], float(eps), float(momentum),
+                                            1 if relu else 0, L.ptr(ws), ws.numel(), L.ptr(stats), L.ptr(y), L.stream_ptr()),
+                    "acr_bn2d_fwd_merged")
+        ctx.save_for_backward(x, weight, stats, y if relu else None)
+        ctx.relu, ctx.ws, ctx.group = bool(relu), ws, group
+        ctx.nres = (resid is not None) + (resid2 is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        x, weight, stats, y = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dev = x.device
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_r = ctx.nres and (ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
+        relu = 1 if ctx.relu else 0
+        with torch.cuda.device(dev):
+            dy = _c16(dy.to(torch.float32))
+            dx = torch.empty_like(x) if need_x else None
+            dgamma = torch.empty(c, dtype=torch.float32, device=dev) if need_w else None
+            dbeta = torch.empty(c, dtype=torch.float32, device=dev) if need_b else None
+            dres = torch.empty_like(x) if (need_r and ctx.relu) else None
+            if need_x or need_w or need_b or dres is not None:
+                sums = torch.empty((c, 2), dtype=torch.float64, device=dev)
+                L.check(lib.acr_bn2d_bwd_sums(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(stats), n, c, h * w, relu, L.ptr(ctx.ws), ctx.ws.numel(),
+                                              L.ptr(sums), L.ptr(dgamma), L.ptr(dbeta), L.stream_ptr()), "acr_bn2d_bwd_sums")
+                if need_x or dres is not None:
+                    # the exchange happens exactly when x needs a gradient, as in torch; dres alone is the masked dy, no sums in it
+                    rows = gather_rows(sums, ctx.group) if need_x else sums.unsqueeze(0)
+                    L.check(lib.acr_bn2d_bwd_merged(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(weight), L.ptr(stats), L.ptr(rows), rows.shape[0],
+                                                    n, c, h * w, relu, L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(dx), L.ptr(dres),
+                                                    L.stream_ptr()), "acr_bn2d_bwd_merged")
+        if need_r and not ctx.relu:
+            dres = dy                                       # without a ReLU the addends' gradient is dy itself
+        d1 = dres if (ctx.nres >= 1 and ctx.needs_input_grad[8]) else None
+        d2 = dres if (ctx.nres >= 2 and ctx.needs_input_grad[9]) else None
+        return dx, dgamma, dbeta, None, None, None, None, None, d1, d2, None
+
+
+def _sync_group(bn):
+    """(exchange?, group) by ``nn.SyncBatchNorm.forward``'s own condition: the module normalises with batch statistics while it
+    trains, ``torch.distributed`` is initialised and the module's group (None: the default one) has more than one rank"""
+    if not (isinstance(bn, nn.SyncBatchNorm) and bn.training and dist.is_available() and dist.is_initialized()):
+        return False, None
+    return dist.get_world_size(bn.process_group) > 1, bn.process_group
+
+
 def batch_norm_act(x, bn, act="none", resid=None, resid2=None):
-    """``act(bn(x) [+ resid] [+ resid2])`` in one pass: ``bn`` an ``nn.BatchNorm2d`` (affine, a float ``momentum``), ``act``
-    "none" or "relu", the addends shaped like ``x`` (``resid2`` only with ``resid``).  In training mode the batch statistics
-    (biased variance) normalise and the module's ``running_mean`` / ``running_var`` / ``num_batches_tracked`` are updated as
-    ``nn.BatchNorm2d`` updates them (the running variance unbiased); in eval mode the running statistics normalise and the
-    backward treats them as constants.  One value per channel in training mode raises ValueError, as torch does.  Statistics are
-    those of this process's batch: nothing is exchanged between ranks.  Differentiable in x, the affine parameters and the
-    addends."""
+    """``act(bn(x) [+ resid] [+ resid2])`` in one pass: ``bn`` an ``nn.BatchNorm2d`` or an ``nn.SyncBatchNorm`` (affine, a float
+    ``momentum``), ``act`` "none" or "relu", the addends shaped like ``x`` (``resid2`` only with ``resid``).  In training mode the
+    batch statistics (biased variance) normalise and the module's ``running_mean`` / ``running_var`` / ``num_batches_tracked`` are
+    updated as ``nn.BatchNorm2d`` updates them (the running variance unbiased); in eval mode the running statistics normalise and
+    the backward treats them as constants.  One value per channel in training mode raises ValueError, as torch does.  An
+    ``nn.BatchNorm2d`` uses this process's batch alone.  An ``nn.SyncBatchNorm`` that trains inside a process group of more than
+    one rank uses every rank's values (the module docstring says what is exchanged); then one value per channel on a rank is
+    legal, an empty batch on a rank is not (every rank must call with N >= 1, or the others wait in the gather).  Anywhere else -- eval mode, no process group, a one-rank group -- it computes the bits of an ``nn.BatchNorm2d`` with
+    the same state.  Differentiable in x, the affine parameters and the addends."""
     if act not in ("none", "relu"):
         raise ValueError("act must be \"none\" or \"relu\", got %r" % (act,))
-    if not isinstance(bn, nn.BatchNorm2d) or not bn.affine:
-        raise NotImplementedError("batch_norm_act takes an affine nn.BatchNorm2d, got %s" % type(bn).__name__)
+    if not isinstance(bn, (nn.BatchNorm2d, nn.SyncBatchNorm)) or not bn.affine:
+        raise NotImplementedError("batch_norm_act takes an affine nn.BatchNorm2d or nn.SyncBatchNorm, got %s" % type(bn).__name__)
     if bn.momentum is None and bn.track_running_stats:
         raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative average) is not built; give a float momentum")
     if resid2 is not None and resid is None:
@@ -112,11 +205,14 @@ def batch_norm_act(x, bn, act="none", resid=None, resid2=None):
     if bn.weight.dtype != torch.float32 or bn.weight.device != x.device:
         raise ValueError("the norm's parameters must be float32 on %s" % x.device)
     training = bn.training or bn.running_mean is None
-    if training and x.shape[0] * x.shape[2] * x.shape[3] < 2:
+    sync, group = _sync_group(bn)
+    if training and not sync and x.shape[0] * x.shape[2] * x.shape[3] < 2:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
     rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
     if bn.training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
+    if sync:
+        return _SyncBatchNormAct.apply(x, bn.weight, bn.bias, rm, rv, bn.momentum or 0.0, bn.eps, act == "relu", resid, resid2, group)
     return _BatchNormAct.apply(x, bn.weight, bn.bias, rm, rv, training, bn.momentum or 0.0, bn.eps, act == "relu", resid, resid2)
 
 
@@ -320,5 +416,6 @@ def fuse(model, l1, l2, l3, l4):
 def decode(model, x):
     """x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> ``path_1`` (B, features, h / 2, w / 2) of a hybrid
     ``ACR(..., seg=True)`` (DPT/DPT.py:274-286); ``SegmentationHead`` turns it into (B, num_classes + 1, h, w) logits.  Other
-    backbones and bf16 raise NotImplementedError.  BatchNorm statistics are per process (see the module docstring)."""
+    backbones and bf16 raise NotImplementedError.  BatchNorm statistics are per process, or those of all ranks after
+    ``nn.SyncBatchNorm.convert_sync_batchnorm`` (see the module docstring)."""
     return fuse(model, *layers_rn(model, x))

@@ -34,7 +34,13 @@ class GradSync:
     parameter without a gradient is zeroed before its bucket leaves (it would otherwise still hold the previous step's
     average), and late gradients are exchanged on their own and ADDED to the averaged slot (re-averaging the whole bucket
     would average already-averaged values with raw ones when the ranks disagree on who was late).
-    ``strict=True`` (or ACR_DP_STRICT=1) turns any disagreement between ranks into an error instead."""
+    ``strict=True`` (or ACR_DP_STRICT=1) turns any disagreement between ranks into an error instead.
+    NARROWER with converted norms: a model whose ``nn.SyncBatchNorm`` layers exchange statistics (``decoder.batch_norm_act``) issues
+    ``all_gather``s on this same group from inside backward, between the bucket all-reduces.  WHERE a bucket leaves (inside
+    backward or from ``finish()``) may differ per rank when gradient presence differs per rank; without gathers that only costs
+    overlap, with them one rank's all-reduce would meet another rank's gather.  Such a model therefore needs the same autograd
+    graph and the same gradient presence on every rank (true for the segmentation step); the guarantee above holds for the
+    all-reduces among themselves only."""
 
     def __init__(self, params, process_group=None, bucket_mb=64, strict=None, always_reduce=False, record_timeline=False,
                  late_params=None, static_graph=False, recheck_every=0):

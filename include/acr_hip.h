@@ -806,6 +806,25 @@ int acr_dense_energy_dot(const float* s, const float* as, int64_t count, float g
  * acr_upsample2x_bwd: dx (planes, H, W), WRITTEN: the adjoint, as a gather per input pixel over exactly the output rows and
  *   columns whose first tap is i - 1 or i (found with the forward's own fp32 index function), summed in ascending order in
  *   double: bit-identical run to run.
+ * Cross-rank statistics (nn.SyncBatchNorm: every rank normalises with the statistics of all ranks' values).  Each direction is
+ *   two entry points with the CALLER'S exchange between them; what is exchanged is a fixed-size double tensor per layer --
+ *   (C, 3) forward, (C, 2) backward -- gathered into W rows in rank order, so the merge order is this library's, the same on
+ *   every rank whatever the collective's algorithm, and every rank computes the same bits.  Ranks may hold different N >= 1 (an empty
+ *   shard is refused like any N < 1); H * W is the same on all.  No pass over a tensor is added: forward x twice, backward x, y, dy twice, as the fused entry points.
+ * acr_bn2d_moments: moments (C, 3) double, WRITTEN: count n = N * HW, mean, M2 = sum (x - mean)^2 of the local tensor, from the
+ *   shifted slab sums a = sum d, b = sum d^2: mean = shift + a / n, M2 = max(b - a^2 / n, 0).  n = 1 is legal (M2 = 0).
+ * acr_bn2d_fwd_merged: gathered (W, C, 3) double, the moments of ranks 0 .. W - 1.  Per channel they are merged in ascending
+ *   rank order by the pairwise update, the only formula used (no difference of sums of squares):
+ *       n = n_a + n_b,  delta = mean_b - mean_a,  mean = mean_a + delta * n_b / n,  M2 = M2_a + M2_b + delta^2 * n_a * n_b / n
+ *   var = M2 / n; the running statistics are updated as acr_bn2d_fwd updates them, with the merged mean and M2 / (n - 1); y as
+ *   acr_bn2d_fwd.  A merged count below 2 returns ACR_ERR_INVALID -- decided on the host from its lower bound N * HW +
+ *   (W - 1) * HW (every rank holds at least one plane), nothing is read back.  stats, 3 C doubles, WRITTEN: (C, 2) mu and invstd
+ *   as acr_bn2d_fwd writes them, then the C merged counts.  1 <= W <= 65536.
+ * acr_bn2d_bwd_sums: stats as acr_bn2d_fwd_merged wrote it.  sums (C, 2) double, WRITTEN: sum g and sum g * xhat of the LOCAL
+ *   tensor under the merged mu / invstd.  dgamma / dbeta (each nullable) are these local sums: the caller averages parameter
+ *   gradients over the ranks afterwards, as it does for every other parameter.
+ * acr_bn2d_bwd_merged: gathered_sums (W, C, 2) double.  The rows are added in ascending rank order and divided by the merged
+ *   count: mean(g), mean(g * xhat) over all ranks; dx and dres as acr_bn2d_bwd with training != 0.
  * The entry points allocate nothing, launch on `stream` and read nothing back; they capture into a hipGraph. */
 int64_t acr_bn2d_ws_bytes(int32_t N, int32_t C, int32_t HW);
 int acr_bn2d_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, const float* resid,
@@ -814,6 +833,15 @@ int acr_bn2d_fwd(const float* x, const float* gamma, const float* beta, float* r
 int acr_bn2d_bwd(const float* x, const float* y, const float* dy, const float* gamma, const double* stats, int32_t N, int32_t C,
                  int32_t HW, int32_t training, int32_t relu, void* ws, int64_t ws_bytes, float* dx, float* dgamma, float* dbeta,
                  float* dres, void* stream);
+int acr_bn2d_moments(const float* x, int32_t N, int32_t C, int32_t HW, void* ws, int64_t ws_bytes, double* moments, void* stream);
+int acr_bn2d_fwd_merged(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                        const float* resid, const float* resid2, int32_t N, int32_t C, int32_t HW, const double* gathered, int32_t W,
+                        double eps, double momentum, int32_t relu, void* ws, int64_t ws_bytes, double* stats, float* y, void* stream);
+int acr_bn2d_bwd_sums(const float* x, const float* y, const float* dy, const double* stats, int32_t N, int32_t C, int32_t HW,
+                      int32_t relu, void* ws, int64_t ws_bytes, double* sums, float* dgamma, float* dbeta, void* stream);
+int acr_bn2d_bwd_merged(const float* x, const float* y, const float* dy, const float* gamma, const double* stats,
+                        const double* gathered_sums, int32_t W, int32_t N, int32_t C, int32_t HW, int32_t relu, void* ws,
+                        int64_t ws_bytes, float* dx, float* dres, void* stream);
 int acr_relu_fwd_f32(const float* x, int64_t n, float* y, void* stream);
 int acr_relu_bwd_f32(const float* y, const float* dy, int64_t n, float* dx, void* stream);
 int acr_upsample2x_fwd(const float* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* y, void* stream);

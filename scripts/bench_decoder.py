@@ -2,14 +2,20 @@
 """Micro-benchmark of the DPT decoder kernels (csrc/decoder.hip) and of one fusion block, forward and backward, at the decoder's
 production width: 16 x 256 x {28^2, 112^2} fp32.
 
-    python scripts/bench_decoder.py [--sizes 28 112] [--repeats 7] [--iters 10]
+    python scripts/bench_decoder.py [--sizes 28 112] [--repeats 7] [--iters 10] [--sync W]
 
 Each entry is timed with device events around ``iters`` calls that ROTATE over enough buffer sets to exceed the 256 MiB Infinity
 Cache (so a 13 MB tensor at 28^2 is not served from cache), repeated ``repeats`` times: the median and the [min, max] range are
 printed.  GB/s are ALGORITHMIC bytes -- what the operation has to move, each tensor once -- over the median; the two-pass
 norm kernels read more than that (x twice in the forward, x and dy twice in the backward) and the table says so.  Every
 hand-written entry runs next to torch's own operator on the same machine, alternating; the fusion block runs next to a plain torch
-composition (nn.BatchNorm2d, F.conv2d, F.relu, F.interpolate) built here.  Needs a GPU: there is no fallback."""
+composition (nn.BatchNorm2d, F.conv2d, F.relu, F.interpolate) built here.  Needs a GPU: there is no fallback.
+
+``--sync W`` times the cross-rank norm's two halves instead, on ONE device: moments -> W device copies of the (C, 3) rows into the
+(W, C, 3) buffer, standing in for the gather -> merged forward, next to the fused ``acr_bn2d_fwd``; and sums -> W copies ->
+merged backward next to the fused ``acr_bn2d_bwd``, all through the C ABI on preallocated buffers.  What it shows is the cost of
+splitting the per-channel finish in two (launches, the extra round trip of the rows); the collective itself is not in it and
+cannot be measured on one GPU."""
 import argparse
 import os
 import statistics
@@ -78,14 +84,62 @@ class TorchFusion(nn.Module):
         return self.out_conv(F.interpolate(out, scale_factor=2, mode="bilinear", align_corners=True))
 
 
+def sync_mode(args):
+    from acr_wsss_amd import _lib as L
+    lib, W = L.load(), args.sync
+    st = L.stream_ptr()
+    for s in args.sizes:
+        tb, hw = 4 * N * C * s * s, s * s
+        R = rotation(3 * tb)
+        print("\n== %d x %d x %d x %d (%.1f MB per tensor, %d rotating buffer sets), W = %d ==" % (N, C, s, s, tb / 1e6, R, W))
+        xs, gs = ([torch.randn(N, C, s, s, device=DEV) for _ in range(R)] for _ in range(2))
+        y, dx = torch.empty_like(xs[0]), torch.empty_like(xs[0])
+        gamma, beta, rm, rv = torch.ones(C, device=DEV), torch.zeros(C, device=DEV), torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+        dgamma, dbeta = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+        ws = torch.empty(lib.acr_bn2d_ws_bytes(N, C, hw), dtype=torch.uint8, device=DEV)
+        f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=DEV)
+        stats2, stats3, moments, gathered, sums, gsums = f64(C, 2), f64(3 * C), f64(C, 3), f64(W, C, 3), f64(C, 2), f64(W, C, 2)
+        p, nb = L.ptr, ws.numel()
+
+        def fwd_fused(i):
+            L.check(lib.acr_bn2d_fwd(p(xs[i % R]), p(gamma), p(beta), p(rm), p(rv), None, None, N, C, hw, 1, 1e-5, 0.1, 0, p(ws), nb, p(stats2),
+                                     p(y), st), "acr_bn2d_fwd")
+
+        def fwd_split(i):
+            L.check(lib.acr_bn2d_moments(p(xs[i % R]), N, C, hw, p(ws), nb, p(moments), st), "acr_bn2d_moments")
+            for r in range(W):
+                gathered[r].copy_(moments)
+            L.check(lib.acr_bn2d_fwd_merged(p(xs[i % R]), p(gamma), p(beta), p(rm), p(rv), None, None, N, C, hw, p(gathered), W, 1e-5, 0.1, 0,
+                                            p(ws), nb, p(stats3), p(y), st), "acr_bn2d_fwd_merged")
+
+        def bwd_fused(i):
+            L.check(lib.acr_bn2d_bwd(p(xs[i % R]), None, p(gs[i % R]), p(gamma), p(stats2), N, C, hw, 1, 0, p(ws), nb, p(dx), p(dgamma),
+                                     p(dbeta), None, st), "acr_bn2d_bwd")
+
+        def bwd_split(i):
+            L.check(lib.acr_bn2d_bwd_sums(p(xs[i % R]), None, p(gs[i % R]), p(stats3), N, C, hw, 0, p(ws), nb, p(sums), p(dgamma), p(dbeta),
+                                          st), "acr_bn2d_bwd_sums")
+            for r in range(W):
+                gsums[r].copy_(sums)
+            L.check(lib.acr_bn2d_bwd_merged(p(xs[i % R]), None, p(gs[i % R]), p(gamma), p(stats3), p(gsums), W, N, C, hw, 0, p(ws), nb, p(dx),
+                                            None, st), "acr_bn2d_bwd_merged")
+        report("bn fwd (train)", timed({"fused": fwd_fused, "split": fwd_split}, args.iters, args.repeats), 2 * tb)
+        report("bn bwd (train)", timed({"fused": bwd_fused, "split": bwd_split}, args.iters, args.repeats), 3 * tb)
+        del xs, gs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[28, 112])
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--sync", type=int, default=0, metavar="W", help="time the cross-rank norm's halves for W ranks instead")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_decoder.py needs a GPU"
     print("device: %s   N x C = %d x %d fp32   repeats %d x iters %d" % (torch.cuda.get_device_name(0), N, C, args.repeats, args.iters))
+    if args.sync:
+        return sync_mode(args)
     for s in args.sizes:
         n = N * C * s * s
         tb = 4 * n                                          # bytes of one (N, C, s, s) tensor
