@@ -15,16 +15,17 @@ import torch.nn.functional as F
 from .. import ops
 from ..backbone import VisionTransformer
 
-# backbone name -> VisionTransformer kwargs, DPT scratch in_shape   (DPT/vit.py:548-632, DPT/blocks.py:26-83)
+# backbone name -> VisionTransformer kwargs, DPT scratch in_shape, the four hooks   (DPT/vit.py:548-632, DPT/blocks.py:26-83,
+# DPT/ACR.py:59-65; the hybrid's hooks 0 and 1 are stem stages, not blocks: backbone.ResNetV2 records them)
 _BACKBONES = {
-    "vitb_rn50_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=True), [256, 512, 768, 768], (8, 11)),
-    "vitb16_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=False), [96, 192, 384, 768], (8, 11)),
-    "deitb16_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=False), [96, 192, 384, 768], (8, 11)),
+    "vitb_rn50_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=True), [256, 512, 768, 768], (0, 1, 8, 11)),
+    "vitb16_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=False), [96, 192, 384, 768], (2, 5, 8, 11)),
+    "deitb16_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=False), [96, 192, 384, 768], (2, 5, 8, 11)),
     "deitb16_distil_384": (dict(embed_dim=768, depth=12, num_heads=12, hybrid=False, distilled=True),
-                           [96, 192, 384, 768], (8, 11)),
-    "vitl16_384": (dict(embed_dim=1024, depth=24, num_heads=16, hybrid=False), [256, 512, 1024, 1024], (17, 23)),
+                           [96, 192, 384, 768], (2, 5, 8, 11)),
+    "vitl16_384": (dict(embed_dim=1024, depth=24, num_heads=16, hybrid=False), [256, 512, 1024, 1024], (5, 11, 17, 23)),
     # BASELINE config 1 (plumbing): ViT-tiny/16 @224 assembled from the same parts
-    "vit_tiny16_224": (dict(embed_dim=192, depth=12, num_heads=3, hybrid=False, img_size=224), [48, 96, 192, 192], (8, 11)),
+    "vit_tiny16_224": (dict(embed_dim=192, depth=12, num_heads=3, hybrid=False, img_size=224), [48, 96, 192, 192], (2, 5, 8, 11)),
 }
 
 
@@ -51,20 +52,22 @@ class DPT(BaseModel):
             assert False
         self.channels_last = channels_last
         self.attention = use_attention
-        vit_kw, scratch_in, (tap3, tap4) = _BACKBONES[backbone]
+        vit_kw, scratch_in, (tap1, tap2, tap3, tap4) = _BACKBONES[backbone]
         # NB use_pretrain: the reference downloads ImageNet weights here (models/helpers.py:177).  There is
         # no network in this build: weights are random-initialised and a checkpoint is loaded via `path`.
         vit = VisionTransformer(**vit_kw)
         vit.tap3, vit.tap4 = tap3, tap4
+        if not vit_kw["hybrid"]:
+            vit.tap1, vit.tap2 = tap1, tap2
         self.pretrained = nn.Module()
         self.pretrained.model = vit
         self.pretrained.activations = {}
         if backbone in ("vitl16_384", "deitb16_384", "deitb16_distil_384") or (seg and backbone == "vitb16_384"):
             # DPT/blocks.py:29-35,62-82 builds these three without `seg=seg`, so DPT/vit.py:263-341 (default seg=True) attaches
-            # the four read-out heads to `pretrained` although ACR never runs them: their 14 tensors are part of every
-            # checkpoint of these backbones.  Created for state-dict compatibility only (indices 3 / 4 of each Sequential hold
-            # the parameters; 0-2 are the parameter-free read-out / transpose / unflatten steps).  vitb16_384 gets them under
-            # seg=True only (blocks.py:51-57).
+            # the four read-out heads to `pretrained` although the ACR forward never runs them: their 14 tensors are part of
+            # every checkpoint of these backbones, and decoder.layers_rn runs them under seg=True (indices 3 / 4 of each
+            # Sequential hold the parameters; 0-2 are the parameter-free read-out / transpose / unflatten steps).  vitb16_384
+            # gets them under seg=True only (blocks.py:51-57).
             D, f = vit.embed_dim, scratch_in
             tails = ([nn.Conv2d(D, f[0], 1), nn.ConvTranspose2d(f[0], f[0], 4, stride=4)],
                      [nn.Conv2d(D, f[1], 1), nn.ConvTranspose2d(f[1], f[1], 2, stride=2)],

@@ -221,6 +221,11 @@ SIGNATURES = {
     "acr_relu_bwd_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "acr_upsample2x_fwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_upsample2x_bwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "acr_reassemble_ws_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "acr_reassemble_fwd": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                     c_void_p]),
+    "acr_reassemble_bwd": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_int64, c_void_p]),
     "acr_segpred_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p]),
 }

@@ -820,6 +820,10 @@ class VisionTransformer(nn.Module):
         for i in range(lo, hi):
             x = self.blocks[i](x, stack, i)
             if taps is not None:
+                if i == self.tap1:                           # a plain ViT's hooks "1", "2" (DPT/vit.py:253-256); the hybrid's are stem stages
+                    taps["1"] = x
+                if i == self.tap2:
+                    taps["2"] = x
                 if i == self.tap3:
                     taps["3"] = x
                 if i == self.tap4:
@@ -890,4 +894,5 @@ class VisionTransformer(nn.Module):
         cache.move_to_end(key)
         return g or None
 
+    tap1, tap2 = None, None
     tap3, tap4 = 8, 11

@@ -10,6 +10,15 @@ __device__ __forceinline__ float acr_wave_sum(float v) {
     return v;
 }
 
+// the sum over W consecutive lanes of a wave (W a power of two up to 64, the group aligned to W) by the same butterfly; every lane of
+// the group gets it
+template <int W>
+__device__ __forceinline__ float acr_lanes_sum(float v) {
+#pragma unroll
+    for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // the sum over a workgroup of NT threads: every wave's sum, then the waves in wave order; sh holds NT / 64 floats
 template <int NT>
 __device__ __forceinline__ float acr_block_sum(float v, float* sh) {

@@ -6,6 +6,9 @@ BatchNorm2d (training and eval; optional fused ReLU and up to two residual adden
 upsampling and the leading ReLU of a residual unit run in csrc/decoder.hip behind ``acr_bn2d_*``, ``acr_upsample2x_*`` and
 ``acr_relu_*`` (include/acr_hip.h states the rules in full); the 3x3 and 1x1 convolutions go through ``ops.conv3x3`` /
 ``ops.conv1x1`` where ``ops.conv3x3_fusable`` / ``ops.conv1x1_fusable`` accept the shape and through ``F.conv2d`` otherwise.
+The read-out heads of the plain ViT backbones (1x1 convolution, then a ``ConvTranspose2d`` whose kernel equals its stride) run as
+two products on the fp32 GEMMs and the token-major -> NCHW depth-to-space shuffle of csrc/reassemble.hip (``readout``,
+``reassemble``; ``acr_reassemble_*``).
 There is no CPU path: a CPU tensor raises ``AcrHipError``.  Forward and backward are bit-identical run to run.
 
 Precision: fp32 tensors under ``math="f32"`` and ``math="f32_split"``; bf16 is not built (``decode`` raises).
@@ -268,6 +271,129 @@ def upsample2x(x):
     return _Upsample2x.apply(_dev32(x, "x"))
 
 
+class _Reassemble(Function):
+    @staticmethod
+    def forward(ctx, y2d, bias, B, T, start, gh, gw, C, s):
+        lib = L.load()
+        dev = y2d.device
+        out = torch.empty((B, C, gh * s, gw * s), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.acr_reassemble_fwd(L.ptr(y2d), y2d.stride(0), L.ptr(bias), B, T, start, gh, gw, C, s, L.ptr(out), L.stream_ptr()),
+                    "acr_reassemble_fwd")
+        ctx.geom = (B, T, start, gh, gw, C, s)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        B, T, start, gh, gw, C, s = ctx.geom
+        dev = dout.device
+        need_b = ctx.has_bias and ctx.needs_input_grad[1]
+        if not (ctx.needs_input_grad[0] or need_b):
+            return (None,) * 9
+        with torch.cuda.device(dev):
+            dout = dout.to(torch.float32).contiguous()
+            dy = torch.empty((B * T, C * s * s), dtype=torch.float32, device=dev)       # every element is written: the skipped rows as zeros
+            dbias = torch.empty(C, dtype=torch.float32, device=dev) if need_b else None
+            ws = torch.empty(lib.acr_reassemble_ws_bytes(B, gh, gw, C, s), dtype=torch.uint8, device=dev) if need_b else None
+            L.check(lib.acr_reassemble_bwd(L.ptr(dout), B, T, start, gh, gw, C, s, L.ptr(dy), dy.stride(0), L.ptr(dbias), L.ptr(ws),
+                                           ws.numel() if ws is not None else 0, L.stream_ptr()), "acr_reassemble_bwd")
+        return (dy if ctx.needs_input_grad[0] else None, dbias) + (None,) * 7
+
+
+def reassemble(y2d, bias, B, T, start, gh, gw, C, s):
+    """Token-major -> NCHW with the depth-to-space shuffle of a ``ConvTranspose2d`` whose kernel equals its stride ``s`` (DPT/vit.py
+    :117-146 with the heads of :263-341): ``y2d`` (B * T, C * s * s) float32 on the GPU, unit inner stride, any row pitch;
+    ``out[b, co, i * s + di, j * s + dj] = y2d[b * T + start + i * gw + j, (co * s + di) * s + dj] + bias[co]`` -> (B, C, gh * s,
+    gw * s).  ``bias`` (C) or None; ``s`` 1, 2 or 4; ``T == start + gh * gw``; the first ``start`` (0 .. 8) tokens of every sample are
+    skipped and receive a zero gradient.  Differentiable in ``y2d`` and ``bias``; forward and backward repeat bit for bit."""
+    if not torch.is_tensor(y2d):
+        raise ValueError("y2d must be a torch tensor on the GPU, got %s" % type(y2d).__name__)
+    L.require_gpu(y2d, bias)
+    B, T, start, gh, gw, C, s = (int(v) for v in (B, T, start, gh, gw, C, s))
+    if s not in (1, 2, 4):
+        raise ValueError("s must be 1, 2 or 4, got %d" % s)
+    if min(B, gh, gw, C) < 1 or not 0 <= start <= 8 or T != start + gh * gw:
+        raise ValueError("need B, gh, gw, C >= 1, 0 <= start <= 8 and T == start + gh * gw, got B=%d T=%d start=%d gh=%d gw=%d C=%d"
+                         % (B, T, start, gh, gw, C))
+    if y2d.dtype != torch.float32 or y2d.dim() != 2 or tuple(y2d.shape) != (B * T, C * s * s) or y2d.stride(1) != 1 or y2d.stride(0) < C * s * s:
+        raise ValueError("y2d must be a (B * T, C * s * s) = (%d, %d) float32 matrix with a unit inner stride, got %s %s strides %s"
+                         % (B * T, C * s * s, y2d.dtype, tuple(y2d.shape), y2d.stride() if y2d.dim() == 2 else None))
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (C,) or bias.device != y2d.device or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous (%d,) float32 tensor on %s, got %s %s" % (C, y2d.device, bias.dtype, tuple(bias.shape)))
+    return _Reassemble.apply(y2d, bias, B, T, start, gh, gw, C, s)
+
+
+class _DeconvProduct(Function):
+    """``y2 (M, f * s * s) = z (M, f) . W.view(f, f * s * s)`` with the ``ConvTranspose2d`` weight (ci, co, s, s) as stored: forward
+    'nn', input gradient 'nt', weight gradient 'tn' of acr_gemm_f32 -- the weight is neither copied nor transposed"""
+    @staticmethod
+    def forward(ctx, z, weight, math):
+        f = weight.shape[0]
+        w2 = weight.view(f, -1)
+        y2 = torch.empty((z.shape[0], w2.shape[1]), dtype=torch.float32, device=z.device)
+        with torch.cuda.device(z.device):
+            ops.gemm_f32_raw("nn", z, w2, y2, math=math)
+        ctx.save_for_backward(z, weight)
+        ctx.math = math
+        return y2
+
+    @staticmethod
+    def backward(ctx, dy2):
+        z, weight = ctx.saved_tensors
+        f = weight.shape[0]
+        w2 = weight.view(f, -1)
+        dy2 = _c16(dy2.to(torch.float32))
+        dz = dw = None
+        with torch.cuda.device(z.device):
+            if ctx.needs_input_grad[0]:
+                dz = torch.empty_like(z)
+                ops.gemm_f32_raw("nt", dy2, w2, dz, math=ctx.math)
+            if ctx.needs_input_grad[1]:
+                dw = torch.empty_like(w2)
+                ops.gemm_f32_raw("tn", z, dy2, dw, math=ctx.math)
+                dw = dw.view(weight.shape)
+        return dz, dw, None
+
+
+def readout(tok, start, gh, gw, conv1, deconv, math=0):
+    """One read-out head of a plain ViT (DPT/vit.py:263-341, run by :117-146) on the tokens ``tok`` (B, T, D) of its hook, ``T ==
+    start + gh * gw``: the 1x1 convolution ``conv1`` (D -> f) as a Linear on ALL tokens (``ops.LinearF32Fn``), then -- for ``deconv``
+    an ``nn.ConvTranspose2d(f, f, s, stride=s)``, s 2 or 4 -- the product with its weight as stored, and ``reassemble`` with its
+    bias -> (B, f, gh * s, gw * s); ``deconv`` None: ``reassemble`` alone (s = 1, no bias) -> (B, f, gh, gw).  ``math``: a
+    ``_lib.MATH`` code; 2 (fp16x2, an opt-in of the block Linears) runs as exact fp32 here."""
+    if not torch.is_tensor(tok):
+        raise ValueError("tok must be a torch tensor on the GPU, got %s" % type(tok).__name__)
+    L.require_gpu(tok)
+    if tok.dtype != torch.float32 or tok.dim() != 3 or tok.numel() == 0:
+        raise ValueError("tok must be a non-empty (B, T, D) float32 tensor, got %s %s" % (tok.dtype, tuple(tok.shape)))
+    B, T, D = tok.shape
+    if not (isinstance(conv1, nn.Conv2d) and conv1.kernel_size == (1, 1) and conv1.stride == (1, 1) and conv1.padding == (0, 0)
+            and conv1.groups == 1 and conv1.in_channels == D):
+        raise ValueError("conv1 must be an nn.Conv2d(%d, f, 1), got %r" % (D, conv1))
+    f, s = conv1.out_channels, 1
+    if deconv is not None:
+        s = deconv.kernel_size[0] if isinstance(deconv, nn.ConvTranspose2d) else 0
+        if not (s in (2, 4) and deconv.kernel_size == (s, s) and deconv.stride == (s, s) and deconv.padding == (0, 0)
+                and deconv.output_padding == (0, 0) and deconv.dilation == (1, 1) and deconv.groups == 1
+                and deconv.in_channels == f and deconv.out_channels == f):
+            raise NotImplementedError("the read-out's second step is an nn.ConvTranspose2d(f, f, s, stride=s) with s 2 or 4 and f = %d, "
+                                      "got %r" % (f, deconv))
+    if T != start + gh * gw:
+        raise ValueError("%d tokens are not %d skipped ones and a %d x %d grid" % (T, start, gh, gw))
+    math = 0 if math == L.MATH["f32_fp16x2"] else int(math)
+    tok = _c16(tok)
+    w1 = conv1.weight.view(f, D)
+    if not ops.linear_f32_usable(tok, w1) or f % 4:
+        raise NotImplementedError("the fp32 GEMMs take D and f that are multiples of 4 and at least 32, got D=%d f=%d" % (D, f))
+    with torch.cuda.device(tok.device):
+        z = ops.LinearF32Fn.apply(tok, w1, conv1.bias, None, None, math).reshape(B * T, f)
+    if deconv is None:
+        return reassemble(z, None, B, T, start, gh, gw, f, 1)
+    return reassemble(_DeconvProduct.apply(z, deconv.weight, math), deconv.bias, B, T, start, gh, gw, f, s)
+
+
 def conv(m, x, math):
     """The ``nn.Conv2d`` ``m`` on x: the hand-written 3x3 / 1x1 kernels where they cover the shape (bias added after), torch's
     convolution otherwise (a stride-2 convolution, channel counts off the tile, a map narrower than 16: the H/32 level at 384^2
@@ -372,16 +498,18 @@ def make_fusion_block(features, use_bn):
 # the decoder pass
 # ------------------------------------------------------------------------------------------------
 def layers_rn(model, x):
-    """``forward_vit`` (DPT/vit.py:103-148) and ``scratch.layerN_rn`` (DPT/DPT.py:274-281) of a hybrid ``seg=True`` model:
-    the four (B, features, h / 4 .. h / 32, ...) maps the fusion blocks take.  Taps 1 and 2 are the stem stages the encoder
-    records; taps 3 and 4 drop the class token (``readout="ignore"``), become (B, D, h / 16, w / 16) and go through
-    ``act_postprocess3`` / ``act_postprocess4``."""
+    """``forward_vit`` (DPT/vit.py:103-148) and ``scratch.layerN_rn`` (DPT/DPT.py:274-281) of a ``seg=True`` model:
+    the four (B, features, h / 4 .. h / 32, ...) maps the fusion blocks take.  Hybrid: taps 1 and 2 are the stem stages the
+    encoder records; taps 3 and 4 drop the class token (``readout="ignore"``), become (B, D, h / 16, w / 16) and go through
+    ``act_postprocess3`` / ``act_postprocess4``.  A plain ViT: ``_layers_rn_plain``.  A model without read-out heads (the
+    project's own ``vit_tiny``) raises NotImplementedError."""
     from .backbone import HybridEmbed
     if not hasattr(model.scratch, "refinenet1"):
         raise ValueError("decode needs a model built with seg=True")
     vit = model.pretrained.model
-    if not isinstance(vit.patch_embed, HybridEmbed):
-        raise NotImplementedError("decode is built for the hybrid backbone; the ConvTranspose2d read-outs of %s are not" % model.cur_backbone)
+    hybrid = isinstance(vit.patch_embed, HybridEmbed)
+    if not hybrid and not all(hasattr(model.pretrained, "act_postprocess%d" % i) for i in (1, 2, 3, 4)):
+        raise NotImplementedError("decode needs the four read-out heads pretrained.act_postprocess1..4; %s has none" % model.cur_backbone)
     if not torch.is_tensor(x):
         raise ValueError("x must be a torch tensor on the GPU, got %s" % type(x).__name__)
     L.require_gpu(x)
@@ -394,6 +522,8 @@ def layers_rn(model, x):
     gh, gw = h // vit.patch_size[1], w // vit.patch_size[0]
     skip = vit.num_tokens                                    # 1: the class token (Slice(start_index=1), DPT/vit.py:57-63)
     math = vit.acr_math
+    if not hybrid:
+        return _layers_rn_plain(model, taps, skip, gh, gw, math)
 
     def grid(tok):
         return tok[:, skip:].transpose(1, 2).reshape(b, tok.shape[2], gh, gw).contiguous()
@@ -402,6 +532,19 @@ def layers_rn(model, x):
     layer_4 = conv(pp.act_postprocess4[4], conv(pp.act_postprocess4[3], grid(taps["4"]), math), math)
     return (conv(sc.layer1_rn, taps["1"].contiguous(), math), conv(sc.layer2_rn, taps["2"].contiguous(), math),
             conv(sc.layer3_rn, layer_3, math), conv(sc.layer4_rn, layer_4, math))
+
+
+def _layers_rn_plain(model, taps, skip, gh, gw, math):
+    """``layers_rn`` of a plain ViT (vitb, deit, deit_distilled, vitl; DPT/vit.py:224-353): every tap is the tokens of a block
+    (hooks DPT/ACR.py:59-65) and goes through ``readout`` -- x4, x2, x1 and, for tap 4, x1 followed by the stride-2 3x3 convolution,
+    which stays on torch's convolution as in the hybrid model.  ``skip`` is 2 for the distilled DeiT (DPT/vit.py:617-632)."""
+    pp, sc = model.pretrained, model.scratch
+    layer_1 = readout(taps["1"], skip, gh, gw, pp.act_postprocess1[3], pp.act_postprocess1[4], math)
+    layer_2 = readout(taps["2"], skip, gh, gw, pp.act_postprocess2[3], pp.act_postprocess2[4], math)
+    layer_3 = readout(taps["3"], skip, gh, gw, pp.act_postprocess3[3], None, math)
+    layer_4 = conv(pp.act_postprocess4[4], readout(taps["4"], skip, gh, gw, pp.act_postprocess4[3], None, math), math)
+    return (conv(sc.layer1_rn, layer_1, math), conv(sc.layer2_rn, layer_2, math), conv(sc.layer3_rn, layer_3, math),
+            conv(sc.layer4_rn, layer_4, math))
 
 
 def fuse(model, l1, l2, l3, l4):
@@ -414,8 +557,9 @@ def fuse(model, l1, l2, l3, l4):
 
 
 def decode(model, x):
-    """x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> ``path_1`` (B, features, h / 2, w / 2) of a hybrid
-    ``ACR(..., seg=True)`` (DPT/DPT.py:274-286); ``SegmentationHead`` turns it into (B, num_classes + 1, h, w) logits.  Other
-    backbones and bf16 raise NotImplementedError.  BatchNorm statistics are per process, or those of all ranks after
+    """x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> ``path_1`` (B, features, h / 2, w / 2) of an
+    ``ACR(..., seg=True)`` with any of the reference's backbones -- vitb_hybrid, vitb, deit, deit_distilled, vitl --
+    (DPT/DPT.py:274-286); ``SegmentationHead`` turns it into (B, num_classes + 1, h, w) logits.  A model without read-out heads
+    (``vit_tiny``) and bf16 raise NotImplementedError.  BatchNorm statistics are per process, or those of all ranks after
     ``nn.SyncBatchNorm.convert_sync_batchnorm`` (see the module docstring)."""
     return fuse(model, *layers_rn(model, x))

@@ -24,7 +24,7 @@ MAX_CLASSES = 128                         # 2 <= K <= 128 (include/acr_hip.h)
 
 def forward_seg(model, head, x):
     """The reference's ``forward_seg`` (:1869): x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> the logits
-    (B, num_classes + 1, h, w) of a hybrid ``ACR(..., seg=True)`` and its ``decoder.SegmentationHead``."""
+    (B, num_classes + 1, h, w) of an ``ACR(..., seg=True)`` (any of the reference's backbones) and its ``decoder.SegmentationHead``."""
     return head(decoder.decode(model, x))
 
 

@@ -847,6 +847,32 @@ int acr_relu_bwd_f32(const float* y, const float* dy, int64_t n, float* dx, void
 int acr_upsample2x_fwd(const float* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* y, void* stream);
 int acr_upsample2x_bwd(const float* dy, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* dx, void* stream);
 
+/* ---- read-out reassembly of the plain ViT backbones under seg=True (vitb, deit, deit_distilled, vitl) ----
+ * The read-out of tap i (DPT/vit.py:263-341, run by forward_vit :117-146; start_index = 2 for the distilled DeiT, :617-632) is
+ * Slice(start) -> Transpose -> Unflatten -> Conv2d(D, f, 1) -> ConvTranspose2d(f, f, s, stride = s) (s = 4, 2; tap 3 has none:
+ * s = 1).  With kernel == stride no two outputs overlap: the transposed convolution is the product
+ *   y2 (B T, C s^2) = z (B T, C) . Wt.view(C, C s^2)          (acr_gemm_f32 'nn', the weight (ci, co, s, s) as stored)
+ * on ALL tokens, followed by what these entry points replace -- :117-146's slice / transpose / unflatten and the scatter of
+ * nn.ConvTranspose2d with its bias:
+ * acr_reassemble_fwd:  out[b][co][i s + di][j s + dj] = y[(b T + start + i gw + j) ldy + (co s + di) s + dj] (+ bias[co]),
+ *   0 <= i < gh, 0 <= j < gw; one fp32 add per element (none for bias == NULL: a copy).  out (B, C, gh s, gw s) contiguous.
+ * acr_reassemble_bwd (their autograd backward): dy[(b T + start + i gw + j) lddy + (co s + di) s + dj] = dout[b][co][i s + di][j s + dj];
+ *   the `start` skipped rows of every sample are WRITTEN with zeros in columns < C s^2; columns >= C s^2 of any row are not
+ *   touched.  dbias (C, nullable) = sum_b sum_pixels dout[b][co]: every tile's sum in a fixed order in fp32, the tiles of a
+ *   channel in a fixed order in double, rounded once; no atomics, bit-identical run to run.  dbias needs ws:
+ *   acr_reassemble_ws_bytes(B, gh, gw, C, s) bytes on the device, 4-byte aligned, contents arbitrary (0 for arguments outside
+ *   the contract).
+ * Contract: s in {1, 2, 4}; T == start + gh gw; 0 <= start <= 8; ldy, lddy >= C s^2 (any value: no alignment is assumed); B, C, gh,
+ *   gw any positive value with gh gw < 2^26, C s^2 < 2^30 and fewer than 2^31 tiles (a tile: 64 columns of y by 32 grid columns of
+ *   one grid row; s = 1: by 64 grid positions).  Anything else returns ACR_ERR_INVALID and launches nothing.
+ * Both directions move contiguous runs on both sides through an LDS tile (csrc/reassemble.hip); edge tiles are masked per element,
+ * nothing outside the tensors is addressed.  The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+size_t acr_reassemble_ws_bytes(int32_t B, int32_t gh, int32_t gw, int32_t C, int32_t s);
+int acr_reassemble_fwd(const float* y, int64_t ldy, const float* bias, int32_t B, int32_t T, int32_t start, int32_t gh, int32_t gw,
+                       int32_t C, int32_t s, float* out, void* stream);
+int acr_reassemble_bwd(const float* dout, int32_t B, int32_t T, int32_t start, int32_t gh, int32_t gw, int32_t C, int32_t s, float* dy,
+                       int64_t lddy, float* dbias, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- segmentation prediction (myTool.py:1826-1895 validation: the resize of the logits to the image's own size :1881, the softmax
  * :1883 and the argmax :1891, or the probabilities _crf_with_alpha_2 :1819-1823 hands to the CRF) in one pass ----
  * logits (B, K, h, w) fp32 contiguous; label (B, H, W) uint8, nullable; probs (B, K, H, W) fp32, nullable; at least one output.

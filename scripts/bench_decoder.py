@@ -15,7 +15,11 @@ composition (nn.BatchNorm2d, F.conv2d, F.relu, F.interpolate) built here.  Needs
 (W, C, 3) buffer, standing in for the gather -> merged forward, next to the fused ``acr_bn2d_fwd``; and sums -> W copies ->
 merged backward next to the fused ``acr_bn2d_bwd``, all through the C ABI on preallocated buffers.  What it shows is the cost of
 splitting the per-channel finish in two (launches, the extra round trip of the rows); the collective itself is not in it and
-cannot be measured on one GPU."""
+cannot be measured on one GPU.
+
+``--readout [--math f32|f32_split]`` times the read-out heads of the plain ViT backbones instead (``readout_mode``): the two
+csrc/reassemble.hip kernels next to a ``copy_`` of the same size, and ``decoder.readout`` forward + backward next to torch's
+operators, per tap shape of vitb and vitl at 384^2, batch 16."""
 import argparse
 import os
 import statistics
@@ -129,8 +133,82 @@ def sync_mode(args):
         torch.cuda.empty_cache()
 
 
+READOUT_SHAPES = {"vitb": (768, [(96, 4), (192, 2), (384, 1), (768, 1)]), "vitl": (1024, [(256, 4), (512, 2), (1024, 1), (1024, 1)])}
+
+
+def readout_mode(args):
+    """Per tap shape of vitb and vitl at 384^2, batch 16 (a 24 x 24 grid, 577 tokens): the two reassemble kernels through the C ABI
+    on preallocated buffers, a plain ``copy_`` of the output's size from the same run (the bandwidth yardstick: it reads and writes
+    what the shuffle has to), the whole ``decoder.readout`` forward + backward, and torch's operator sequence for the same work
+    (slice / transpose / contiguous, ``F.conv2d``, ``F.conv_transpose2d``).  Tap 4's stride-2 3x3 is torch's on both sides and is
+    left out."""
+    from acr_wsss_amd import _lib as L
+    lib, st, p = L.load(), L.stream_ptr(), L.ptr
+    B, gh, gw, start = N, 24, 24, 1
+    T = start + gh * gw
+    math = L.MATH[args.math]
+    for name, (Dm, taps) in READOUT_SHAPES.items():
+        for tap, (f, s) in enumerate(taps, 1):
+            ob = 4 * B * f * gh * s * gw * s                   # bytes of the output map (the token side holds the skipped rows on top)
+            R = rotation(2 * ob)
+            print("\n== %s tap %d: D %d -> f %d, s %d, out %d x %d x %d x %d (%.1f MB, %d rotating buffer sets), math %s =="
+                  % (name, tap, Dm, f, s, B, f, gh * s, gw * s, ob / 1e6, R, args.math))
+            y2 = [torch.randn(B * T, f * s * s, device=DEV) for _ in range(R)]
+            outs = [torch.randn(B, f, gh * s, gw * s, device=DEV) for _ in range(R)]
+            bias, dbias = torch.randn(f, device=DEV), torch.empty(f, device=DEV)
+            nws = lib.acr_reassemble_ws_bytes(B, gh, gw, f, s)
+            ws = torch.empty(nws, dtype=torch.uint8, device=DEV)
+
+            def k_fwd(i):
+                L.check(lib.acr_reassemble_fwd(p(y2[i % R]), f * s * s, p(bias), B, T, start, gh, gw, f, s, p(outs[(i + 1) % R]), st),
+                        "acr_reassemble_fwd")
+
+            def k_bwd(i):
+                L.check(lib.acr_reassemble_bwd(p(outs[i % R]), B, T, start, gh, gw, f, s, p(y2[(i + 1) % R]), f * s * s, p(dbias), p(ws), nws,
+                                               st), "acr_reassemble_bwd")
+
+            def k_copy(i):
+                outs[(i + 1) % R].copy_(outs[i % R])
+            times = timed({"fwd": k_fwd, "bwd": k_bwd, "copy_": k_copy}, args.iters, args.repeats)
+            report("reassemble kernels", times, 2 * ob)
+            med = {k: statistics.median(v) for k, v in times.items()}
+            print("%-34s fwd %.2f, bwd %.2f of the copy_ rate" % ("reassemble / copy_", med["copy_"] / med["fwd"], med["copy_"] / med["bwd"]))
+            del y2
+            conv1 = nn.Conv2d(Dm, f, 1).to(DEV)
+            deconv = nn.ConvTranspose2d(f, f, s, stride=s).to(DEV) if s > 1 else None
+            Rt = max(2, min(R, 4))
+            toks = [torch.randn(B, T, Dm, device=DEV) for _ in range(Rt)]
+            params = list(conv1.parameters()) + (list(deconv.parameters()) if deconv is not None else [])
+
+            def torch_ops(tok):
+                x = tok[:, start:].transpose(1, 2).reshape(B, Dm, gh, gw).contiguous()
+                x = F.conv2d(x, conv1.weight, conv1.bias)
+                return x if deconv is None else F.conv_transpose2d(x, deconv.weight, deconv.bias, stride=s)
+
+            def whole(fn):
+                def run(i):
+                    tok = toks[i % Rt].requires_grad_(True)
+                    fn(tok).backward(outs[i % R])
+                    tok.grad = None
+                    for q in params:
+                        q.grad = None
+                return run
+            with torch.no_grad():
+                a, b = D.readout(toks[0], start, gh, gw, conv1, deconv, math), torch_ops(toks[0])
+                print("readout output, hand-written vs torch's operators: max |diff| %.3e of max %.3e" % (float((a - b).abs().max()), float(b.abs().max())))
+                del a, b
+            times = timed({"hip": whole(lambda tok: D.readout(tok, start, gh, gw, conv1, deconv, math)), "torch": whole(torch_ops)},
+                          max(2, args.iters // 2), args.repeats)
+            for k, v in times.items():
+                print("%-34s %-6s median %9.1f us  [%9.1f, %9.1f]" % ("readout fwd+bwd", k, statistics.median(v), min(v), max(v)))
+            del toks, outs
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--readout", action="store_true", help="time the plain-ViT read-outs (reassemble kernels, readout, torch's operators) instead")
+    ap.add_argument("--math", default="f32_split", choices=["f32", "f32_split"], help="arithmetic of --readout's products")
     ap.add_argument("--sizes", type=int, nargs="+", default=[28, 112])
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
@@ -140,6 +218,8 @@ def main():
     print("device: %s   N x C = %d x %d fp32   repeats %d x iters %d" % (torch.cuda.get_device_name(0), N, C, args.repeats, args.iters))
     if args.sync:
         return sync_mode(args)
+    if args.readout:
+        return readout_mode(args)
     for s in args.sizes:
         n = N * C * s * s
         tb = 4 * n                                          # bytes of one (N, C, s, s) tensor
