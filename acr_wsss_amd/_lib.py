@@ -228,6 +228,9 @@ SIGNATURES = {
                                      c_void_p, c_int64, c_void_p]),
     "acr_segpred_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p]),
+    "acr_train_cam_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "acr_train_cam_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

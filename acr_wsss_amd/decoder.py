@@ -516,9 +516,24 @@ def layers_rn(model, x):
     if x.dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
         raise NotImplementedError("decode is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s input / %s weights"
                                   % (x.dtype, model.cls_head.weight.dtype))
-    b, _, h, w = x.shape
     model._encode(x)
-    taps = model.pretrained.activations
+    return layers_rn_taps(model, model.pretrained.activations, x.shape[2:])
+
+
+def layers_rn_taps(model, taps, hw, rows=None):
+    """The part of ``layers_rn`` after the encoder pass: ``taps`` is what ``model._encode(x)`` left in
+    ``model.pretrained.activations`` for an x of spatial size ``hw`` = (h, w) (``layers_rn`` has checked model and input).
+    ``rows``: take the first ``rows`` samples of every tap -- a step that ran both views as one 2B batch (``forward_mirror``)
+    decodes view 1 from it, ``rows`` = B."""
+    from .backbone import HybridEmbed
+    vit = model.pretrained.model
+    hybrid = isinstance(vit.patch_embed, HybridEmbed)
+    if rows is not None:
+        if not 1 <= rows <= taps["4"].shape[0]:
+            raise ValueError("rows=%r outside 1..%d, the batch of the pass" % (rows, taps["4"].shape[0]))
+        taps = {k: taps[k][:rows] for k in ("1", "2", "3", "4")}
+    h, w = hw
+    b = taps["4"].shape[0]
     gh, gw = h // vit.patch_size[1], w // vit.patch_size[0]
     skip = vit.num_tokens                                    # 1: the class token (Slice(start_index=1), DPT/vit.py:57-63)
     math = vit.acr_math
@@ -563,3 +578,17 @@ def decode(model, x):
     (``vit_tiny``) and bf16 raise NotImplementedError.  BatchNorm statistics are per process, or those of all ranks after
     ``nn.SyncBatchNorm.convert_sync_batchnorm`` (see the module docstring)."""
     return fuse(model, *layers_rn(model, x))
+
+
+def decode_taps(model, taps, hw, rows=None):
+    """``decode`` from an encoder pass that has already run: ``taps`` = ``model.pretrained.activations`` after ``model._encode(x)``
+    (``forward_cls``, ``forward_cam``, ``forward_mirror``) on a float32 x of spatial size ``hw``; ``rows`` as in
+    ``layers_rn_taps``.  On the taps of ``decode``'s own pass the result is ``decode``'s, bit for bit."""
+    if not hasattr(model.scratch, "refinenet1"):
+        raise ValueError("decode needs a model built with seg=True")
+    if any(k not in taps for k in ("1", "2", "3", "4")):
+        raise ValueError("taps holds %s: run the encoder pass first (the four taps \"1\" .. \"4\")" % sorted(taps))
+    if taps["4"].dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
+        raise NotImplementedError("decode is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s taps / %s weights"
+                                  % (taps["4"].dtype, model.cls_head.weight.dtype))
+    return fuse(model, *layers_rn_taps(model, taps, hw, rows))

@@ -42,6 +42,70 @@ def seg_train_step(model, head, optimizer, images, ori_images, croppings, seg_la
     return loss, dict(celoss=celoss, dloss=dloss, loss=loss)
 
 
+def joint_targets(model, labels, saliency, hw, *, cam_kw=None, label_kw=None):
+    """The segmentation targets of a ``forward_mirror`` pass that has just run (its 2B batch: view 1, then the h-flipped view 2),
+    without grad: the tap-4 tokens of both views -- ``vit.num_tokens`` leading tokens skipped, so the distilled DeiT yields a grid
+    too -- through ``ops.patch_cam`` (DPT/ACR.py:133-134), ``traincam.training_cams`` (view 2 mirrored back and added, min-max
+    normalised) and ``saliency_labels``.  Returns (seg_label, saliency_out)."""
+    from . import traincam
+    vit = model.pretrained.model
+    with torch.no_grad():
+        tok = model.pretrained.activations["4"].detach()           # (2B, T, D), contiguous
+        n2, T, D = tok.shape
+        B = n2 // 2
+        cams = ops.patch_cam(tok.reshape(n2 * T, D), model.cls_head.weight.detach(), model.cls_head.bias.detach()).view(n2, T, -1)
+        skip = vit.num_tokens
+        norm_cam = traincam.training_cams(cams[:B, skip:], labels, hw, patch_cam_flipped=cams[B:, skip:],
+                                          grid=(hw[0] // vit.patch_size[1], hw[1] // vit.patch_size[0]), **(cam_kw or {}))
+        return saliency_labels(norm_cam, labels, saliency, **(label_kw or {}))
+
+
+def joint_train_step(model, head, optimizer, images, ori_images, croppings, labels, saliency, dense_energy_layer, *, alpha,
+                     seg_weight=1.0, batch_average=False, grad_sync=None, cam_kw=None, label_kw=None):
+    """One single-stage iteration on a ``get_data_from_chunk_v3`` batch: the classifier's own CAMs become the segmentation head's
+    targets in the same step, over ONE 2B encoder pass (the loop ``_v3`` and ``compute_seg_label_3`` are written for; the
+    reference tree holds no script that runs it, the composition is this project's).
+      ``optimizer.zero_grad`` -> ``model.forward_mirror(images, images.flip(-1))`` (``train.train_step``'s pass) ->
+      ``train.acr_loss`` -> targets without grad (``joint_targets``: tap-4 tokens of both views -> ``ops.patch_cam`` ->
+      ``traincam.training_cams`` -> ``saliency_labels``) -> ``head(decoder.decode_taps(first B rows))`` -> ``segloss.joint_loss``
+      (``split_cross_entropy`` alone when ``dense_energy_layer`` is None) -> ``loss = acr + seg_weight * (celoss + dloss)`` ->
+      one backward (``grad_sync.prepare`` / ``finish`` around it as in the other steps) -> ``optimizer.step`` ->
+      ``refresh_weight_transposes(model)``, ``ops.invalidate_weight_images(head)``.
+    images (B,3,S,S) float32 on the GPU (S a multiple of 32), ori_images, croppings as in ``seg_train_step``; labels (B,C) the
+    image-level labels; saliency (B,S,S) uint8.  ``cam_kw`` goes to ``training_cams`` (eps), ``label_kw`` to ``saliency_labels``
+    (bg_alpha, cut, open_size).  bf16 raises NotImplementedError as ``decode`` does.  Returns (loss, terms): the four ACR terms
+    (cls_loss_1, cls_loss_2, cls_align, aff_align), acr_loss, celoss, dloss, loss, and seg_label / saliency_out for inspection."""
+    from . import decoder
+    from .train import acr_loss
+    if images.dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
+        raise NotImplementedError("joint_train_step is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s input / %s weights"
+                                  % (images.dtype, model.cls_head.weight.dtype))
+    if not hasattr(model.scratch, "refinenet1"):
+        raise ValueError("joint_train_step needs a model built with seg=True")
+    hw = tuple(images.shape[2:])
+    optimizer.zero_grad(set_to_none=True)
+    cls_list, attn_list = model.forward_mirror(images, images.flip(-1))
+    acr, terms = acr_loss(cls_list, attn_list, labels, hw[0] // 16, alpha)
+    seg_label, saliency_out = joint_targets(model, labels, saliency, hw, cam_kw=cam_kw, label_kw=label_kw)
+    logits = head(decoder.decode_taps(model, model.pretrained.activations, hw, rows=images.shape[0]))
+    if dense_energy_layer is None:
+        celoss = segloss.split_cross_entropy(logits, seg_label, batch_average)[0]
+        dloss = torch.zeros((), dtype=celoss.dtype, device=celoss.device)
+    else:
+        celoss, dloss = segloss.joint_loss(ori_images, logits, seg_label, croppings, batch_average, dense_energy_layer)
+    loss = acr + seg_weight * (celoss + dloss)
+    if grad_sync is not None:
+        grad_sync.prepare()
+    loss.backward()
+    if grad_sync is not None:
+        grad_sync.finish()
+    optimizer.step()
+    refresh_weight_transposes(model)
+    ops.invalidate_weight_images(head)
+    terms = dict(terms, acr_loss=acr, celoss=celoss, dloss=dloss, loss=loss, seg_label=seg_label, saliency_out=saliency_out)
+    return loss, terms
+
+
 def saliency_labels(norm_cam, labels, saliency, **kw):
     """The pseudo-labels of a ``get_data_from_chunk_v3`` batch while training runs: norm_cam (B, C, S, S) float32 normalised CAMs
     (``forward_cam``), labels (B, C) the image-level labels of the batch (any real dtype; the reference's

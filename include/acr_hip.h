@@ -897,6 +897,40 @@ int acr_reassemble_bwd(const float* dout, int32_t B, int32_t T, int32_t start, i
 int acr_segpred_f32(const float* logits, int32_t B, int32_t K, int32_t h, int32_t w, int32_t H, int32_t W, int32_t hflip,
                     int32_t accumulate, float* probs, uint8_t* label, void* stream);
 
+/* ---- training-time CAM targets (compute_cam_up, myTool.py:860-864: the patch CAMs of forward_cam upsampled to the crop and
+ * multiplied by the image-level label; with normalize, the two-view sum and min-max normalisation infer_cam.py:156-162, 201-202
+ * applies to patch CAMs) -- the (B, C, oh, ow) tensor acr_sal_pseudo_compose takes as `cams`, made while training runs ----
+ * cam1 fp32 patch CAMs of view 1, token-major (B, gh * gw, C): element (b, t, c) lies at cam1[b * batch_stride + t * tok_stride +
+ *   c] (strides in elements, >= 0; the class stride is 1), so a slice of a (B, T, C) tensor that skips the class / distillation
+ *   tokens is passed as it lies.  cam2, nullable: the CAMs of the H-FLIPPED view, same geometry and strides.  label (B, C) fp32
+ *   contiguous: the multipliers.  out (B, C, oh, ow) fp32 contiguous; every element is WRITTEN exactly once.
+ * Rule, all in fp32, the operations and their order as written (the build has -ffp-contract=off):
+ *   up(src)[y, x]: torch's upsample_bilinear2d with align_corners=False, the rule of acr_bilinear_resize (csrc/acr_resample.h:
+ *     scale = in / out, src = max(scale * (dst + 0.5) - 0.5, 0), i0 = min((int)src, in - 1), lambda = src - i0, i1 = i0 + (i0 < in - 1),
+ *     v = hy * (hx * p[y0][x0] + lx * p[y0][x1]) + ly * (hx * p[y1][x0] + lx * p[y1][x1])) for any gh, gw, oh, ow >= 1;
+ *   l = label[b][c];
+ *   s[y, x] = up(cam1)[y, x] * l                                       without cam2,
+ *   s[y, x] = up(cam1)[y, x] * l + up(cam2)[y, ow - 1 - x] * l         with cam2: view 2 enters at the mirrored OUTPUT column, as
+ *     acr_bilinear_resize's hflip + accumulate does it (np.flip of the upsampled map, infer_cam.py:159-160) -- not at mirrored
+ *     taps, which differ in the last bit;
+ *   normalize == 0: out = s (compute_cam_up for the whole batch);
+ *   normalize == 1: out = (s - mn) / ((mx - mn) + eps), mn and mx the minimum and maximum of s over the UPSAMPLED plane
+ *     (infer_cam.py:202), not of the source: with half-pixel sampling an enlargement never hits an interior texel centre, so the
+ *     plane's maximum lies below the source's.  min / max are exact in any order: the result does not depend on the launch geometry.
+ *   A plane with l == 0 is written as +0 WITHOUT READING ITS SOURCE -- the one deviation from v * 0, which a non-finite source
+ *   value would turn into NaN (and the normalisation of a plane of zeros gives 0 / eps = +0 anyway).
+ * Requires B, C, gh, gw, oh, ow >= 1, B * C <= 2^22, gh * gw < 2^31, oh * ow < 2^31, eps > 0, normalize 0 or 1; anything else
+ *   returns ACR_ERR_INVALID and launches nothing.  Present planes hold finite values (NaN is outside the contract).
+ * ws: acr_train_cam_ws_bytes(B, C, oh, ow) bytes on the device, 4-byte aligned, contents arbitrary; used (and required) with
+ *   normalize == 1 only.  acr_train_cam_ws_bytes: host only; negative for arguments outside the supported range.
+ * 16-byte stores where ow is a multiple of 4 and out is 16-byte aligned, 4-byte stores otherwise.  No atomics, nothing outside the
+ * tensors is read or written: bit-identical run to run.  The entry point allocates nothing and does not synchronise; it captures
+ * into a hipGraph. */
+int64_t acr_train_cam_ws_bytes(int32_t B, int32_t C, int32_t oh, int32_t ow);
+int acr_train_cam_f32(const float* cam1, const float* cam2, int64_t tok_stride, int64_t batch_stride, const float* label, int32_t B,
+                      int32_t C, int32_t gh, int32_t gw, int32_t oh, int32_t ow, float eps, int32_t normalize, void* ws,
+                      int64_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
