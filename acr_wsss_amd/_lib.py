@@ -231,6 +231,17 @@ SIGNATURES = {
     "acr_train_cam_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "acr_train_cam_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "acr_aff_pairs": (c_int32, [c_int32]),
+    "acr_aff_pair_codes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "acr_aff_loss_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "acr_aff_loss_fwd": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int64, c_void_p, c_void_p]),
+    "acr_aff_loss_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "acr_aff_walk_weights": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.c_double, c_void_p, c_void_p]),
+    "acr_aff_walk_resident": (c_int32, [c_int32, c_int32, c_int32]),
+    "acr_aff_walk_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "acr_aff_walk": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                               c_int64, c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

@@ -931,6 +931,76 @@ int acr_train_cam_f32(const float* cam1, const float* cam2, int64_t tok_stride, 
                       int32_t C, int32_t gh, int32_t gw, int32_t oh, int32_t ow, float eps, int32_t normalize, void* ws,
                       int64_t ws_bytes, float* out, void* stream);
 
+/* ---- affinity stage (PSA, Ahn & Kwak CVPR 2018): pair labels (tool/torchutils.py:107-157 ExtractAffinityLabelInRadius, fed by
+ * AffinityFromMaskDataset :159-173 and voc12/data.py:222-278 VOC12AffDataset), pair geometry (tool/pyutils.py:125-159
+ * get_indices_of_pairs), and -- this project's own statement of PSA's definitions, which the reference expects around them -- the
+ * pair affinity, its loss with gradient, and the random walk ----
+ * Geometry: radius R (2..5; the reference's default 5), r = R - 1.  Offsets (dy, dx) in the reference's order: (0, x) for
+ *   x = 1 .. r, then for y = 1 .. r, x = -r .. r: (y, x) where x^2 + y^2 < R^2; P = acr_aff_pairs(R) of them (34 for R = 5; -1 for
+ *   a radius outside 2..5; host only).  On an h x w grid the from-pixels are rows [0, h - r) and columns [r, w - r):
+ *   N = (h - r)(w - 2 r); from-index n = yy (w - 2 r) + xx is pixel (yy, r + xx), its partner under offset p is
+ *   (yy + dy, r + xx + dx) -- flat index to = from + dy w + dx.  Requires h > r, w > 2 r, h, w <= 4096, 1 <= B <= 65535;
+ *   anything else returns ACR_ERR_INVALID and launches nothing.
+ * acr_aff_pair_codes: label_map (B, S0, S1) uint8 on the device: class ids, 255 = ignore.  The grid is the map subsampled by
+ *   `stride` -- g[y][x] = map[stride y][stride x], h = S0 / stride, w = S1 / stride; this rule IS the definition of the
+ *   reference's RescaleNearest(0.125) here (stride 8); S0 and S1 must be multiples of stride; stride 1 takes a grid-sized map.
+ *   The subsampled map never exists.  With lf = g(from), lt = g(to), codes (B, P, N) uint8, WRITTEN:
+ *       1  bg-pos  lf == lt == 0
+ *       2  fg-pos  lf == lt, lf != 0, both < 255
+ *       3  neg     lf != lt, both < 255
+ *       0  none    otherwise
+ *   so that (codes == k) are the three float masks of ExtractAffinityLabelInRadius.  counts int64[3] on the device, WRITTEN
+ *   (cleared on the stream first): the batch totals of codes 1, 2, 3 -- 64-bit integer atomics, exact in any order.
+ * acr_aff_loss_fwd: feat (B, C, h, w) fp32 contiguous.  With eps = 1e-5:
+ *       d[b,p,n] = (1 / C) sum_c |feat[b,c,from] - feat[b,c,to]|,   aff = exp(-d)
+ *       bg  = sum_{code 1} -log(aff + eps)     / (counts[0] + eps)
+ *       fg  = sum_{code 2} -log(aff + eps)     / (counts[1] + eps)
+ *       neg = sum_{code 3} -log(1 + eps - aff) / (counts[2] + eps)
+ *       loss = bg / 4 + fg / 4 + neg / 2
+ *   the counts those of the whole batch, as acr_aff_pair_codes left them on the device.  aff (B, P, N) fp32, nullable, WRITTEN;
+ *   g (B, P, N) fp32, WRITTEN: d loss / d d -- (1/4) aff / (aff + eps) / (counts[k-1] + eps) for codes k = 1, 2,
+ *   -(1/2) aff / (1 + eps - aff) / (counts[2] + eps) for code 3, 0 for code 0; loss4 = (loss, bg, fg, neg) fp32, WRITTEN.  A term
+ *   without a pair is exactly 0.  codes == NULL is the inference forward: only aff is written (counts, g, ws, loss4 unused).
+ *   Every value is evaluated in double -- the differences, the channel sum (channels ascending), exp, log -- and rounded to
+ *   fp32 once; the three sums are double: a thread's pairs in offset order, the LDS tree of its 16 x 16 tile, the tiles
+ *   ascending.  ws: acr_aff_loss_ws_bytes(B, h, w, R) bytes on the device, 8-byte aligned, contents arbitrary (host only;
+ *   negative for arguments outside the contract).  1 <= C <= 2^20.
+ * acr_aff_loss_bwd: dfeat (B, C, h, w), WRITTEN (every element) = gscale[0] * d loss / d feat, gscale one fp32 value on the
+ *   device (the upstream gradient).  Gather form, no atomics: a pixel sums, offsets ascending, g * sign(f_me - f_partner) / C
+ *   over the pairs it starts (partner at +offset) and the pairs that end in it (partner at -offset, where that pixel is a
+ *   from-pixel), in double; sign(0) = 0, as torch's abs has it.
+ *   Both directions stage 8 channels of a 16 x 16 tile's rows and columns (with the halo of r) in LDS per round and keep the P
+ *   (forward) or 2 P (backward) per-pixel values in registers; nothing with a C x P extent exists.
+ * acr_aff_walk_weights: the symmetric A has A[i][j] = A[j][i] = aff^beta for every listed pair (i, j), A[i][i] = 1, 0 otherwise;
+ *   T[i][j] = A[i][j] / sum_k A[k][j].  wt (B, 2 P + 1, h w) fp32, WRITTEN: for pixel j tap 0 = T[j][j], tap 1 + 2 p = T[i][j]
+ *   with i = j + offset p (the pair j starts), tap 2 + 2 p = T[i][j] with i = j - offset p (the pair that ends in j); 0 where
+ *   there is no such pair.  pow, the column sum (1, then the taps ascending) and the division in double.  beta > 0.
+ * acr_aff_walk: scores (B, K, h, w) fp32 -> out = scores . T^steps (out is not scores), as `steps` gathers
+ *       new[j] = sum_t wt[t][j] * old[i_t(j)]          (taps ascending, in double, rounded to fp32 once per step)
+ *   the K planes of an image independent under its T.  resident = 1: one launch, one workgroup per (image, plane), the plane
+ *   ping-ponged in LDS -- needs acr_aff_walk_resident(h, w, R) == 1 (two planes of h w + 2 (r w + r) floats within 64 KiB; host
+ *   only); resident = 0: one launch per step on planes in ws through the same step function -- the two forms agree bit for
+ *   bit; resident = -1 chooses, and chooses the stepwise form: it spreads every plane over all CUs and was the faster one at
+ *   every plane count measured, the resident form runs on request.  ws (used by the stepwise form only):
+ *   acr_aff_walk_ws_bytes(B, K, h, w, R) bytes on the device, 4-byte aligned, cleared here on the stream (host only; negative
+ *   for arguments outside the contract).  B * K <= 65535, 0 <= steps <= 2^20; steps = 0 copies.  Scores are finite: a tap of
+ *   weight 0 is multiplied, not skipped.
+ * No float atomics, fixed orders, nothing outside the tensors is read or written: bit-identical run to run, and a sample's result
+ * does not depend on its batch.  The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+int32_t acr_aff_pairs(int32_t R);
+int acr_aff_pair_codes(const uint8_t* label_map, int32_t B, int32_t S0, int32_t S1, int32_t stride, int32_t R, uint8_t* codes,
+                       int64_t* counts, void* stream);
+int64_t acr_aff_loss_ws_bytes(int32_t B, int32_t h, int32_t w, int32_t R);
+int acr_aff_loss_fwd(const float* feat, int32_t B, int32_t C, int32_t h, int32_t w, int32_t R, const uint8_t* codes,
+                     const int64_t* counts, float* aff, float* g, void* ws, int64_t ws_bytes, float* loss4, void* stream);
+int acr_aff_loss_bwd(const float* feat, const float* g, const float* gscale, int32_t B, int32_t C, int32_t h, int32_t w, int32_t R,
+                     float* dfeat, void* stream);
+int acr_aff_walk_weights(const float* aff, int32_t B, int32_t h, int32_t w, int32_t R, double beta, float* wt, void* stream);
+int32_t acr_aff_walk_resident(int32_t h, int32_t w, int32_t R);
+int64_t acr_aff_walk_ws_bytes(int32_t B, int32_t K, int32_t h, int32_t w, int32_t R);
+int acr_aff_walk(const float* wt, const float* scores, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t R,
+                 int32_t steps, int32_t resident, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
