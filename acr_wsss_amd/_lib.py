@@ -242,6 +242,11 @@ SIGNATURES = {
     "acr_aff_walk_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "acr_aff_walk": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                c_int64, c_void_p]),
+    "acr_featdis_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "acr_featdis_fwd": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acr_featdis_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                  c_void_p]),
 }
 
 # acr_option (include/acr_hip.h): the kernel-variant selector of the library's explicit option table, name -> code.  Set through

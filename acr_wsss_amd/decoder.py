@@ -488,6 +488,13 @@ class SegmentationHead(nn.Sequential):
         x = batch_norm_act(conv(self[0], x, self.acr_math), self[1], "relu")
         return self[5](conv(self[4], self[3](x), self.acr_math))
 
+    def forward_features(self, x):
+        """(logits, feat, logits_half): ``forward``'s logits by the same calls, ``feat`` the tensor the 1x1 classifier ``self[4]``
+        reads and ``logits_half`` that classifier's output before the x2 upsampling -- what ``featdis.feature_distance_loss`` takes."""
+        feat = self[3](batch_norm_act(conv(self[0], x, self.acr_math), self[1], "relu"))
+        logits_half = conv(self[4], feat, self.acr_math)
+        return self[5](logits_half), feat, logits_half
+
 
 def make_fusion_block(features, use_bn):
     """DPT/ACR.py:15-23"""

@@ -9,28 +9,38 @@ saliency map instead of a label, ``saliency_labels`` makes the label on the way 
 reference's ``_v3`` loader is written for)."""
 import torch
 
-from . import ops, pseudo, segloss, segval
+from . import featdis, ops, pseudo, segloss, segval
 from .train import refresh_weight_transposes
 
 
 def seg_train_step(model, head, optimizer, images, ori_images, croppings, seg_label, dense_energy_layer, *, batch_average=False,
-                   grad_sync=None):
+                   grad_sync=None, dis_weight=0.0):
     """``optimizer.zero_grad`` -> ``forward_seg(model, head, images)`` -> ``joint_loss`` -> ``loss = celoss + dloss`` -> backward ->
     ``optimizer.step``.  images (B,3,S,S) float32 on the GPU (S a multiple of 32), ori_images (B,3,S,S) values 0..255, croppings
     (S,S,B), seg_label (B,S,S) uint8 (255 = ignore) -- the loader's tuple; ``optimizer`` holds the parameters of ``model`` and
     ``head`` that are to train.  ``dense_energy_layer``: a ``segloss.DenseEnergyLoss``, or None for the cross-entropy alone (dloss
     is then 0).  ``batch_average`` is ``joint_loss``'s ``criterion_batch_average``.  ``grad_sync`` (``dp.GradSync``) all-reduces the
     gradients while backward runs, as in ``train.train_step``.  After the update the cached split-product weight images and weight
-    transposes of model and head are renewed: the fused optimizer writes the weights in place.  Returns (loss, terms) with terms =
-    dict(celoss, dloss, loss)."""
+    transposes of model and head are renewed: the fused optimizer writes the weights in place.  ``dis_weight`` > 0 adds
+    ``dis_weight * featdis.feature_distance_loss(logits_half, feat)`` on the head's own tensors (``head.forward_features``: the
+    features its classifier reads and the logits before the x2 upsampling); at 0 the step makes the calls it made without the
+    argument.  Returns (loss, terms) with terms = dict(celoss, dloss, loss), and disloss when ``dis_weight`` > 0."""
     optimizer.zero_grad(set_to_none=True)
-    logits = segval.forward_seg(model, head, images)
+    if dis_weight > 0:
+        from . import decoder
+        logits, feat, logits_half = head.forward_features(decoder.decode(model, images))
+    else:
+        logits = segval.forward_seg(model, head, images)
     if dense_energy_layer is None:
         celoss = segloss.split_cross_entropy(logits, seg_label, batch_average)[0]
         dloss = torch.zeros((), dtype=celoss.dtype, device=celoss.device)
     else:
         celoss, dloss = segloss.joint_loss(ori_images, logits, seg_label, croppings, batch_average, dense_energy_layer)
     loss = celoss + dloss
+    terms = dict(celoss=celoss, dloss=dloss)
+    if dis_weight > 0:
+        terms["disloss"] = featdis.feature_distance_loss(logits_half, feat)
+        loss = loss + dis_weight * terms["disloss"]
     if grad_sync is not None:
         grad_sync.prepare()
     loss.backward()
@@ -39,7 +49,7 @@ def seg_train_step(model, head, optimizer, images, ori_images, croppings, seg_la
     optimizer.step()
     refresh_weight_transposes(model)
     ops.invalidate_weight_images(head)
-    return loss, dict(celoss=celoss, dloss=dloss, loss=loss)
+    return loss, dict(terms, loss=loss)
 
 
 def joint_targets(model, labels, saliency, hw, *, cam_kw=None, label_kw=None):
@@ -61,7 +71,7 @@ def joint_targets(model, labels, saliency, hw, *, cam_kw=None, label_kw=None):
 
 
 def joint_train_step(model, head, optimizer, images, ori_images, croppings, labels, saliency, dense_energy_layer, *, alpha,
-                     seg_weight=1.0, batch_average=False, grad_sync=None, cam_kw=None, label_kw=None):
+                     seg_weight=1.0, batch_average=False, grad_sync=None, cam_kw=None, label_kw=None, dis_weight=0.0):
     """One single-stage iteration on a ``get_data_from_chunk_v3`` batch: the classifier's own CAMs become the segmentation head's
     targets in the same step, over ONE 2B encoder pass (the loop ``_v3`` and ``compute_seg_label_3`` are written for; the
     reference tree holds no script that runs it, the composition is this project's).
@@ -73,8 +83,11 @@ def joint_train_step(model, head, optimizer, images, ori_images, croppings, labe
       ``refresh_weight_transposes(model)``, ``ops.invalidate_weight_images(head)``.
     images (B,3,S,S) float32 on the GPU (S a multiple of 32), ori_images, croppings as in ``seg_train_step``; labels (B,C) the
     image-level labels; saliency (B,S,S) uint8.  ``cam_kw`` goes to ``training_cams`` (eps), ``label_kw`` to ``saliency_labels``
-    (bg_alpha, cut, open_size).  bf16 raises NotImplementedError as ``decode`` does.  Returns (loss, terms): the four ACR terms
-    (cls_loss_1, cls_loss_2, cls_align, aff_align), acr_loss, celoss, dloss, loss, and seg_label / saliency_out for inspection."""
+    (bg_alpha, cut, open_size).  bf16 raises NotImplementedError as ``decode`` does.  ``dis_weight`` > 0 adds
+    ``dis_weight * featdis.feature_distance_loss(logits_half, feat)`` (``head.forward_features``) to the loss, beside the
+    ``seg_weight`` term; at 0 the step makes the calls it made without the argument.  Returns (loss, terms): the four ACR terms
+    (cls_loss_1, cls_loss_2, cls_align, aff_align), acr_loss, celoss, dloss, loss, disloss when ``dis_weight`` > 0, and seg_label /
+    saliency_out for inspection."""
     from . import decoder
     from .train import acr_loss
     if images.dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
@@ -87,13 +100,20 @@ def joint_train_step(model, head, optimizer, images, ori_images, croppings, labe
     cls_list, attn_list = model.forward_mirror(images, images.flip(-1))
     acr, terms = acr_loss(cls_list, attn_list, labels, hw[0] // 16, alpha)
     seg_label, saliency_out = joint_targets(model, labels, saliency, hw, cam_kw=cam_kw, label_kw=label_kw)
-    logits = head(decoder.decode_taps(model, model.pretrained.activations, hw, rows=images.shape[0]))
+    decoded = decoder.decode_taps(model, model.pretrained.activations, hw, rows=images.shape[0])
+    if dis_weight > 0:
+        logits, feat, logits_half = head.forward_features(decoded)
+    else:
+        logits = head(decoded)
     if dense_energy_layer is None:
         celoss = segloss.split_cross_entropy(logits, seg_label, batch_average)[0]
         dloss = torch.zeros((), dtype=celoss.dtype, device=celoss.device)
     else:
         celoss, dloss = segloss.joint_loss(ori_images, logits, seg_label, croppings, batch_average, dense_energy_layer)
     loss = acr + seg_weight * (celoss + dloss)
+    if dis_weight > 0:
+        terms = dict(terms, disloss=featdis.feature_distance_loss(logits_half, feat))
+        loss = loss + dis_weight * terms["disloss"]
     if grad_sync is not None:
         grad_sync.prepare()
     loss.backward()

@@ -1001,6 +1001,49 @@ int64_t acr_aff_walk_ws_bytes(int32_t B, int32_t K, int32_t h, int32_t w, int32_
 int acr_aff_walk(const float* wt, const float* scores, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t R,
                  int32_t steps, int32_t resident, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- class-centre feature-distance loss (myTool.py:1616-1710 compute_dis_no_batch with compute_cos: the feature-clustering term
+ * of the single-stage recipe) ----
+ * seg (B, K, h, w) fp32 logits and feat (B, C, h, w) fp32, both contiguous; N = h w, eps = 1e-7.  The reference hard-codes the
+ * classes 1..20; here they are 1..K-1, K = 21 reproduces it.
+ *   lab[b,n] = the first index of the maximum of seg[b,:,n], a NaN counting as the maximum (torch.argmax).  The loss is not
+ *     differentiable in seg.  n_b = #{n : lab[b,n] = 0} per image, m_i = #{(b,n) : lab[b,n] = i} over the batch, i >= 1.
+ *   background centre per image   c_b = sum_{n in bg(b)} f_n / (n_b + eps)   (the zero vector when n_b = 0);
+ *   foreground centre over the batch   g_i = sum_{n in i} f_n / (m_i + eps)   for the classes with m_i >= 1: F of them, ordered
+ *     by class;   cos(x, y) = x . y / (|x| |y| + eps).
+ *   pixel_dis = [ sum_b T_b + sum_{i present} (sum_{n in i} (1 - cos(f_n, g_i))) / (m_i + eps) ] / (F + B),
+ *     T_b = (sum_{n in bg(b)} (1 - cos(f_n, c_b))) / (n_b + eps) when n_b >= 1, T_b = 2 when n_b = 0.
+ *   ff = [sum_{i != j} (1 + cos(g_i, g_j))] / (F (F - 1)) when F > 1, else 0;  fb = the mean over the F x B matrix of
+ *     1 + cos(g_i, c_b), an image without background contributing 1 per entry.
+ *   dis = ff / 2 + fb / 2 with at least one foreground and one background pixel in the batch; ff / 2 + 1 with no background
+ *     pixel at all; 0 with no foreground pixel.
+ *   loss = dis + pixel_dis.  Its gradient in feat is that of this expression with d|x|/dx := 0 at x = 0 (torch's rule for norm).
+ *     At an all-zero feature vector the denominator is eps, so that pixel's gradient is of order 1 / eps: the reference's
+ *     behaviour, kept.  The divisors n + eps are formed in double (the reference forms them in fp32, where 1 + 1e-7 rounds to
+ *     1 + 2^-23).
+ * In closed form, with k the centre of pixel n (centre r < B: the background of image r; centre B + i - 1: class i; NC = B + K - 1),
+ * D_n = |f_n| |c_k| + eps, Z = F + B and cnt' = count_k + eps:
+ *     d_feat[b,:,n] = g_out (a_n c_k + b_n f_n + G_k / cnt'),   a_n = -1 / (Z cnt' D_n),
+ *     b_n = (f_n . c_k) |c_k| / (Z cnt' |f_n| D_n^2)   (0 at |f_n| = 0),   G_k = d loss / d c_k.
+ * acr_featdis_fwd: loss (3) fp32 = (dis + pixel_dis, dis, pixel_dis); labels (B, h, w) uint8; counts (B + K - 1) int64: n_b per
+ *   image, then m_i per class i = 1..K-1; pix (B, N, 2) double: (a_n, b_n); cst (2, NC, C) double: the centres c_k, then
+ *   G_k / cnt' (0 for a centre without a pixel).  All WRITTEN, every element; labels, pix and cst are what acr_featdis_bwd takes.
+ *   Every value is evaluated in double and rounded once.  Sums: per slab of 2048 ceil(K / 32) pixels of an image, per class and
+ *   channel, the pixels ascending; then the slabs in (image, slab) order, as eight consecutive runs whose sums are added in order; channel
+ *   sums in channel order, by fixed quarters or by a fixed butterfly.
+ *   The forward reads feat three times (class sums; dot products; the class sums weighted by 1 / D_n that G_k needs -- the
+ *   re-read form, the weight of a pixel being known only after its dot product), the backward once.
+ *   ws: acr_featdis_ws_bytes(B, K, C, h, w) bytes on the device, 16-byte aligned, contents arbitrary (host only; negative for
+ *   arguments outside the contract).  The slab partials in it are [slabs][K][C] doubles: 2 K / (2048 ceil(K / 32)) <= 1/32 of feat.
+ * acr_featdis_bwd: dfeat (B, C, h, w), WRITTEN (every element) = gscale[0] * d loss / d feat, gscale one fp32 value on the device.
+ * Contract: 1 <= B <= 65535, 2 <= K <= 128, 1 <= C <= 2^20, h, w >= 1, B h w < 2^31; anything else returns ACR_ERR_INVALID and
+ * launches nothing.  No float atomics, fixed orders: bit-identical run to run.  The entry points allocate nothing and do not
+ * synchronise. */
+int64_t acr_featdis_ws_bytes(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w);
+int acr_featdis_fwd(const float* seg, const float* feat, int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, void* ws,
+                    int64_t ws_bytes, float* loss, uint8_t* labels, int64_t* counts, double* pix, double* cst, void* stream);
+int acr_featdis_bwd(const float* feat, const uint8_t* labels, const double* pix, const double* cst, const float* gscale, int32_t B,
+                    int32_t K, int32_t C, int32_t h, int32_t w, float* dfeat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
