@@ -242,6 +242,7 @@ SIGNATURES = {
     "acr_aff_walk_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "acr_aff_walk": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                c_int64, c_void_p]),
+    "acr_aff_label_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acr_featdis_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "acr_featdis_fwd": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),

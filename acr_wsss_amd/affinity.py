@@ -5,6 +5,8 @@ tool/torchutils.py:107-157, pair geometry ``get_indices_of_pairs``, tool/pyutils
 the indices and expects PSA's loss and random walk around them; their statement here is this project's own
 (include/acr_hip.h, "affinity stage", has every rule in full).
 
+  ``aff_label``      the two score stacks of an image -> the label grid of ``VOC12AffDataset`` (csrc/affdata.hip; the batched, cropped
+                     and flipped form is ``data.AffTrainBatcher`` / ``ChunkLoader.get_data_from_chunk_aff``)
   ``pair_codes``     label map -> one code per pixel pair (1 bg-pos, 2 fg-pos, 3 neg, 0 none) and the batch counts
   ``pair_affinity``  feat (B, C, h, w) -> aff = exp(-mean_c |f_from - f_to|), (B, P, N); no grad
   ``aff_loss``       the three-term loss on aff, differentiable in feat
@@ -79,6 +81,56 @@ def pair_codes(label_map, radius=5, stride=8):
         L.check(lib.acr_aff_pair_codes(L.ptr(label_map), B, S0, S1, stride, int(radius), L.ptr(codes), L.ptr(counts), L.stream_ptr()),
                 "acr_aff_pair_codes")
     return codes, counts
+
+
+def aff_label(la, ha, *, box=None):
+    """The label grid of ONE image out of its two CRF score stacks (``VOC12AffDataset.__getitem__``, voc12/data.py:251-275;
+    include/acr_hip.h, "affinity-stage input"): ``la`` / ``ha`` the low- / high-alpha scores, each an (n, h, w) float32 device tensor
+    (what ``crf.crf_with_alpha_device`` returns) or a {key: (h, w)} dict of device tensors or arrays (what the dumps hold; both dicts
+    with the same keys in the same order; host planes go to the current GPU).  With ``box=None`` the image is taken whole: the result
+    is the (ceil(h / 8), ceil(w / 8)) uint8 label of the image zero-padded to multiples of 8, as ``block_reduce`` pads.  ``box`` =
+    (SH, SW, cont_top, cont_left, img_top, img_left, ch, cw, flip) is an ``acr_pre_image`` geometry in a SH x SW container (flip, then
+    crop) -> (SH / 8, SW / 8).  A stride-1 grid for ``pair_codes``; plane indices, 0 and 255, not class ids."""
+    from . import data as D
+
+    def stack(s, who):
+        if isinstance(s, dict):
+            keys, planes = list(s.keys()), [v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v)) for v in s.values()]
+            if len(planes) < D.AFF_MIN_PLANES:
+                raise ValueError("%s: %d planes, need at least %d" % (who, len(planes), D.AFF_MIN_PLANES))
+            if any(p.dim() != 2 or p.shape != planes[0].shape or p.device != planes[0].device for p in planes):
+                raise ValueError("%s: every plane must be (h, w) like the first, on one device" % who)
+            return keys, torch.stack(planes)
+        if not torch.is_tensor(s) or s.dim() != 3:
+            raise ValueError("%s must be an (n, h, w) tensor or a {key: (h, w)} dict" % who)
+        return None, s
+    (kl, la), (kh, ha) = stack(la, "la"), stack(ha, "ha")
+    if (kl is not None and kh is not None and kl != kh) or la.shape != ha.shape:
+        raise ValueError("la (keys %s, %s) and ha (keys %s, %s) differ" % (kl, tuple(la.shape), kh, tuple(ha.shape)))
+    if la.dtype != torch.float32 or ha.dtype != torch.float32:
+        raise ValueError("scores must be float32, got %s and %s" % (la.dtype, ha.dtype))
+    n, h, w = la.shape
+    if not D.AFF_MIN_PLANES <= n <= D.AFF_MAX_PLANES or h == 0 or w == 0:
+        raise ValueError("%d planes of %d x %d outside %d..%d non-empty planes" % (n, h, w, D.AFF_MIN_PLANES, D.AFF_MAX_PLANES))
+    if box is None:
+        box = ((h + 7) // 8 * 8, (w + 7) // 8 * 8, 0, 0, 0, 0, h, w, 0)
+    SH, SW, ct, cl, it, il, ch, cw, flip = (int(v) for v in box)
+    rec = np.zeros(1, D.PRE_IMAGE)
+    rec[0] = (0, h, w, h, w, flip, ct, cl, it, il, ch, cw, 0)
+    D._check_aff_records(rec, [(h, w)], SH, SW)
+    if (kl is not None and not la.is_cuda) or (kh is not None and not ha.is_cuda):      # host planes of a dump: to the GPU
+        if not torch.cuda.is_available():
+            raise L.AcrHipError("aff_label needs a GPU (no CPU path in the product)")
+        dev = la.device if la.is_cuda else ha.device if ha.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        la, ha = (la.to(dev) if kl is not None else la), (ha.to(dev) if kh is not None else ha)
+    L.require_gpu(la, ha)
+    if la.device != ha.device:
+        raise ValueError("la on %s and ha on %s do not belong together" % (la.device, ha.device))
+    buf = torch.cat((la.reshape(-1), ha.reshape(-1)))
+    label = D.aff_label_launch(buf, rec, [0], [4 * n * h * w], [n], SH, SW)
+    out = label[0]
+    out._acr_keep = label._acr_keep
+    return out
 
 
 def pair_affinity(feat, radius=5):
@@ -236,7 +288,8 @@ def aff_train_step(model, head, optimizer, images, label_map, radius=5):
     """``optimizer.zero_grad`` -> ``decoder.layers_rn(model, images)`` -> ``head`` -> ``pair_codes(label_map, radius, stride)`` ->
     ``aff_loss`` -> backward -> ``optimizer.step`` -> the cached weight images of model and head renewed, as in
     ``segtrain.seg_train_step``.  images (B, 3, S, S') float32 on the GPU (multiples of 32), label_map (B, S, S') uint8 at image
-    size (stride 8) or at the head's grid (stride 1).  Returns (loss, bg, fg, neg)."""
+    size (stride 8) or at the head's grid (stride 1).  The label of ``ChunkLoader.get_data_from_chunk_aff`` is a stride-1 grid.
+    Returns (loss, bg, fg, neg)."""
     from . import decoder, ops
     from .train import refresh_weight_transposes
     optimizer.zero_grad(set_to_none=True)

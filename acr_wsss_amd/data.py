@@ -20,6 +20,11 @@ Segmentation training (myTool.py:1257-1310 `get_data_from_chunk_v4`: image + tar
 puts a single-channel uint8 map through the image's own resize (nearest) / flip / crop: `preprocess_seg_batch`, `SegTrainBatcher`
 and `ChunkLoader.get_data_from_chunk_v4 / _v3` give images, the de-normalised uint8 `ori_images`, the `croppings` masks and the map
 from ONE launch (`acr_preprocess_seg_batch`), on the device and shaped for `segloss.joint_loss`.
+
+Affinity training (voc12/data.py:222-278 `VOC12AffDataset`: image + the two CRF score dumps) crops and flips the 2n score planes with
+the image, pools them 8 x 8 and reduces them to the label grid the pair masks are cut from: `preprocess_aff_batch`, `AffTrainBatcher`
+and `ChunkLoader.get_data_from_chunk_aff` give images (the existing `acr_preprocess_batch`) and that label (ONE launch of
+`acr_aff_label_batch`), shaped for `affinity.aff_train_step`.
 """
 import concurrent.futures
 import ctypes
@@ -263,6 +268,141 @@ class SegTrainBatcher(TrainBatcher):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Affinity-stage training input: image + the label grid cut from the two CRF score dumps (voc12/data.py:241-278)
+# ------------------------------------------------------------------------------------------------------------------
+AFF_MIN_PLANES, AFF_MAX_PLANES = 2, 81
+
+
+def score_planes(s, who="scores"):
+    """One score dump as ``acr_aff_label_batch`` takes it: a {key: (h, w) float32} dict (what ``infer_cam_list(out_crf=...)`` writes:
+    key 0 the background, then class + 1) or an (n, h, w) float32 stack -> (keys or None, (n, h, w) float32 C-contiguous numpy array,
+    the planes in the dict's own order).  Raises ValueError for anything else: nothing is cast."""
+    if isinstance(s, dict):
+        keys, planes = list(s.keys()), [np.asarray(v) for v in s.values()]
+        if len(planes) < AFF_MIN_PLANES:
+            raise ValueError("%s: %d planes, need at least %d (background and one class)" % (who, len(planes), AFF_MIN_PLANES))
+        for k, p in zip(keys, planes):
+            if p.dtype != np.float32 or p.ndim != 2:
+                raise ValueError("%s[%r] must be a (h, w) float32 array, got %s %s" % (who, k, p.dtype, p.shape))
+            if p.shape != planes[0].shape:
+                raise ValueError("%s[%r] is %s, the first plane %s" % (who, k, p.shape, planes[0].shape))
+        a = np.stack(planes)
+    else:
+        keys, a = None, np.asarray(s)
+        if a.dtype != np.float32:
+            raise ValueError("%s must be float32, got %s" % (who, a.dtype))
+        if a.ndim != 3:
+            raise ValueError("%s must be an (n, h, w) stack or a {key: (h, w)} dict, got shape %s" % (who, a.shape))
+    if not AFF_MIN_PLANES <= a.shape[0] <= AFF_MAX_PLANES or a.size == 0:
+        raise ValueError("%s: %d planes of %s outside %d..%d non-empty planes" % (who, a.shape[0], a.shape[1:], AFF_MIN_PLANES, AFF_MAX_PLANES))
+    return keys, np.ascontiguousarray(a)
+
+
+def score_pair(la, ha, hw=None, who="scores"):
+    """The low- and the high-alpha dump of one image -> their two (n, h, w) float32 stacks, after the checks the kernel relies on: the
+    same keys in the same order, the same n, and planes of ``hw`` (the image's size) where that is given."""
+    kl, a = score_planes(la, who + " la")
+    kh, b = score_planes(ha, who + " ha")
+    if (kl is not None and kh is not None and kl != kh) or a.shape != b.shape:
+        raise ValueError("%s: the low-alpha dump (keys %s, %s) and the high-alpha dump (keys %s, %s) differ" % (who, kl, a.shape, kh, b.shape))
+    if hw is not None and tuple(a.shape[1:]) != tuple(hw):
+        raise ValueError("%s: planes of %s for an image of %s" % (who, a.shape[1:], tuple(hw)))
+    return a, b
+
+
+def aff_record(h, w, S, cont_top, cont_left, img_top, img_left, ch, cw, flip):
+    """The PRE_IMAGE record (no resize) of the reference's joint crop-THEN-flip: the box is the one ``get_random_crop_box``
+    (tool/imutils.py:167-190; ``random_crop_boxes`` here) draws on the unflipped image, the flip is ``np.fliplr`` of the S-wide
+    container.  The record describes flip-then-crop, so a flip mirrors the box: cont_left' = S - cont_left - cw,
+    img_left' = w - img_left - cw."""
+    if flip:
+        cont_left, img_left = S - cont_left - cw, w - img_left - cw
+    return (0, h, w, h, w, int(bool(flip)), cont_top, cont_left, img_top, img_left, ch, cw, 0)
+
+
+def _check_aff_records(records, shapes, SH, SW):
+    """What acr_aff_label_batch trusts about its table: one record per image, no resize, both boxes inside image and container."""
+    if len(records) != len(shapes) or len(shapes) == 0:
+        raise ValueError("need one record per image (got %d score pairs, %d records)" % (len(shapes), len(records)))
+    if SH <= 0 or SW <= 0 or SH % 8 or SW % 8 or SH > 32768 or SW > 32768:
+        raise ValueError("container %r x %r must be multiples of 8 up to 32768" % (SH, SW))
+    for rec, (h, w) in zip(records, shapes):
+        ok = (rec["h"] == h and rec["w"] == w and rec["rh"] == h and rec["rw"] == w and rec["flip"] in (0, 1) and rec["ch"] >= 0 and rec["cw"] >= 0
+              and 0 <= rec["cont_top"] and rec["cont_top"] + rec["ch"] <= SH and 0 <= rec["cont_left"] and rec["cont_left"] + rec["cw"] <= SW
+              and 0 <= rec["img_top"] and rec["img_top"] + rec["ch"] <= h and 0 <= rec["img_left"] and rec["img_left"] + rec["cw"] <= w)
+        if not ok:
+            raise L.AcrHipError("acr_aff_label_batch: inconsistent geometry record %s for planes of %s in a %d x %d container" % (rec, (h, w), SH, SW))
+
+
+def aff_label_launch(scores, records, la_off, ha_off, n_planes, SH, SW):
+    """Run acr_aff_label_batch on ``scores``, a device buffer that holds every image's two stacks at the byte offsets ``la_off`` /
+    ``ha_off``: the table, the offsets and the plane counts go up in one pinned copy, one launch writes the (B, SH / 8, SW / 8) uint8
+    label.  The callers have validated records and offsets (``_check_aff_records``, ``score_pair``)."""
+    B, device = len(records), scores.device
+    n32 = np.zeros(B + (B & 1), "<i4")                      # int32 counts, padded to whole int64 words of the table's tail
+    n32[:B] = n_planes
+    tail = np.concatenate([np.asarray(la_off, "<i8"), np.asarray(ha_off, "<i8"), n32.view("<i8")])
+    table = _upload_table(records, np.zeros(B, "<i8"), device, extra=tail)
+    base = B * PRE_IMAGE.itemsize
+    label = torch.empty((B, SH // 8, SW // 8), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        L.check(L.load().acr_aff_label_batch(L.ptr(scores), L.ptr(table), L.ptr(table[base:]), L.ptr(table[base + 8 * B:]),
+                                             L.ptr(table[base + 16 * B:]), B, SH, SW, L.ptr(label), L.stream_ptr()), "acr_aff_label_batch")
+    label._acr_keep = (scores, table)
+    return label
+
+
+def preprocess_aff_batch(images_uint8, la, ha, records, S, device, dtype=torch.float32):
+    """The affinity stage's batch under given geometry records (PRE_IMAGE, no resize: rh = h, rw = w; ``aff_record`` writes them):
+    ``images_uint8`` = list of (h, w, 3) uint8 RGB arrays, ``la`` / ``ha`` = per image the low- / high-alpha score dict or (n, h, w)
+    float32 stack.  Images go through the existing ``preprocess_batch`` (an identity resize has integer sample positions and weights
+    0 / 1, hence exact values; the zero padding after the normalisation is the recipe's fill), all scores through ONE pinned
+    staging buffer, one H2D copy and one ``acr_aff_label_batch`` launch (include/acr_hip.h, "affinity-stage input").  Returns
+    ``(images (B, 3, S, S), label (B, S / 8, S / 8) uint8)`` on the device; ``label`` is a stride-1 grid for ``affinity.pair_codes``.
+    Everything is validated on the host before any device is asked for."""
+    if not (len(images_uint8) == len(la) == len(ha)):
+        raise ValueError("need one low- and one high-alpha dump per image (got %d images, %d, %d)" % (len(images_uint8), len(la), len(ha)))
+    if int(S) <= 0 or int(S) % 32:
+        raise ValueError("crop size %r must be a positive multiple of 32" % (S,))
+    _check_images("acr_aff_label_batch", images_uint8, records, S)
+    stacks = [score_pair(l, h, a.shape[:2], "image %d" % i) for i, (a, l, h) in enumerate(zip(images_uint8, la, ha))]
+    _check_aff_records(records, [a.shape[:2] for a in images_uint8], S, S)
+    device = _cuda_device("acr_aff_label_batch", device)
+    images = preprocess_batch(images_uint8, records, S, device, dtype)
+    flat = [s.view(np.uint8).reshape(-1) for pair in stacks for s in pair]
+    offs, stage, packed = _upload_packed(flat, device)
+    label = aff_label_launch(packed, records, offs[0::2], offs[1::2], [p[0].shape[0] for p in stacks], S, S)
+    label._acr_keep += (stage,)                             # the staging buffer must outlive the asynchronous copy
+    return images, label
+
+
+class AffTrainBatcher(TrainBatcher):
+    """``VOC12AffDataset.__getitem__`` (voc12/data.py:241-278) under PSA's transforms -- joint RandomCrop(S) and RandomHorizontalFlip,
+    Normalize + HWC_to_CHW on the image, AvgPool2d(8) on the scores -- for a chunk of decoded images and their two score dumps.
+    Flip and box are drawn as ``TrainBatcher`` draws them, without its resize draw: per image ``uniform(0, 1) > 0.5`` from the numpy
+    generator, then ``random_crop_boxes`` (w before h) from Python's; the box is mirrored where a flip was drawn (``aff_record``).
+    ColorJitter is not part of this."""
+
+    def draw(self, h, w):
+        flip_p = self.nprandom.uniform(0, 1)
+        return aff_record(h, w, self.S, *random_crop_boxes(h, w, self.S, self.pyrandom), flip_p > 0.5)
+
+    def __call__(self, images_uint8, la, ha, records=None):
+        """images_uint8: list of (h, w, 3) uint8 RGB arrays; la, ha: per image the low- / high-alpha {key: (h, w)} dict or (n, h, w)
+        float32 stack.  ``records``: a PRE_IMAGE array to replay instead of drawing.  Returns (images (B, 3, S, S), label
+        (B, S / 8, S / 8) uint8) on the device."""
+        if records is None:
+            for a in images_uint8:                           # before any draw: a refused chunk leaves the generators alone
+                if getattr(a, "ndim", 0) != 3:
+                    raise ValueError("every image must be a (h, w, 3) array, got %s" % (getattr(a, "shape", None),))
+            records = np.zeros(len(images_uint8), PRE_IMAGE)
+            for i, a in enumerate(images_uint8):
+                records[i] = self.draw(int(a.shape[0]), int(a.shape[1]))
+        self.last_records = records
+        return preprocess_aff_batch(images_uint8, la, ha, records, self.S, self.device, self.dtype)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # The reference's own call contract: names in, tensors out (myTool.py:1158-1199, :1364-1403)
 # ------------------------------------------------------------------------------------------------------------------
 def decode_rgb(path):
@@ -281,6 +421,11 @@ def decode_map(path):
         return np.asarray(im)
 
 
+def load_score_dump(path):
+    """One ``<out_crf>_<alpha>/<name>.npy`` file -> its {key: (h, w) float32} dict (voc12/data.py:248-249)."""
+    return np.load(path, allow_pickle=True).item()
+
+
 class ChunkLoader:
     """`get_data_from_chunk_v2(chunk, args)` / `get_data_from_chunk_val(chunk, args)` for a training process that must not
     wait for its input: files are read and decoded by a small thread pool, geometry is drawn on the host in the reference's
@@ -296,12 +441,18 @@ class ChunkLoader:
     With `map_dir` (and `map_ext`, default ".png") the loader also serves segmentation training:
         images, ori_images, labels, croppings, names, target = loader.get_data_from_chunk_v4(chunk)    # or _v3: saliency maps
         for batch in loader.iterate(chunks, kind="v4"): ...
-    where the map of image <name> is <map_dir>/<name><map_ext> and `map_fill` is what the map holds outside the crop box."""
+    where the map of image <name> is <map_dir>/<name><map_ext> and `map_fill` is what the map holds outside the crop box.
+
+    With `la_dir` and `ha_dir` (the ``<out_crf>_<low_alpha>`` / ``<out_crf>_<high_alpha>`` folders ``infer_cam_list`` writes) it serves
+    the affinity stage (voc12/data.py:222-278 VOC12AffDataset; `cls_labels` is not read on this path):
+        images, label, names = loader.get_data_from_chunk_aff(chunk)
+        for images, label, names in loader.iterate(chunks, kind="aff"): ..."""
 
     def __init__(self, img_dir, cls_labels, crop_size, device="cuda", seed=None, workers=8, dtype=torch.float32, ext=".jpg",
-                 with_ori=False, map_dir=None, map_ext=".png", map_fill=0):
+                 with_ori=False, map_dir=None, map_ext=".png", map_fill=0, la_dir=None, ha_dir=None):
         self.img_dir, self.S, self.ext, self.with_ori = img_dir, crop_size, ext, with_ori
         self.map_dir, self.map_ext, self.map_fill = map_dir, map_ext, map_fill
+        self.la_dir, self.ha_dir, self._aff = la_dir, ha_dir, None
         self._seg_batchers = {}
         self.device, self.dtype = torch.device(device), dtype
         if isinstance(cls_labels, (str, os.PathLike)):
@@ -382,13 +533,46 @@ class ChunkLoader:
         self._seg_batcher("v3")
         return self._finish_seg(chunk, self._submit_seg(chunk), "v3")
 
+    # ---- affinity stage: image + the label grid of its two CRF score dumps (voc12/data.py:241-278) ----
+    def _aff_batcher(self):
+        """The AffTrainBatcher of this loader, drawing from the loader's two generators"""
+        if self.la_dir is None or self.ha_dir is None:
+            raise ValueError("get_data_from_chunk_aff needs ChunkLoader(la_dir=..., ha_dir=...)")
+        if self._aff is None:
+            self._aff = AffTrainBatcher(self.S, self.device, None, self.dtype)
+            self._aff.pyrandom, self._aff.nprandom = self.batcher.pyrandom, self.batcher.nprandom
+        return self._aff
+
+    def _submit_aff(self, chunk):
+        return (self._submit(chunk), [self.pool.submit(load_score_dump, os.path.join(self.la_dir, name + ".npy")) for name in chunk],
+                [self.pool.submit(load_score_dump, os.path.join(self.ha_dir, name + ".npy")) for name in chunk])
+
+    def _finish_aff(self, chunk, futures):
+        decoded, la, ha = ([f.result() for f in fs] for fs in futures)
+        images, label = self._aff_batcher()(decoded, la, ha)
+        return images, label, list(chunk)
+
+    def get_data_from_chunk_aff(self, chunk):
+        """voc12/data.py:241-278 for a chunk of names -> (images (B,3,S,S), label (B,S/8,S/8) uint8, name_list), the tensors on the
+        device: the image <img_dir>/<name><ext> and the pickled score dicts <la_dir>/<name>.npy and <ha_dir>/<name>.npy, read by the
+        worker threads, through ``AffTrainBatcher``.  ``label`` is a stride-1 grid: ``affinity.aff_train_step(model, head, optimizer,
+        images, label)`` takes it as it is."""
+        self._aff_batcher()
+        return self._finish_aff(chunk, self._submit_aff(chunk))
+
     def iterate(self, chunks, train=True, depth=2, kind="v2"):
         """Yield the batches of `chunks` in order while the pool already decodes the next `depth` chunks (the previous step's
         GPU work and this thread's Python run meanwhile; the RNG draws stay in chunk order because they happen here).  ``kind``:
-        "v2" (classification: get_data_from_chunk_v2 / _val) or "v3" / "v4" (the segmentation tuples; training only)."""
+        "v2" (classification: get_data_from_chunk_v2 / _val), "v3" / "v4" (the segmentation tuples; training only) or "aff" (the
+        affinity stage's; training only)."""
         chunks = list(chunks)
         if kind == "v2":
             submit, finish = self._submit, lambda c, f: self._finish(c, f, train)
+        elif kind == "aff":
+            self._aff_batcher()
+            if not train:
+                raise ValueError("kind='aff' has no validation form; use train=True")
+            submit, finish = self._submit_aff, self._finish_aff
         else:
             self._seg_batcher(kind)
             if not train:

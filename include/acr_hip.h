@@ -1001,6 +1001,39 @@ int64_t acr_aff_walk_ws_bytes(int32_t B, int32_t K, int32_t h, int32_t w, int32_
 int acr_aff_walk(const float* wt, const float* scores, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t R,
                  int32_t steps, int32_t resident, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- affinity-stage input (voc12/data.py:241-278 VOC12AffDataset.__getitem__ under PSA's transforms: the joint RandomCrop(S) --
+ * tool/imutils.py:167-190 get_random_crop_box, :201-225 random_crop -- and RandomHorizontalFlip :239-246, then AvgPool2d(8)
+ * :228-236 on the scores): the label grid the pair masks are cut from, out of the two CRF score dumps ----
+ * Per image, with n planes per dump (n_planes[b], 2..81; plane 0 the background, then class + 1 in the dicts' own key order):
+ *   1. stack    the n low-alpha planes, then the n high-alpha planes: 2 n planes of (h, w) fp32.
+ *   2. crop     into a zero container of SH x SW: container pixel (y, x) is "inside" when cont_top <= y < cont_top + ch and
+ *               cont_left <= x < cont_left + cw, and then holds pixel (ry, rx) = (img_top + y - cont_top, img_left + x - cont_left)
+ *               of the FLIPPED planes, i.e. column w - 1 - rx of the stored ones when flip is set; every other pixel is 0.  This is
+ *               the acr_pre_image record's own meaning (flip, then crop) with rh = h and rw = w: no resize.  The reference crops and
+ *               then flips the container (np.fliplr); that equals this form with the box mirrored, cont_left' = S - cont_left - cw
+ *               and img_left' = w - img_left - cw, which is what the caller writes into the record when it draws a flip.
+ *   3. pool     the mean over each 8 x 8 block of the container, per plane: the exact sum of the 64 values times 1 / 64, rounded to
+ *               fp32 once.  Summed in double in a fixed order: a column's rows ascending, then the 8 columns by a butterfly (xor 1,
+ *               2, 4).  For values that are 0 or in [2^-20, 1] that sum is exact in any order.
+ *   4. no score where the maximum over all 2 n pooled planes < 1e-5f, compared in fp32.
+ *   5. argmax   la over the first n pooled planes, ha over the last n; the first maximum wins; a plane INDEX 0 .. n - 1, not a class
+ *               id (the pair masks test only equality, 0 and 255).  Scores are finite.
+ *   6. label    = la; 255 where la == 0; then 0 where ha == 0; then 255 where there is no score (data.py:268-275).
+ * label_u8 (batch, SH / 8, SW / 8) uint8, WRITTEN, every element: the grid ExtractAffinityLabelInRadius(cropsize // 8) takes, i.e.
+ * acr_aff_pair_codes' label_map at stride 1.
+ * scores: one device buffer; image b's low-alpha stack, n_planes[b] contiguous (h, w) fp32 planes, starts at BYTE offset la_off[b],
+ * its high-alpha stack at ha_off[b] (both multiples of 4).  table: `batch` acr_pre_image records on the device, unchanged (their
+ * offset field is not read); la_off, ha_off (int64) and n_planes (int32): device arrays of `batch` entries.  SH and SW are separate
+ * so that a whole uncropped image is the record cont = img = (0, 0), ch = h, cw = w in a container of its size rounded up to
+ * multiples of 8: the zero padding of skimage's block_reduce.
+ * One launch per batch.  Every score element inside the crop box is read exactly once, in wave-wide runs of 256 contiguous bytes
+ * along x (4-byte loads: an image row starts at any 4-byte boundary); nothing outside the box is addressed.  The kernel trusts the
+ * table and the offsets: the caller validates them.  Contract: 1 <= batch <= 65535, SH and SW multiples of 8 up to 32768; anything
+ * else returns ACR_ERR_INVALID and launches nothing.  No atomics, no workspace, plain stores: bit-identical run to run.  The entry
+ * point allocates nothing and does not synchronise; it captures into a hipGraph. */
+int acr_aff_label_batch(const void* scores, const void* table, const int64_t* la_off, const int64_t* ha_off, const int32_t* n_planes,
+                        int32_t batch, int32_t SH, int32_t SW, uint8_t* label_u8, void* stream);
+
 /* ---- class-centre feature-distance loss (myTool.py:1616-1710 compute_dis_no_batch with compute_cos: the feature-clustering term
  * of the single-stage recipe) ----
  * seg (B, K, h, w) fp32 logits and feat (B, C, h, w) fp32, both contiguous; N = h w, eps = 1e-7.  The reference hard-codes the
