@@ -290,6 +290,16 @@ def check(rc, what):
         raise AcrHipError("%s failed (%d): %s" % (what, rc, load().acr_last_error().decode()))
 
 
+def workspace(query, *dims, device, dtype=torch.uint8):
+    """(tensor, nbytes) of the workspace the size query ``query`` (an ``acr_*_ws_bytes``) asks for at ``dims``: allocated on
+    ``device`` as ``dtype`` elements.  A negative answer is the library's refusal and raises with its message, before anything
+    is allocated."""
+    nbytes = getattr(load(), query)(*dims)
+    if nbytes < 0:
+        check(-1, query)
+    return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=device), nbytes
+
+
 def stream_ptr():
     """Raw hipStream_t of torch's current stream (kernels are enqueued there; graph-capturable)."""
     return c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -20,9 +20,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _args as A
 from . import _lib as L
 
 MIN_RADIUS, MAX_RADIUS = 2, 5
+_BCHW = ("B", "C", "h", "w")
 
 
 def search_dist(radius):
@@ -46,26 +48,16 @@ def _geometry(h, w, radius):
     return len(search_dist(radius)), (h - r) * (w - 2 * r)
 
 
-def _f32(t, name, dim=4):
-    if not torch.is_tensor(t) or t.dim() != dim or t.numel() == 0:
-        raise ValueError("%s must be a %d-d torch tensor on the GPU" % (name, dim))
-    L.require_gpu(t)
-    if t.dtype != torch.float32:
-        raise ValueError("%s must be float32, got %s" % (name, t.dtype))
-    return t
-
-
 def pair_codes(label_map, radius=5, stride=8):
     """label_map (B, S, S') uint8 on the device, class ids with 255 = ignore (what ``ChunkLoader.get_data_from_chunk_v4`` returns
     with ``map_fill=255``; a single (S, S') map is a batch of one) -> (codes (B, P, N) uint8, counts int64[3] on the device: the
     batch totals of codes 1, 2, 3).  The grid is the map subsampled by ``stride`` -- g[y, x] = map[stride y, stride x], the
     reference's ``RescaleNearest(0.125)`` -- in the same kernel; ``stride=1`` takes a grid-sized map."""
     lib = L.load()
-    if not torch.is_tensor(label_map) or label_map.dtype != torch.uint8:
-        raise ValueError("label_map must be a uint8 torch tensor on the GPU")
+    label_map = A.tensor_arg(label_map, "label_map", torch.uint8, contiguous=False, on_gpu=False)
     if label_map.dim() == 2:
         label_map = label_map.unsqueeze(0)
-    if label_map.dim() != 3 or label_map.numel() == 0:
+    if label_map.dim() != 3:
         raise ValueError("label_map %s must be (B, S, S')" % (tuple(label_map.shape),))
     L.require_gpu(label_map)
     stride = int(stride)
@@ -119,9 +111,7 @@ def aff_label(la, ha, *, box=None):
     rec[0] = (0, h, w, h, w, flip, ct, cl, it, il, ch, cw, 0)
     D._check_aff_records(rec, [(h, w)], SH, SW)
     if (kl is not None and not la.is_cuda) or (kh is not None and not ha.is_cuda):      # host planes of a dump: to the GPU
-        if not torch.cuda.is_available():
-            raise L.AcrHipError("aff_label needs a GPU (no CPU path in the product)")
-        dev = la.device if la.is_cuda else ha.device if ha.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        dev = la.device if la.is_cuda else ha.device if ha.is_cuda else A.gpu_device("cuda", "aff_label")
         la, ha = (la.to(dev) if kl is not None else la), (ha.to(dev) if kh is not None else ha)
     L.require_gpu(la, ha)
     if la.device != ha.device:
@@ -137,7 +127,7 @@ def pair_affinity(feat, radius=5):
     """feat (B, C, h, w) float32 on the GPU -> aff (B, P, N) = exp(-(1 / C) sum_c |feat[from] - feat[to]|).  The inference
     forward: no grad (the result is detached whatever feat requires)."""
     lib = L.load()
-    feat = _f32(feat, "feat").detach().contiguous()
+    feat = A.tensor_arg(feat, "feat", torch.float32, shape=_BCHW, contiguous=False).detach().contiguous()
     B, C, h, w = feat.shape
     P, N = _geometry(h, w, radius)
     aff = torch.empty((B, P, N), dtype=torch.float32, device=feat.device)
@@ -157,10 +147,7 @@ class _AffLoss(torch.autograd.Function):
         B, C, h, w = feat.shape
         dev = feat.device
         with torch.cuda.device(dev):
-            nbytes = lib.acr_aff_loss_ws_bytes(B, h, w, radius)
-            if nbytes < 0:
-                L.check(-1, "acr_aff_loss_ws_bytes")
-            ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+            ws, nbytes = L.workspace("acr_aff_loss_ws_bytes", B, h, w, radius, device=dev, dtype=torch.float64)
             aff = torch.empty(codes.shape, dtype=torch.float32, device=dev)
             g = torch.empty(codes.shape, dtype=torch.float32, device=dev)
             loss4 = torch.empty(4, dtype=torch.float32, device=dev)
@@ -186,11 +173,13 @@ class _AffLoss(torch.autograd.Function):
 
 
 def _aff_loss(feat, codes, counts, radius=None):
-    feat = _f32(feat, "feat")
+    feat = A.tensor_arg(feat, "feat", torch.float32, shape=_BCHW, contiguous=False)
     B, C, h, w = feat.shape
-    if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 3 or codes.device != feat.device:
+    codes = A.tensor_arg(codes, "codes", torch.uint8, shape=("B", "P", "N"), contiguous=False, on_gpu=False)
+    counts = A.tensor_arg(counts, "counts", torch.int64, contiguous=False, on_gpu=False)
+    if codes.device != feat.device:
         raise ValueError("codes must be the (B, P, N) uint8 tensor pair_codes returned, on the device of feat")
-    if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.numel() != 3 or counts.device != feat.device:
+    if counts.numel() != 3 or counts.device != feat.device:
         raise ValueError("counts must be the int64[3] tensor pair_codes returned, on the device of feat")
     if radius is None:
         fits = [R for R in range(MIN_RADIUS, MAX_RADIUS + 1) if h > R - 1 and w > 2 * (R - 1) and tuple(codes.shape[1:]) == _geometry(h, w, R)]
@@ -215,7 +204,7 @@ def walk_weights(aff, hw, radius=5, beta=8):
     """aff (B, P, N) -> the normalised (B, 2 P + 1, h w) tap table of the transition matrix T (include/acr_hip.h)"""
     lib = L.load()
     h, w = hw
-    aff = _f32(aff, "aff", 3).detach().contiguous()
+    aff = A.tensor_arg(aff, "aff", torch.float32, shape=("B", "P", "N"), contiguous=False).detach().contiguous()
     P, N = _geometry(h, w, radius)
     if tuple(aff.shape[1:]) != (P, N):
         raise ValueError("aff %s does not fit a %d x %d grid at radius %d" % (tuple(aff.shape), h, w, radius))
@@ -233,7 +222,7 @@ def random_walk(aff, scores, beta=8, logt=8, resident=None, steps=None, radius=5
     plane spread over the chip; bit-identical.  None chooses, and chooses the stepwise form: the faster one at every plane count
     measured.  ``logt=None`` with ``steps=t`` runs t steps.  No grad."""
     lib = L.load()
-    scores = _f32(scores, "scores").detach().contiguous()
+    scores = A.tensor_arg(scores, "scores", torch.float32, shape=_BCHW, contiguous=False).detach().contiguous()
     B, K, h, w = scores.shape
     if (logt is None) == (steps is None):
         raise ValueError("give logt, or logt=None with steps")
@@ -250,10 +239,7 @@ def random_walk(aff, scores, beta=8, logt=8, resident=None, steps=None, radius=5
     with torch.cuda.device(dev):
         ws, nbytes = None, 0
         if steps > 0 and mode != 1:
-            nbytes = lib.acr_aff_walk_ws_bytes(B, K, h, w, int(radius))
-            if nbytes < 0:
-                L.check(-1, "acr_aff_walk_ws_bytes")
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            ws, nbytes = L.workspace("acr_aff_walk_ws_bytes", B, K, h, w, int(radius), device=dev, dtype=torch.float32)
         L.check(lib.acr_aff_walk(L.ptr(wt), L.ptr(scores), L.ptr(out), B, K, h, w, int(radius), steps, mode, L.ptr(ws), nbytes,
                                  L.stream_ptr()), "acr_aff_walk")
     return out

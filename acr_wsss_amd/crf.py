@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 
@@ -31,10 +32,7 @@ class PermutohedralLattice:
                 raise ValueError("rgb must be (H, W, 3) uint8, got %s %s" % (tuple(rgb.shape), rgb.dtype))
             rgb = rgb.to(dev).contiguous()
         with torch.cuda.device(dev):
-            nbytes = lib.acr_lattice_ws_bytes(self.n, self.d)
-            if nbytes < 0:
-                L.check(-1, "acr_lattice_ws_bytes")
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.ws, nbytes = L.workspace("acr_lattice_ws_bytes", self.n, self.d, device=dev)
             L.check(lib.acr_lattice_build(L.ptr(rgb) if rgb is not None else None, self.h, self.w, float(sxy), float(srgb),
                                           L.ptr(self.ws), nbytes, L.stream_ptr()), "acr_lattice_build")
             m, ovf = ctypes.c_int32(0), ctypes.c_int32(0)
@@ -45,9 +43,7 @@ class PermutohedralLattice:
     def filter(self, x, pre=None, post=None, scale=None, out=None):
         """x (K, n) float32 on the device -> scale * post * filter(pre * x), (K, n)."""
         lib = L.load()
-        L.require_gpu(x)
-        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.n or not x.is_contiguous():
-            raise ValueError("x must be a contiguous (K, %d) float32 tensor" % self.n)
+        A.tensor_arg(x, "x", torch.float32, shape=("K", self.n))
         k = x.shape[0]
         need = 2 * k * (self.n_points + 2)
         if self._vals is None or self._vals.numel() < need:
@@ -125,10 +121,7 @@ def _mean_field(img, probs, t, labels, device, gaussian, bilateral):
     h, w = img.shape[:2]
     n = h * w
     if torch.is_tensor(probs):
-        L.require_gpu(probs)
-        if probs.dtype != torch.float32 or tuple(probs.shape) != (labels, h, w) or not probs.is_contiguous():
-            raise ValueError("probs on the device must be a contiguous (%d, %d, %d) float32 tensor, got %s %s"
-                             % (labels, h, w, probs.dtype, tuple(probs.shape)))
+        A.tensor_arg(probs, "probs", torch.float32, shape=(labels, h, w))
         dev = probs.device
         p = probs.reshape(labels, n)
     else:

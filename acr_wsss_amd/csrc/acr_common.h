@@ -22,6 +22,14 @@ void acr_set_error(const char* fmt, ...);
             return ACR_ERR_INVALID;         \
         }                                   \
     } while (0)
+// a workspace the entry point `who` cannot do without: there, aligned to `align` bytes (a power of two), of `need` bytes at least
+#define ACR_CHECK_WS(who, ws, align, ws_bytes, need)                                                                              \
+    do {                                                                                                                          \
+        ACR_CHECK_ARG((ws) && ((uintptr_t)(ws) & ((align)-1)) == 0, "%s: null workspace or not aligned to %d bytes", who, align); \
+        const long long acr_ws_need_ = (long long)(need);                                                                         \
+        ACR_CHECK_ARG((long long)(ws_bytes) >= acr_ws_need_, "%s: workspace of %lld bytes, %lld needed", who, (long long)(ws_bytes), \
+                      acr_ws_need_);                                                                                              \
+    } while (0)
 int acr_check_launch(const char* what);
 int32_t acr_opt(int option);          // explicit option table (acr_set_option), api.hip
 

@@ -408,8 +408,7 @@ extern "C" int acr_aff_loss_fwd(const float* feat, int32_t B, int32_t C, int32_t
     if (rc != ACR_OK) return rc;
     if (codes) {
         ACR_CHECK_ARG(counts && g && ws && loss4, "acr_aff_loss_fwd: codes need counts, g, ws and loss4");
-        ACR_CHECK_ARG(ws_bytes >= acr_aff_loss_ws_bytes(B, h, w, R) && ((uintptr_t)ws & 7) == 0,
-                      "acr_aff_loss_fwd: ws of %lld bytes is too small or not 8-byte aligned", (long long)ws_bytes);
+        ACR_CHECK_WS("acr_aff_loss_fwd", ws, 8, ws_bytes, acr_aff_loss_ws_bytes(B, h, w, R));
     } else {
         ACR_CHECK_ARG(aff, "acr_aff_loss_fwd: without codes there is nothing to write but aff");
     }
@@ -484,9 +483,7 @@ extern "C" int acr_aff_walk(const float* wt, const float* scores, float* out, in
                                         steps));
         return acr_check_launch("acr_aff_walk (resident)");
     }
-    ACR_CHECK_ARG(ws && ws_bytes >= acr_aff_walk_ws_bytes(B, K, h, w, R) && ((uintptr_t)ws & 3) == 0,
-                  "acr_aff_walk: the stepwise form needs acr_aff_walk_ws_bytes = %lld bytes of ws, got %lld",
-                  (long long)acr_aff_walk_ws_bytes(B, K, h, w, R), (long long)ws_bytes);
+    ACR_CHECK_WS("acr_aff_walk (stepwise)", ws, 4, ws_bytes, acr_aff_walk_ws_bytes(B, K, h, w, R));
     float* buf[2] = {(float*)ws, (float*)ws + (int64_t)planes * stride};
     if (hipMemsetAsync(ws, 0, (size_t)(2 * planes * stride) * sizeof(float), st) != hipSuccess) {
         acr_set_error("acr_aff_walk: clearing ws failed");

@@ -507,9 +507,8 @@ extern "C" int acr_bn2d_fwd(const float* x, const float* gamma, const float* bet
     ACR_CHECK_ARG(x && gamma && beta && stats && y, "acr_bn2d_fwd: null pointer");
     ACR_CHECK_ARG(resid || !resid2, "acr_bn2d_fwd: resid2 given without resid");
     ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(resid) && BN_ALIGNED(resid2), "acr_bn2d_fwd: a tensor is not 16-byte aligned");
-    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0, "acr_bn2d_fwd: null workspace, or ws / stats not aligned to 8 bytes");
-    ACR_CHECK_ARG(ws_bytes >= acr_bn2d_ws_bytes(N, C, HW), "acr_bn2d_fwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-                  (long long)acr_bn2d_ws_bytes(N, C, HW));
+    ACR_CHECK_ARG(((uintptr_t)stats & 7) == 0, "acr_bn2d_fwd: stats not aligned to 8 bytes");
+    ACR_CHECK_WS("acr_bn2d_fwd", ws, 8, ws_bytes, acr_bn2d_ws_bytes(N, C, HW));
     const int64_t M = (int64_t)N * HW;
     if (training)
         ACR_CHECK_ARG(M >= 2, "acr_bn2d_fwd: %lld value per channel in training mode, 2 at least", (long long)M);
@@ -538,9 +537,8 @@ extern "C" int acr_bn2d_bwd(const float* x, const float* y, const float* dy, con
     ACR_CHECK_ARG(relu || !dres, "acr_bn2d_bwd: without a fused ReLU the addends' gradient is dy itself; dres must be null");
     ACR_CHECK_ARG(BN_ALIGNED(x) && BN_ALIGNED(y) && BN_ALIGNED(dy) && BN_ALIGNED(dx) && BN_ALIGNED(dres),
                   "acr_bn2d_bwd: a tensor is not 16-byte aligned");
-    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0, "acr_bn2d_bwd: null workspace, or ws / stats not aligned to 8 bytes");
-    ACR_CHECK_ARG(ws_bytes >= acr_bn2d_ws_bytes(N, C, HW), "acr_bn2d_bwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-                  (long long)acr_bn2d_ws_bytes(N, C, HW));
+    ACR_CHECK_ARG(((uintptr_t)stats & 7) == 0, "acr_bn2d_bwd: stats not aligned to 8 bytes");
+    ACR_CHECK_WS("acr_bn2d_bwd", ws, 8, ws_bytes, acr_bn2d_ws_bytes(N, C, HW));
     hipStream_t st = (hipStream_t)stream;
     const int64_t M = (int64_t)N * HW;
     const int S = bn_slabs(M, C);
@@ -562,10 +560,9 @@ static int bn_sync_check(const char* who, int32_t N, int32_t C, int32_t HW, cons
                          const void* d2) {
     const int rc = bn_check(who, N, C, HW);
     if (rc != ACR_OK) return rc;
-    ACR_CHECK_ARG(ws && d1 && d2, "%s: null pointer", who);
-    ACR_CHECK_ARG((((uintptr_t)ws | (uintptr_t)d1 | (uintptr_t)d2) & 7) == 0, "%s: ws or a double buffer not aligned to 8 bytes", who);
-    ACR_CHECK_ARG(ws_bytes >= acr_bn2d_ws_bytes(N, C, HW), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
-                  (long long)acr_bn2d_ws_bytes(N, C, HW));
+    ACR_CHECK_ARG(d1 && d2, "%s: null pointer", who);
+    ACR_CHECK_ARG((((uintptr_t)d1 | (uintptr_t)d2) & 7) == 0, "%s: a double buffer not aligned to 8 bytes", who);
+    ACR_CHECK_WS(who, ws, 8, ws_bytes, acr_bn2d_ws_bytes(N, C, HW));
     return ACR_OK;
 }
 

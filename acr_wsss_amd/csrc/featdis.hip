@@ -541,12 +541,10 @@ extern "C" int acr_featdis_fwd(const float* seg, const float* feat, int32_t B, i
     const int rc = fd_check("acr_featdis_fwd", B, K, C, h, w);
     if (rc != ACR_OK) return rc;
     ACR_CHECK_ARG(seg && feat && loss && labels && counts && pix && cst, "acr_featdis_fwd: null pointer");
-    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 15) == 0, "acr_featdis_fwd: null workspace or not aligned to 16 bytes");
     ACR_CHECK_ARG((((uintptr_t)pix | (uintptr_t)cst) & 15) == 0 && ((uintptr_t)counts & 7) == 0,
                   "acr_featdis_fwd: pix and cst must be aligned to 16 bytes, counts to 8");
     const fd_plan pl = fd_make_plan(B, K, C, h, w);
-    ACR_CHECK_ARG(ws_bytes >= (int64_t)pl.total, "acr_featdis_fwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-                  (long long)pl.total);
+    ACR_CHECK_WS("acr_featdis_fwd", ws, 16, ws_bytes, pl.total);
     hipStream_t st = (hipStream_t)stream;
     unsigned char* base = reinterpret_cast<unsigned char*>(ws);
     double* partial = reinterpret_cast<double*>(base + pl.o_partial);

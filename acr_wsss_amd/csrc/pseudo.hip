@@ -264,10 +264,7 @@ extern "C" int acr_pseudo_compose(const float* cams, const int32_t* classes, int
     ACR_CHECK_ARG(cam_floor >= 0.f, "acr_pseudo_compose: cam_floor=%g < 0", (double)cam_floor);
     ACR_CHECK_ARG(fg_quantile >= 0.0 && fg_quantile < 1.0, "acr_pseudo_compose: fg_quantile=%g outside [0, 1)", fg_quantile);
     ACR_CHECK_ARG(crf_sure > 0.f, "acr_pseudo_compose: crf_sure=%g <= 0", (double)crf_sure);
-    ACR_CHECK_ARG(ws, "acr_pseudo_compose: null workspace");
-    ACR_CHECK_ARG(((uintptr_t)ws & 3) == 0, "acr_pseudo_compose: workspace not aligned to 4 bytes");
-    ACR_CHECK_ARG(ws_bytes >= acr_pseudo_ws_bytes(K, h, w), "acr_pseudo_compose: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-                  (long long)acr_pseudo_ws_bytes(K, h, w));
+    ACR_CHECK_WS("acr_pseudo_compose", ws, 4, ws_bytes, acr_pseudo_ws_bytes(K, h, w));
     uint32_t* words = reinterpret_cast<uint32_t*>(ws);
     uint8_t* sel = reinterpret_cast<uint8_t*>(words + pseudo_head_words(K));
     const size_t lds = (size_t)K * PSEUDO_BINS * 4;      // at most 127 KB

@@ -309,10 +309,7 @@ extern "C" int acr_sal_pseudo_compose(const float* cams, const uint8_t* present,
     ACR_CHECK_ARG(bg_alpha > 0.0, "acr_sal_pseudo_compose: bg_alpha=%g <= 0", bg_alpha);
     ACR_CHECK_ARG(cut >= 0.0 && cut < 1.0, "acr_sal_pseudo_compose: cut=%g outside [0, 1)", cut);
     ACR_CHECK_ARG(open_size >= 0 && open_size <= PSAL_MAX_K, "acr_sal_pseudo_compose: open_size=%d outside 0..%d", open_size, PSAL_MAX_K);
-    ACR_CHECK_ARG(ws, "acr_sal_pseudo_compose: null workspace");
-    ACR_CHECK_ARG(((uintptr_t)ws & 3) == 0, "acr_sal_pseudo_compose: workspace not aligned to 4 bytes");
-    const int64_t need = acr_sal_pseudo_ws_bytes(B, C, h, w);
-    ACR_CHECK_ARG(ws_bytes >= need, "acr_sal_pseudo_compose: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+    ACR_CHECK_WS("acr_sal_pseudo_compose", ws, 4, ws_bytes, acr_sal_pseudo_ws_bytes(B, C, h, w));
     hipStream_t st = (hipStream_t)stream;
     const int64_t hw = (int64_t)h * w, P = (int64_t)B * C;
     uint32_t* words = reinterpret_cast<uint32_t*>(ws);

@@ -216,10 +216,7 @@ extern "C" int acr_reassemble_bwd(const float* dout, int32_t B, int32_t T, int32
     ACR_CHECK_ARG(dout && dy, "acr_reassemble_bwd: null pointer");
     const Plan p = plan_of(gh, gw, C, s);
     const int64_t np = (int64_t)B * p.gh * p.ntj;
-    if (dbias)
-        ACR_CHECK_ARG(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= np * C * (int64_t)sizeof(float),
-                      "acr_reassemble_bwd: dbias needs a 4-byte aligned workspace of acr_reassemble_ws_bytes() = %lld bytes, got %lld",
-                      (long long)(np * C * (int64_t)sizeof(float)), (long long)ws_bytes);
+    if (dbias) ACR_CHECK_WS("acr_reassemble_bwd (dbias)", ws, 4, ws_bytes, np * C * (int64_t)sizeof(float));
     float* part = dbias ? (float*)ws : nullptr;
     const dim3 grid((unsigned)(p.tiles * B)), block(256);
     hipStream_t st = (hipStream_t)stream;

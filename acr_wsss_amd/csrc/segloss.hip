@@ -263,9 +263,7 @@ extern "C" int acr_segloss_fwd(const float* logits, const uint8_t* label, int32_
     const int rc = segloss_check("acr_segloss_fwd", B, K, h, w, W, H);
     if (rc != ACR_OK) return rc;
     ACR_CHECK_ARG(logits && label && sums && counts && loss, "acr_segloss_fwd: null pointer");
-    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0, "acr_segloss_fwd: null workspace or not aligned to 8 bytes");
-    ACR_CHECK_ARG(ws_bytes >= acr_segloss_ws_bytes(B, K, h, w, W, H), "acr_segloss_fwd: workspace of %lld bytes, %lld needed",
-                  (long long)ws_bytes, (long long)acr_segloss_ws_bytes(B, K, h, w, W, H));
+    ACR_CHECK_WS("acr_segloss_fwd", ws, 8, ws_bytes, acr_segloss_ws_bytes(B, K, h, w, W, H));
     ACR_CHECK_ARG(!rowstat || ((uintptr_t)rowstat & 7) == 0, "acr_segloss_fwd: rowstat not aligned to 8 bytes");
     hipStream_t st = (hipStream_t)stream;
     const int nblk = segloss_nblk((int64_t)W * H);
@@ -296,9 +294,7 @@ extern "C" int acr_segloss_bwd(const float* logits, const uint8_t* label, const 
     const int64_t WH = (int64_t)W * H;
     float* dot = nullptr;
     if (d_probs) {
-        ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0, "acr_segloss_bwd: null workspace or not aligned to 8 bytes");
-        ACR_CHECK_ARG(ws_bytes >= acr_segloss_ws_bytes(B, K, h, w, W, H), "acr_segloss_bwd: workspace of %lld bytes, %lld needed",
-                      (long long)ws_bytes, (long long)acr_segloss_ws_bytes(B, K, h, w, W, H));
+        ACR_CHECK_WS("acr_segloss_bwd", ws, 8, ws_bytes, acr_segloss_ws_bytes(B, K, h, w, W, H));
         dot = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + segloss_part_bytes(B, W, H));
         int64_t nb = (B * WH + 255) / 256;
         if (nb > 2048) nb = 2048;
@@ -317,9 +313,7 @@ extern "C" int acr_dense_energy_dot(const float* s, const float* as, int64_t cou
                                     int64_t ws_bytes, float* out, void* stream) {
     ACR_CHECK_ARG(s && as && out, "acr_dense_energy_dot: null pointer");
     ACR_CHECK_ARG(count >= 1, "acr_dense_energy_dot: count=%lld < 1", (long long)count);
-    ACR_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0, "acr_dense_energy_dot: null workspace or not aligned to 8 bytes");
-    ACR_CHECK_ARG(ws_bytes >= ACR_DENSE_ENERGY_WS_BYTES, "acr_dense_energy_dot: workspace of %lld bytes, %d needed", (long long)ws_bytes,
-                  ACR_DENSE_ENERGY_WS_BYTES);
+    ACR_CHECK_WS("acr_dense_energy_dot", ws, 8, ws_bytes, ACR_DENSE_ENERGY_WS_BYTES);
     hipStream_t st = (hipStream_t)stream;
     const int nblk = segloss_nblk(count);
     double* part = reinterpret_cast<double*>(ws);

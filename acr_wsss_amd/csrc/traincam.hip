@@ -231,11 +231,7 @@ extern "C" int acr_train_cam_f32(const float* cam1, const float* cam2, int64_t t
     g.sw = (float)gw / (float)ow;
     tc_slabs(oh, ow, &g.rows, &g.ns);
     const int64_t blocks = (int64_t)B * C * g.ns;        // <= 2^22 * 2^8
-    if (normalize) {
-        ACR_CHECK_ARG(ws, "acr_train_cam_f32: null workspace");
-        ACR_CHECK_ARG(((uintptr_t)ws & 3) == 0, "acr_train_cam_f32: workspace not aligned to 4 bytes");
-        ACR_CHECK_ARG(ws_bytes >= blocks * 8, "acr_train_cam_f32: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)(blocks * 8));
-    }
+    if (normalize) ACR_CHECK_WS("acr_train_cam_f32", ws, 4, ws_bytes, blocks * 8);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = ow % 4 == 0 && ((uintptr_t)out & 15) == 0;
     float* pairs = reinterpret_cast<float*>(ws);

@@ -34,6 +34,7 @@ import random as _pyrandom
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 MEAN = (0.485, 0.456, 0.406)
@@ -93,13 +94,6 @@ def _check_images(who, images_uint8, records, S):
             raise L.AcrHipError("%s: inconsistent geometry record %s for a %s image" % (who, rec, a.shape))
 
 
-def _cuda_device(who, device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise L.AcrHipError("acr_wsss_amd.data runs on the GPU only (%s); there is no CPU path" % who)
-    return device
-
-
 def _upload_packed(arrays, device):
     """The uint8 arrays back to back, each at a 16-byte aligned offset of ONE pinned staging buffer, and its one H2D copy.
     Returns (offsets, staging buffer, device buffer); the staging buffer must outlive the asynchronous copy."""
@@ -127,7 +121,7 @@ def preprocess_batch(images_uint8, records, S, device, dtype=torch.float32):
     """Run acr_preprocess_batch: ``images_uint8`` = list of (h,w,3) uint8 RGB arrays, ``records`` = PRE_IMAGE array with
     everything but ``offset`` filled in.  One pinned staging buffer, one H2D copy, one launch."""
     _check_images("acr_preprocess_batch", images_uint8, records, S)
-    device = _cuda_device("acr_preprocess_batch", device)
+    device = A.gpu_device(device, "acr_preprocess_batch")
     offs, stage, packed = _upload_packed(images_uint8, device)
     table = _upload_table(records, offs, device)
     out = torch.empty((len(images_uint8), 3, S, S), dtype=dtype, device=device)
@@ -210,7 +204,7 @@ def preprocess_seg_batch(images_uint8, maps_uint8, records, S, device, dtype=tor
         raise ValueError("map_fill=%r outside 0..255" % (map_fill,))
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("dtype must be float32 or bfloat16, got %s" % (dtype,))
-    device = _cuda_device("acr_preprocess_seg_batch", device)
+    device = A.gpu_device(device, "acr_preprocess_seg_batch")
     B = len(images_uint8)
     offs, stage, packed = _upload_packed(list(images_uint8) + list(maps_uint8), device)      # images and maps share the buffer
     table = _upload_table(records, offs[:B], device, extra=offs[B:])                        # ... and the map offsets the table's
@@ -367,7 +361,7 @@ def preprocess_aff_batch(images_uint8, la, ha, records, S, device, dtype=torch.f
     _check_images("acr_aff_label_batch", images_uint8, records, S)
     stacks = [score_pair(l, h, a.shape[:2], "image %d" % i) for i, (a, l, h) in enumerate(zip(images_uint8, la, ha))]
     _check_aff_records(records, [a.shape[:2] for a in images_uint8], S, S)
-    device = _cuda_device("acr_aff_label_batch", device)
+    device = A.gpu_device(device, "acr_aff_label_batch")
     images = preprocess_batch(images_uint8, records, S, device, dtype)
     flat = [s.view(np.uint8).reshape(-1) for pair in stacks for s in pair]
     offs, stage, packed = _upload_packed(flat, device)

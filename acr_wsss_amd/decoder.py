@@ -51,13 +51,6 @@ def _c16(t):
     return t.clone() if t.data_ptr() % 16 else t
 
 
-def _ws(lib, n, c, hw, dev):
-    nbytes = lib.acr_bn2d_ws_bytes(n, c, hw)
-    if nbytes < 0:
-        L.check(-1, "acr_bn2d_ws_bytes")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-
 # ------------------------------------------------------------------------------------------------
 # autograd functions over the C ABI
 # ------------------------------------------------------------------------------------------------
@@ -69,8 +62,7 @@ class _BatchNormAct(Function):
         n, c, h, w = x.shape
         dev = x.device
         with torch.cuda.device(dev):
-            ws = _ws(lib, n, c, h * w, dev)
-            nbytes = ws.numel()
+            ws, nbytes = L.workspace("acr_bn2d_ws_bytes", n, c, h * w, device=dev)
             stats = torch.empty((c, 2), dtype=torch.float64, device=dev)
             y = torch.empty_like(x)
             L.check(lib.acr_bn2d_fwd(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
@@ -126,7 +118,7 @@ class _SyncBatchNormAct(Function):
         n, c, h, w = x.shape
         dev = x.device
         with torch.cuda.device(dev):
-            ws = _ws(lib, n, c, h * w, dev)
+            ws = L.workspace("acr_bn2d_ws_bytes", n, c, h * w, device=dev)[0]
             moments = torch.empty((c, 3), dtype=torch.float64, device=dev)
             L.check(lib.acr_bn2d_moments(L.ptr(x), n, c, h * w, L.ptr(ws), ws.numel(), L.ptr(moments), L.stream_ptr()), "acr_bn2d_moments")
             gathered = gather_rows(moments, group)

@@ -20,10 +20,11 @@ the integers the numpy code would hold; there is no CPU path behind them.  ``Cam
 ``infer_cam.infer_cam_list(..., evaluate=...)`` fills.  One deviation, shared by every class here: a ground-truth label that is
 neither < num_cls nor 255 is ignored like 255 (the reference counts such a pixel in P only; VOC and COCO hold none).
 """
-import ctypes
 import os
 
 import numpy as np
+
+from . import _args as A
 
 CATEGORIES = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow',
               'diningtable', 'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
@@ -195,33 +196,10 @@ MAX_CLS, MAX_THRESHOLDS = 128, 256        # limits of the ABI (include/acr_hip.h
 
 def _device(device):
     """torch.device of a GPU with the library loaded, else AcrHipError: nothing below has a CPU path."""
-    import torch
     from . import _lib as L
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise L.AcrHipError("device-side evaluation needs a GPU (got device %r); use SweepCounters / LabelCounters on the host" % (device,))
+    dev = A.gpu_device(device, "device-side evaluation (SweepCounters / LabelCounters count on the host)")
     L.load()
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
-def _check_map(t, name, dtype, dev):
-    import torch
-    from . import _lib as L
-    if not torch.is_tensor(t):
-        raise ValueError("%s must be a tensor" % name)
-    L.require_gpu(t)
-    if t.dtype != dtype or not t.is_contiguous():
-        raise ValueError("%s must be a contiguous %s tensor, got %s with strides %s" % (name, dtype, t.dtype, tuple(t.stride())))
-    if t.device != dev:
-        raise ValueError("%s lies on %s, the counters on %s" % (name, t.device, dev))
-
-
-def _upload_u8(a, name, dev):
-    import torch
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise ValueError("%s must be uint8, got %s" % (name, a.dtype))
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+    return dev
 
 
 class DeviceSweepCounters:
@@ -250,35 +228,16 @@ class DeviceSweepCounters:
     def reset(self):
         self._raw.zero_()
 
-    def _classes(self, classes):
-        cl = [int(c) for c in classes]
-        if not cl:
-            raise ValueError("no classes: an image without a positive class has no CAM to score")
-        if any(c < 0 or c >= self.num_cls - 1 for c in cl):
-            raise ValueError("classes %s outside 0..%d" % (cl, self.num_cls - 2))
-        if any(b <= a for a, b in zip(cl, cl[1:])):
-            raise ValueError("classes %s must be strictly ascending (sorted, no duplicates)" % (cl,))
-        return cl
-
     def add(self, cams, classes, gt):
         """cams: (n, h, w) contiguous float32 device tensor, plane j the CAM of class ``classes[j]`` (0-based, without
         background, strictly ascending); gt: (h, w) uint8, a device tensor or a numpy array (uploaded), 255 = ignore."""
         import torch
         from . import _lib as L
         lib = L.load()
-        cl = self._classes(classes)
-        _check_map(cams, "cams", torch.float32, self.device)
-        if cams.dim() != 3 or cams.shape[0] != len(cl):
-            raise ValueError("cams %s must be (n, h, w) with one plane per class (%d classes)" % (tuple(cams.shape), len(cl)))
-        if not torch.is_tensor(gt):
-            gt = _upload_u8(gt, "gt", self.device)
-        _check_map(gt, "gt", torch.uint8, self.device)
-        if tuple(gt.shape) != tuple(cams.shape[1:]):
-            raise ValueError("gt %s does not match cams %s" % (tuple(gt.shape), tuple(cams.shape)))
+        arr, cl = A.class_array(classes, self.num_cls - 1, "no CAM to score")
+        cams = A.tensor_arg(cams, "cams", torch.float32, shape=(len(cl), "h", "w"), device=self.device)
         n, h, w = cams.shape
-        if h * w == 0:
-            raise ValueError("empty image %s" % (tuple(cams.shape),))
-        arr = (ctypes.c_int32 * n)(*cl)
+        gt = A.tensor_arg(gt, "gt", torch.uint8, shape=(h, w), device=self.device, upload=True)
         with torch.cuda.device(self.device):
             L.check(lib.acr_eval_sweep_f32(L.ptr(cams), arr, n, L.ptr(gt), h, w, L.ptr(self._th), len(self.t), self.num_cls,
                                            L.ptr(self._raw), L.stream_ptr()), "acr_eval_sweep_f32")
@@ -336,16 +295,8 @@ class DeviceLabelCounters:
         import torch
         from . import _lib as L
         lib = L.load()
-        if not torch.is_tensor(pred):
-            pred = _upload_u8(pred, "pred", self.device)
-        if not torch.is_tensor(gt):
-            gt = _upload_u8(gt, "gt", self.device)
-        _check_map(pred, "pred", torch.uint8, self.device)
-        _check_map(gt, "gt", torch.uint8, self.device)
-        if pred.shape != gt.shape:
-            raise ValueError("pred %s and gt %s differ in shape" % (tuple(pred.shape), tuple(gt.shape)))
-        if pred.numel() == 0:
-            raise ValueError("empty label map")
+        pred = A.tensor_arg(pred, "pred", torch.uint8, device=self.device, upload=True)
+        gt = A.tensor_arg(gt, "gt", torch.uint8, shape=tuple(pred.shape), device=self.device, upload=True)
         with torch.cuda.device(self.device):
             L.check(lib.acr_eval_confusion_u8(L.ptr(pred), L.ptr(gt), pred.numel(), self.num_cls, L.ptr(self._conf), L.stream_ptr()),
                     "acr_eval_confusion_u8")

@@ -10,6 +10,7 @@ The reference hard-codes the classes 1..20 and 1024 channels; here the classes a
 The features are read as they lie (NCHW): no (B N, C) copy and no per-class masked copy exists."""
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 MAX_CLASSES = 128                         # 2 <= K <= 128 (include/acr_hip.h)
@@ -24,11 +25,8 @@ def slab_pixels(k):
 
 def _inputs(seg, feat):
     """The arguments are judged before the device is asked for: a bad dtype, rank, shape or K is a ValueError with or without a GPU."""
-    for name, t in (("seg", seg), ("feat", feat)):
-        if not torch.is_tensor(t):
-            raise ValueError("%s must be a torch tensor on the GPU, got %s" % (name, type(t).__name__))
-        if t.dtype != torch.float32 or t.dim() != 4 or t.numel() == 0:
-            raise ValueError("%s must be a 4-d float32 tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    seg = A.tensor_arg(seg, "seg", torch.float32, shape=("B", "K", "h", "w"), contiguous=False, on_gpu=False)
+    feat = A.tensor_arg(feat, "feat", torch.float32, shape=("B", "C", "h", "w"), contiguous=False, on_gpu=False)
     if not 2 <= seg.shape[1] <= MAX_CLASSES:
         raise ValueError("K=%d outside 2..%d" % (seg.shape[1], MAX_CLASSES))
     if feat.shape[1] > MAX_CHANNELS:
@@ -37,9 +35,8 @@ def _inputs(seg, feat):
         raise ValueError("seg %s and feat %s must share B, h and w" % (tuple(seg.shape), tuple(feat.shape)))
     if seg.shape[0] * seg.shape[2] * seg.shape[3] >= 1 << 31:
         raise ValueError("B h w = %d must stay below 2^31" % (seg.shape[0] * seg.shape[2] * seg.shape[3]))
-    L.require_gpu(seg, feat)
-    if seg.device != feat.device:
-        raise ValueError("seg lies on %s, feat on %s" % (seg.device, feat.device))
+    L.require_gpu(feat)
+    A.on_device(seg, "seg", feat.device)
 
 
 class _FeatDis(torch.autograd.Function):
@@ -53,10 +50,7 @@ class _FeatDis(torch.autograd.Function):
         c = feat.shape[1]
         dev = feat.device
         with torch.cuda.device(dev):
-            nbytes = lib.acr_featdis_ws_bytes(b, k, c, h, w)
-            if nbytes < 0:
-                L.check(-1, "acr_featdis_ws_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws, nbytes = L.workspace("acr_featdis_ws_bytes", b, k, c, h, w, device=dev)
             loss = torch.empty(3, dtype=torch.float32, device=dev)
             labels = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
             counts = torch.empty(b + k - 1, dtype=torch.int64, device=dev)

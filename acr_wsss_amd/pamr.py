@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 
@@ -18,11 +19,7 @@ def _dilation_array(dilations):
 
 
 def _check_input(t, name):
-    if not torch.is_tensor(t) or t.dim() != 4:
-        raise ValueError("%s must be a 4-d tensor" % name)
-    L.require_gpu(t)
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError("%s must be a contiguous float32 tensor, got %s with strides %s" % (name, t.dtype, tuple(t.stride())))
+    A.tensor_arg(t, name, torch.float32, shape=("B", "C", "H", "W"))
     if t.requires_grad:
         raise ValueError("%s requires grad: pamr has no backward (detach it, as the reference's callers do)" % name)
 

@@ -11,56 +11,21 @@ raises IndexError there).
 ``bg_alpha=32`` gives the label ``compute_seg_label_two_step`` composes, :313-367): a whole batch at once in csrc/pseudo_sal.hip
 behind ``acr_sal_pseudo_compose``, its 10 x 10 opening also on its own as ``morph_open`` (``acr_morph_open_u8``).  Of the
 reference's saliency variants the CRF-based siblings and the COCO ones are not covered, nor ``two_step``'s resize and PNG writes."""
-import ctypes
-
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 MAX_LABELS = 128                          # C + 1 <= 128 (include/acr_hip.h)
+_WHAT = "pseudo-label composition"
 
 
-def _class_array(classes, num_classes):
-    cl = [int(c) for c in classes]
-    if not cl:
-        raise ValueError("no classes: an image without a positive class has no scores to label")
+def _classes(classes, num_classes):
     if not 1 <= int(num_classes) <= MAX_LABELS - 1:
         raise ValueError("num_classes=%d outside 1..%d" % (num_classes, MAX_LABELS - 1))
-    if any(c < 0 or c >= num_classes for c in cl):
-        raise ValueError("classes %s outside 0..%d" % (cl, num_classes - 1))
-    if any(b <= a for a, b in zip(cl, cl[1:])):
-        raise ValueError("classes %s must be strictly ascending (sorted, no duplicates)" % (cl,))
-    return (ctypes.c_int32 * len(cl))(*cl), len(cl)
-
-
-def _device_of(tensors, device):
-    """The GPU the call runs on: that of the first device tensor among ``tensors``, else ``device``; AcrHipError without one."""
-    for t in tensors:
-        if torch.is_tensor(t):
-            L.require_gpu(t)
-            return t.device
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise L.AcrHipError("pseudo-label composition needs a GPU (got device %r): there is no CPU path" % (device,))
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
-def _planes(a, name, dev, n, hw=None):
-    """(n, W, H) contiguous float32 on ``dev``; numpy arrays are uploaded."""
-    if not torch.is_tensor(a):
-        a = np.asarray(a)
-        if a.dtype != np.float32:
-            raise ValueError("%s must be float32, got %s" % (name, a.dtype))
-        a = torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-    L.require_gpu(a)
-    if a.dtype != torch.float32 or not a.is_contiguous():
-        raise ValueError("%s must be a contiguous float32 tensor, got %s with strides %s" % (name, a.dtype, tuple(a.stride())))
-    if a.device != dev:
-        raise ValueError("%s lies on %s, the other inputs on %s" % (name, a.device, dev))
-    if a.dim() != 3 or a.shape[0] != n or a.numel() == 0 or (hw is not None and tuple(a.shape[1:]) != tuple(hw)):
-        raise ValueError("%s %s must be (%d, W, H)%s" % (name, tuple(a.shape), n, "" if hw is None else " with (W, H) = %s" % (tuple(hw),)))
-    return a
+    arr, cl = A.class_array(classes, num_classes, "no scores to label")
+    return arr, len(cl)
 
 
 def label_map(scores, labels, num_classes=20, device="cuda"):
@@ -71,10 +36,10 @@ def label_map(scores, labels, num_classes=20, device="cuda"):
     labels = [int(l) for l in labels]
     if not labels or labels[0] != 0:
         raise ValueError("labels %s must start with the background label 0" % (labels,))
-    arr, k = _class_array([l - 1 for l in labels[1:]], num_classes)
-    dev = _device_of((scores,), device)
+    arr, k = _classes([l - 1 for l in labels[1:]], num_classes)
+    dev = A.first_device((scores,), device, _WHAT)
     lib = L.load()
-    scores = _planes(scores, "scores", dev, k + 1)
+    scores = A.tensor_arg(scores, "scores", torch.float32, shape=(k + 1, "W", "H"), device=dev, upload=True)
     _, w, h = scores.shape
     with torch.cuda.device(dev):
         out = torch.empty((w, h), dtype=torch.uint8, device=dev)
@@ -90,24 +55,18 @@ def seg_label(cams, classes, la, ha, *, ignore_uncertain=False, bg_alpha=36, cam
     (W, H) pseudo-label on the device: the low-alpha label, 255 where that is background, 0 where the high-alpha label is
     background; with ``ignore_uncertain`` also 255 wherever the refined score or the CAM is not confident (defaults: the
     reference's constants).  Nothing here synchronises."""
-    arr, k = _class_array(classes, num_classes)
+    arr, k = _classes(classes, num_classes)
     if not (cam_floor >= 0 and 0 <= fg_quantile < 1 and crf_sure > 0):
         raise ValueError("need cam_floor >= 0, 0 <= fg_quantile < 1, crf_sure > 0 (got %r, %r, %r)" % (cam_floor, fg_quantile, crf_sure))
-    dev = _device_of((cams, la, ha), device)
+    dev = A.first_device((cams, la, ha), device, _WHAT)
     lib = L.load()
-    cams = _planes(cams, "cams", dev, k)
-    hw = tuple(cams.shape[1:])
-    la = _planes(la, "la", dev, k + 1, hw)
-    ha = _planes(ha, "ha", dev, k + 1, hw)
-    w, h = hw
+    cams = A.tensor_arg(cams, "cams", torch.float32, shape=(k, "W", "H"), device=dev, upload=True)
+    _, w, h = cams.shape
+    la = A.tensor_arg(la, "la", torch.float32, shape=(k + 1, w, h), device=dev, upload=True)
+    ha = A.tensor_arg(ha, "ha", torch.float32, shape=(k + 1, w, h), device=dev, upload=True)
     with torch.cuda.device(dev):
         out = torch.empty((w, h), dtype=torch.uint8, device=dev)
-        ws, nbytes = None, 0
-        if ignore_uncertain:
-            nbytes = lib.acr_pseudo_ws_bytes(k, w, h)
-            if nbytes < 0:
-                L.check(-1, "acr_pseudo_ws_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = (None, 0) if not ignore_uncertain else L.workspace("acr_pseudo_ws_bytes", k, w, h, device=dev)
         L.check(lib.acr_pseudo_compose(L.ptr(cams), arr, k, L.ptr(la), L.ptr(ha), w, h, int(num_classes), 1 if ignore_uncertain else 0,
                                        float(bg_alpha), float(cam_floor), float(fg_quantile), float(bg_sure), float(crf_sure),
                                        L.ptr(ws), nbytes, L.ptr(out), L.stream_ptr()), "acr_pseudo_compose")
@@ -117,26 +76,6 @@ def seg_label(cams, classes, la, ha, *, ignore_uncertain=False, bg_alpha=36, cam
 MAX_SAL_CLASSES = 127                     # labels c + 1 next to 255 (include/acr_hip.h)
 OPEN_TILE = 64                            # edge of the opening kernel's output tile (PSAL_TILE, csrc/pseudo_sal.hip)
 MAX_OPEN = 32                             # largest opening box
-
-
-def _bytes_on(a, name, dev, shape=None, ndim=None):
-    """contiguous uint8 (bool counts) on ``dev``; numpy arrays are uploaded"""
-    if not torch.is_tensor(a):
-        a = np.asarray(a)
-        if a.dtype not in (np.uint8, np.bool_):
-            raise ValueError("%s must be uint8 or bool, got %s" % (name, a.dtype))
-        a = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev, non_blocking=True)
-    L.require_gpu(a)
-    if a.dtype == torch.bool:
-        a = a.contiguous().view(torch.uint8)
-    if a.dtype != torch.uint8 or not a.is_contiguous():
-        raise ValueError("%s must be a contiguous uint8 tensor, got %s with strides %s" % (name, a.dtype, tuple(a.stride())))
-    if a.device != dev:
-        raise ValueError("%s lies on %s, the other inputs on %s" % (name, a.device, dev))
-    if a.numel() == 0 or (shape is not None and tuple(a.shape) != tuple(shape)) or (ndim is not None and a.dim() != ndim):
-        want = tuple(shape) if shape is not None else "not empty" if ndim is None else "%d-d and not empty" % ndim
-        raise ValueError("%s %s must be %s" % (name, tuple(a.shape), want))
-    return a
 
 
 def seg_label_saliency(cams, present, saliency, *, bg_alpha=12, cut=0.9, open_size=10, device="cuda"):
@@ -150,29 +89,16 @@ def seg_label_saliency(cams, present, saliency, *, bg_alpha=12, cut=0.9, open_si
     inputs nothing here synchronises (a numpy input is uploaded from pageable memory, which holds the host until it is copied)."""
     if not (bg_alpha > 0 and 0 <= cut < 1 and int(open_size) == open_size and 0 <= open_size <= MAX_OPEN):
         raise ValueError("need bg_alpha > 0, 0 <= cut < 1, open_size an integer in 0..%d (got %r, %r, %r)" % (MAX_OPEN, bg_alpha, cut, open_size))
-    dev = _device_of((cams, present, saliency), device)
+    dev = A.first_device((cams, present, saliency), device, _WHAT)
     lib = L.load()
-    if not torch.is_tensor(cams):
-        cams = np.asarray(cams)
-        if cams.dtype != np.float32:
-            raise ValueError("cams must be float32, got %s" % cams.dtype)
-        cams = torch.from_numpy(np.ascontiguousarray(cams)).to(dev, non_blocking=True)
-    L.require_gpu(cams)
-    if cams.dtype != torch.float32 or not cams.is_contiguous() or cams.dim() != 4 or cams.numel() == 0:
-        raise ValueError("cams must be a contiguous float32 (B, C, H, W) tensor, got %s %s with strides %s" % (
-            cams.dtype, tuple(cams.shape), tuple(cams.stride())))
-    if cams.device != dev:
-        raise ValueError("cams lies on %s, the other inputs on %s" % (cams.device, dev))
+    cams = A.tensor_arg(cams, "cams", torch.float32, shape=("B", "C", "H", "W"), device=dev, upload=True)
     b, c, h, w = cams.shape
     if c > MAX_SAL_CLASSES:
         raise ValueError("C=%d outside 1..%d" % (c, MAX_SAL_CLASSES))
-    present = _bytes_on(present, "present", dev, (b, c))
-    saliency = _bytes_on(saliency, "saliency", dev, (b, h, w))
+    present = A.tensor_arg(present, "present", torch.uint8, shape=(b, c), device=dev, upload=True, bool_as_u8=True)
+    saliency = A.tensor_arg(saliency, "saliency", torch.uint8, shape=(b, h, w), device=dev, upload=True, bool_as_u8=True)
     with torch.cuda.device(dev):
-        nbytes = lib.acr_sal_pseudo_ws_bytes(b, c, h, w)
-        if nbytes < 0:
-            L.check(-1, "acr_sal_pseudo_ws_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = L.workspace("acr_sal_pseudo_ws_bytes", b, c, h, w, device=dev)
         label = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
         sal_out = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
         L.check(lib.acr_sal_pseudo_compose(L.ptr(cams), L.ptr(present), b, c, h, w, L.ptr(saliency), float(bg_alpha), float(cut),
@@ -188,9 +114,9 @@ def morph_open(mask_u8, k=10, device="cuda"):
     left out.  1 <= k <= 32."""
     if not (int(k) == k and 1 <= k <= MAX_OPEN):
         raise ValueError("k=%r outside 1..%d" % (k, MAX_OPEN))
-    dev = _device_of((mask_u8,), device)
+    dev = A.first_device((mask_u8,), device, _WHAT)
     lib = L.load()
-    mask = _bytes_on(mask_u8, "mask_u8", dev)
+    mask = A.tensor_arg(mask_u8, "mask_u8", torch.uint8, device=dev, upload=True, bool_as_u8=True)
     if mask.dim() not in (2, 3):
         raise ValueError("mask_u8 %s must be (H, W) or (B, H, W)" % (tuple(mask.shape),))
     b = mask.shape[0] if mask.dim() == 3 else 1

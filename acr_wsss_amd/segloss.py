@@ -17,45 +17,33 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import _args as A
 from . import _lib as L
 
-MAX_CLASSES = 128                         # 2 <= K <= 128 (include/acr_hip.h)
 _ENERGY_WS_BYTES = 2048                   # ACR_DENSE_ENERGY_WS_BYTES
 
 
 def _logits(logits):
-    if not torch.is_tensor(logits):
-        raise ValueError("logits must be a torch tensor on the GPU, got %s" % type(logits).__name__)
-    if logits.dtype != torch.float32 or logits.dim() != 4 or logits.numel() == 0:
-        raise ValueError("logits must be a (B, K, h, w) float32 tensor, got %s %s" % (logits.dtype, tuple(logits.shape)))
-    if not 2 <= logits.shape[1] <= MAX_CLASSES:
-        raise ValueError("K=%d outside 2..%d" % (logits.shape[1], MAX_CLASSES))
+    logits = A.tensor_arg(logits, "logits", torch.float32, shape=("B", "K", "h", "w"), contiguous=False, on_gpu=False)
+    if not 2 <= logits.shape[1] <= A.MAX_SEG_CLASSES:
+        raise ValueError("K=%d outside 2..%d" % (logits.shape[1], A.MAX_SEG_CLASSES))
     return logits
 
 
 def _label(label, logits):
-    """(B, W, H) contiguous uint8 on the device of ``logits``; numpy arrays are uploaded; a single (W, H) map serves a batch of
-    one.  The arguments are judged before the device is asked for: a bad shape is a ValueError with or without a GPU."""
+    """(B, W, H) contiguous uint8 on the device of ``logits``; numpy arrays and host tensors are uploaded; a single (W, H) map
+    serves a batch of one.  The arguments are judged before the device is asked for: a bad shape is a ValueError with or without a
+    GPU."""
     b = logits.shape[0]
-    if not torch.is_tensor(label):
-        label = np.asarray(label)
-        if label.dtype != np.uint8:
-            raise ValueError("label must be uint8, got %s" % label.dtype)
-        label = torch.from_numpy(np.ascontiguousarray(label))
-    elif label.dtype != torch.uint8:
-        raise ValueError("label must be a uint8 tensor, got %s" % label.dtype)
+    label = A.tensor_arg(label, "label", torch.uint8, contiguous=False, upload=True, on_gpu=False)
     if label.dim() == 2 and b == 1:
         label = label.unsqueeze(0)
-    if label.dim() != 3 or label.shape[0] != b or label.numel() == 0:
+    if label.dim() != 3 or label.shape[0] != b:
         raise ValueError("label %s must be (%d, W, H)" % (tuple(label.shape), b))
     if logits.shape[2] > label.shape[1] or logits.shape[3] > label.shape[2]:
         raise ValueError("logits %s must be no larger than the label %s" % (tuple(logits.shape[2:]), tuple(label.shape[1:])))
     L.require_gpu(logits)
-    if not label.is_cuda:
-        label = label.to(logits.device, non_blocking=True)
-    if label.device != logits.device:
-        raise ValueError("label lies on %s, the other inputs on %s" % (label.device, logits.device))
-    return label.contiguous()
+    return A.on_device(label, "label", logits.device, upload=True).contiguous()
 
 
 class _SplitCE(torch.autograd.Function):
@@ -70,10 +58,7 @@ class _SplitCE(torch.autograd.Function):
         _, W, H = label.shape
         dev = logits.device
         with torch.cuda.device(dev):
-            nbytes = lib.acr_segloss_ws_bytes(b, k, h, w, W, H)
-            if nbytes < 0:
-                L.check(-1, "acr_segloss_ws_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws, nbytes = L.workspace("acr_segloss_ws_bytes", b, k, h, w, W, H, device=dev)
             probs = torch.empty((b, k, W, H), dtype=torch.float32, device=dev) if want_probs else None
             rowstat = torch.empty((b, W, H, 2), dtype=torch.float32, device=dev)
             sums = torch.empty((b, 2), dtype=torch.float32, device=dev)
@@ -128,28 +113,15 @@ def split_cross_entropy(logits, label, batch_average=False, return_stats=False):
     return out + (sums, counts) if return_stats else out
 
 
-def _images(ori_img, dev, b, hw):
-    """(B, 3, W, H) image values 0..255 (uint8 or a float type, numpy or tensor: the reference's ``ori_images``) on ``dev``"""
-    if not torch.is_tensor(ori_img):
-        ori_img = torch.from_numpy(np.ascontiguousarray(ori_img)).to(dev, non_blocking=True)
-    L.require_gpu(ori_img)
-    if ori_img.device != dev:
-        raise ValueError("ori_img lies on %s, the other inputs on %s" % (ori_img.device, dev))
-    if tuple(ori_img.shape) != (b, 3) + tuple(hw):
-        raise ValueError("ori_img %s must be (%d, 3, W, H) with (W, H) = %s" % (tuple(ori_img.shape), b, tuple(hw)))
-    return ori_img
-
-
-def _rois(croppings, dev, b, hw):
-    """(B, W, H) float32 in [0, 1] on ``dev``"""
-    if not torch.is_tensor(croppings):
-        croppings = torch.from_numpy(np.ascontiguousarray(croppings, dtype=np.float32)).to(dev, non_blocking=True)
-    L.require_gpu(croppings)
-    if croppings.device != dev:
-        raise ValueError("croppings lie on %s, the other inputs on %s" % (croppings.device, dev))
-    if tuple(croppings.shape) != (b,) + tuple(hw):
-        raise ValueError("croppings %s must be (%d, W, H) with (W, H) = %s" % (tuple(croppings.shape), b, tuple(hw)))
-    return croppings.to(torch.float32)
+def _placed(x, name, dev, shape, np_dtype=None):
+    """``x`` -- a tensor of any dtype, or a numpy array (uploaded, as ``np_dtype`` if given) -- on ``dev`` and of ``shape``"""
+    host = not torch.is_tensor(x)
+    if host:
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype))
+    x = A.on_device(x, name, dev, upload=host)
+    if tuple(x.shape) != shape:
+        raise ValueError("%s %s must be %s" % (name, tuple(x.shape), shape))
+    return x
 
 
 def filtered_probs(images, probs, roi, sigma_rgb, sigma_xy):
@@ -206,14 +178,10 @@ class DenseEnergyLoss(torch.nn.Module):
     def inputs(self, ori_img, probs, croppings):
         """What the kernels are given: (images (B, W', H', 3) uint8, probs (B, K, W', H'), roi (B, W', H'), sigma_xy') after the
         ``scale_factor`` plumbing"""
-        if not torch.is_tensor(probs):
-            raise ValueError("probs must be a torch tensor on the GPU, got %s" % type(probs).__name__)
-        L.require_gpu(probs)
-        if probs.dtype != torch.float32 or probs.dim() != 4 or probs.numel() == 0:
-            raise ValueError("probs must be a (B, K, W, H) float32 tensor, got %s %s" % (probs.dtype, tuple(probs.shape)))
+        probs = A.tensor_arg(probs, "probs", torch.float32, shape=("B", "K", "W", "H"), contiguous=False)
         b, _, W, H = probs.shape
-        img = _images(ori_img, probs.device, b, (W, H))
-        roi = _rois(croppings, probs.device, b, (W, H))
+        img = _placed(ori_img, "ori_img", probs.device, (b, 3, W, H))                    # values 0..255, uint8 or a float type
+        roi = _placed(croppings, "croppings", probs.device, (b, W, H), np.float32).to(torch.float32)
         sxy = self.sigma_xy
         if self.scale_factor != 1.0:
             size = (max(1, int(W * self.scale_factor)), max(1, int(H * self.scale_factor)))

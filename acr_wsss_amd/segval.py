@@ -14,12 +14,11 @@ import os
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 from . import crf, data, decoder, pseudo
 from .evaluation import DeviceLabelCounters
 from .infer_cam import shard_indices
-
-MAX_CLASSES = 128                         # 2 <= K <= 128 (include/acr_hip.h)
 
 
 def forward_seg(model, head, x):
@@ -45,15 +44,10 @@ def predict(logits, out_hw, *, hflip=False, probs=None, accumulate=False, want_l
     ``accumulate`` ADDED to -- the label is then the argmax of the updated buffer (the last pass of a sum over scales and flips
     leaves the final map).  ``hflip``: the logits are those of the mirrored image; the result is that of ``logits.flip(-1)``.
     Any ratio per axis works, enlarging or shrinking.  Nothing here synchronises."""
-    if not torch.is_tensor(logits):
-        raise ValueError("logits must be a torch tensor on the GPU, got %s" % type(logits).__name__)
-    if logits.dtype != torch.float32 or logits.dim() != 4 or logits.numel() == 0:
-        raise ValueError("logits must be a (B, K, h, w) float32 tensor, got %s %s" % (logits.dtype, tuple(logits.shape)))
+    logits = A.tensor_arg(logits, "logits", torch.float32, shape=("B", "K", "h", "w"), on_gpu=False)
     b, k, h, w = logits.shape
-    if not 2 <= k <= MAX_CLASSES:
-        raise ValueError("K=%d outside 2..%d" % (k, MAX_CLASSES))
-    if not logits.is_contiguous():
-        raise ValueError("logits must be contiguous, got strides %s" % (tuple(logits.stride()),))
+    if not 2 <= k <= A.MAX_SEG_CLASSES:
+        raise ValueError("K=%d outside 2..%d" % (k, A.MAX_SEG_CLASSES))
     H, W = _out_hw(out_hw)
     if k * h * w >= 2 ** 31 or k * H * W >= 2 ** 31:
         raise ValueError("K * h * w and K * H * W must stay below 2^31 (K=%d, %d x %d -> %d x %d)" % (k, h, w, H, W))
@@ -63,12 +57,10 @@ def predict(logits, out_hw, *, hflip=False, probs=None, accumulate=False, want_l
         if not want_label:
             raise ValueError("nothing to compute: neither a label map nor probs was asked for")
     else:
-        if not torch.is_tensor(probs) or probs.dtype != torch.float32 or tuple(probs.shape) != (b, k, H, W) or not probs.is_contiguous():
-            raise ValueError("probs must be a contiguous (%d, %d, %d, %d) float32 tensor, got %s" % (
-                b, k, H, W, "%s %s" % (probs.dtype, tuple(probs.shape)) if torch.is_tensor(probs) else type(probs).__name__))
-    L.require_gpu(logits, probs)
-    if probs is not None and probs.device != logits.device:
-        raise ValueError("probs lies on %s, the logits on %s" % (probs.device, logits.device))
+        probs = A.tensor_arg(probs, "probs", torch.float32, shape=(b, k, H, W), on_gpu=False)
+    L.require_gpu(logits)
+    if probs is not None:
+        A.on_device(probs, "probs", logits.device)
     lib = L.load()
     with torch.cuda.device(logits.device):
         label = torch.empty((b, H, W), dtype=torch.uint8, device=logits.device) if want_label else None

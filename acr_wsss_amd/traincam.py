@@ -5,6 +5,7 @@ it applies to patch CAMs (infer_cam.py:156-162, 201-202) -- in one entry point, 
 writes the largest tensor of the loop once.  include/acr_hip.h states the rule."""
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 MAX_PLANES = 1 << 22          # B * C (TC_MAX_PLANES, csrc/traincam.hip)
@@ -37,12 +38,7 @@ def training_cams(patch_cam, labels, out_hw, *, grid=None, patch_cam_flipped=Non
         raise ValueError("normalize must be True or False, got %r" % (normalize,))
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 1e-45 < eps < 3e38:       # positive and finite as float32
         raise ValueError("eps must be a positive finite float32 number, got %r" % (eps,))
-    if not torch.is_tensor(patch_cam):
-        raise ValueError("patch_cam must be a torch tensor on the GPU, got %s" % type(patch_cam).__name__)
-    if patch_cam.dtype != torch.float32:
-        raise ValueError("patch_cam must be float32, got %s" % patch_cam.dtype)
-    if patch_cam.dim() != 3 or patch_cam.numel() == 0:
-        raise ValueError("patch_cam must be a non-empty (B, N, C) tensor, got %s" % (tuple(patch_cam.shape),))
+    patch_cam = A.tensor_arg(patch_cam, "patch_cam", torch.float32, shape=("B", "N", "C"), contiguous=False, on_gpu=False)
     B, N, C = patch_cam.shape
     gh, gw = _int_pair(grid, "grid") if grid is not None else (oh // 16, ow // 16)
     if gh < 1 or gw < 1 or gh * gw != N:
@@ -68,9 +64,9 @@ def training_cams(patch_cam, labels, out_hw, *, grid=None, patch_cam_flipped=Non
     if (B - 1) * patch_cam.stride(0) + (N - 1) * patch_cam.stride(1) + C >= 1 << 62 or B * C * oh * ow >= 1 << 60:
         raise ValueError("index range: B * C * oh * ow = %d values, strides %s" % (B * C * oh * ow, tuple(patch_cam.stride())))
     if out is not None:
-        if (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (B, C, oh, ow) or not out.is_contiguous()
-                or out.device != patch_cam.device):
-            raise ValueError("out must be a contiguous float32 (%d, %d, %d, %d) tensor on %s" % (B, C, oh, ow, patch_cam.device))
+        A.tensor_arg(out, "out", torch.float32, shape=(B, C, oh, ow), on_gpu=False)
+        if out.device != patch_cam.device:                  # a ValueError like every refusal here, the host included (below)
+            raise ValueError("out must be on %s like patch_cam, got %s" % (patch_cam.device, out.device))
     if not patch_cam.is_cuda:
         raise ValueError("training_cams runs on the GPU only (got a %s tensor); there is no CPU path" % patch_cam.device)
     dev = patch_cam.device
@@ -81,10 +77,7 @@ def training_cams(patch_cam, labels, out_hw, *, grid=None, patch_cam_flipped=Non
     with torch.cuda.device(dev):
         ws, nbytes = None, 0
         if normalize:
-            nbytes = lib.acr_train_cam_ws_bytes(B, C, oh, ow)
-            if nbytes < 0:
-                L.check(-1, "acr_train_cam_ws_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws, nbytes = L.workspace("acr_train_cam_ws_bytes", B, C, oh, ow, device=dev)
         if out is None:
             out = torch.empty((B, C, oh, ow), dtype=torch.float32, device=dev)
         L.check(lib.acr_train_cam_f32(L.ptr(cam1), L.ptr(cam2), cam1.stride(1), cam1.stride(0), L.ptr(lab), B, C, gh, gw, oh, ow,
