@@ -7,7 +7,9 @@ import ctypes
 
 import numpy as np
 
-MAX_SEG_CLASSES = 128                     # 2 <= K <= 128: the logits segloss trains on and segval predicts from (include/acr_hip.h)
+from . import _abi
+
+MAX_SEG_CLASSES = _abi.constants["ACR_SEG_MAX_K"]   # 2 <= K <= 128: the logits segloss trains on and segval predicts from
 
 
 def gpu_device(device, what):

@@ -108,7 +108,7 @@ def aff_label(la, ha, *, box=None):
         box = ((h + 7) // 8 * 8, (w + 7) // 8 * 8, 0, 0, 0, 0, h, w, 0)
     SH, SW, ct, cl, it, il, ch, cw, flip = (int(v) for v in box)
     rec = np.zeros(1, D.PRE_IMAGE)
-    rec[0] = (0, h, w, h, w, flip, ct, cl, it, il, ch, cw, 0)
+    rec[0] = (0, h, w, h, w, flip, ct, cl, it, il, ch, cw)
     D._check_aff_records(rec, [(h, w)], SH, SW)
     if (kl is not None and not la.is_cuda) or (kh is not None and not ha.is_cuda):      # host planes of a dump: to the GPU
         dev = la.device if la.is_cuda else ha.device if ha.is_cuda else A.gpu_device("cuda", "aff_label")

@@ -15,13 +15,7 @@
 // The planes are walked with a running best per half because n differs from image to image.
 #include "acr_common.h"
 
-struct AffPreImg {         // mirrors acr_pre_image (include/acr_hip.h); rh = h, rw = w here
-    int64_t offset;
-    int32_t h, w;
-    int32_t rh, rw;
-    int32_t flip;
-    int32_t cont_top, cont_left, img_top, img_left, ch, cw;
-};
+struct AffPreImg : acr_pre_image {};   // the header's record (rh = h, rw = w here) under the name the kernel's symbol carries
 
 __global__ __launch_bounds__(256) void aff_label_kernel(const uint8_t* __restrict__ scores, const AffPreImg* __restrict__ tab,
                                                         const int64_t* __restrict__ la_off, const int64_t* __restrict__ ha_off,
@@ -78,7 +72,6 @@ extern "C" int acr_aff_label_batch(const void* scores, const void* table, const 
     ACR_CHECK_ARG(scores && table && la_off && ha_off && n_planes && label_u8, "acr_aff_label_batch: null pointer");
     ACR_CHECK_ARG(batch > 0 && batch <= 65535 && SH > 0 && SW > 0 && SH <= 32768 && SW <= 32768 && SH % 8 == 0 && SW % 8 == 0,
                   "acr_aff_label_batch: bad geometry batch=%d SH=%d SW=%d (multiples of 8 up to 32768)", batch, SH, SW);
-    static_assert(sizeof(AffPreImg) == sizeof(acr_pre_image), "acr_pre_image layout");
     const int units = (SH / 8) * ((SW + 63) / 64);
     hipLaunchKernelGGL(aff_label_kernel, dim3((unsigned)((units + 3) / 4), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t*)scores, (const AffPreImg*)table, la_off, ha_off, n_planes, SH, SW, label_u8);

@@ -9,8 +9,8 @@
 // the cost on inputs without structure.  A histogram too large for LDS is counted the same way straight into the global counters.
 #include "acr_common.h"
 
-#define EVAL_MAX_CLS 128                 // num_cls <= 128: labels and class indices travel as bytes
-#define EVAL_MAX_NT 256
+#define EVAL_MAX_CLS ACR_EVAL_MAX_CLS
+#define EVAL_MAX_NT ACR_EVAL_MAX_NT
 #define EVAL_PEEL 4
 #define EVAL_LDS_BYTES (128 * 1024)      // histograms up to this size live in LDS
 #define EVAL_MAX_BLOCKS 512

@@ -17,7 +17,7 @@
 // bit-identical run to run.  The only atomics count labels in LDS as integers.
 #include "acr_reduce.h"
 
-#define FD_MAX_K 128
+#define FD_MAX_K ACR_FEATDIS_MAX_K
 #define FD_MAX_B 65535
 #define FD_MAX_C (1 << 20)
 #define FD_SLAB 2048                      // pixels of a slab per 32 classes: a slab holds FD_SLAB * ceil(K / 32) pixels

@@ -271,11 +271,7 @@ __global__ __launch_bounds__(256) void h2_colexp_kernel(const float* __restrict_
 // w (co, ci, 3, 3) (sr = 9 ci, kin = ci, sko = 1, ski = 9) and its input-gradient pack w[o][c][8 - t'] as (ci x 9 co)
 // (src + 8, sr = 9, kin = co, sko = -1, ski = 9 ci).  Workgroup = (image, row block, 64 k) as in planes_tile_kernel; `blk` maps a
 // workgroup to its image.  Reads are strided (the weights are a few MB: L2-resident), writes are the image's contiguous chunks.
-struct X3ManyDesc {
-    const float* src;
-    char* dst;
-    int32_t rows, K, sr, kin, sko, ski, wg0, nkb;
-};
+struct X3ManyDesc : acr_x3_many_desc {};   // the header's record under the name the kernel's symbol carries
 __global__ __launch_bounds__(256) void planes_tile_many_kernel(const X3ManyDesc* __restrict__ descs, const int32_t* __restrict__ blk) {
     const X3ManyDesc d = descs[blk[blockIdx.x]];
     const int local = (int)blockIdx.x - d.wg0;
@@ -298,7 +294,7 @@ __global__ __launch_bounds__(256) void planes_tile_many_kernel(const X3ManyDesc*
         }
         bf16x8 p0, p1, p2;
         split3_bf16(v, p0, p1, p2);
-        char* dst = d.dst + IMG_STAGE_OFF(rb, d.nkb, k >> 4, 3) + planes_chunk_off(rr, k8 & 1);
+        char* dst = (char*)d.dst + IMG_STAGE_OFF(rb, d.nkb, k >> 4, 3) + planes_chunk_off(rr, k8 & 1);
         *reinterpret_cast<bf16x8*>(dst) = p0;
         *reinterpret_cast<bf16x8*>(dst + IMG_PLANE_B) = p1;
         *reinterpret_cast<bf16x8*>(dst + 2 * IMG_PLANE_B) = p2;

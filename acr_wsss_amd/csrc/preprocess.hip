@@ -12,13 +12,7 @@
 // -- identical to F.interpolate(bilinear, align_corners=False) without antialiasing.
 #include "acr_common.h"
 
-struct PreImg {            // mirrors acr_pre_image (include/acr_hip.h)
-    int64_t offset;        // byte offset of the image in the packed uint8 buffer
-    int32_t h, w;          // decoded size
-    int32_t rh, rw;        // size after the resize step
-    int32_t flip;          // 1: horizontal flip after the resize
-    int32_t cont_top, cont_left, img_top, img_left, ch, cw;   // RandomCrop boxes (myTool.py:923-955)
-};
+struct PreImg : acr_pre_image {};   // the header's record under the name the kernels' symbols carry
 
 // The normalised image value at pixel (ry, rx) of the resized image: cv2.resize's float INTER_LINEAR sample, then (v / 255 - mean) /
 // std.  Not the fp32 rule of acr_resample.h: the sample position (d + 0.5) * in/out - 0.5 = ((2d + 1) * in - out) / (2 * out) is
@@ -74,7 +68,6 @@ extern "C" int acr_preprocess_batch(const void* packed_u8, const void* table, in
                                     const float* std3, int32_t out_dtype, void* out, void* stream) {
     ACR_CHECK_ARG(packed_u8 && table && out && mean3 && std3, "acr_preprocess_batch: null pointer");
     ACR_CHECK_ARG(batch > 0 && S > 0, "acr_preprocess_batch: bad geometry batch=%d S=%d", batch, S);
-    static_assert(sizeof(PreImg) == sizeof(acr_pre_image), "acr_pre_image layout");
     const dim3 grid((unsigned)((S * S + 255) / 256), (unsigned)batch);
     if (out_dtype == ACR_F32)
         hipLaunchKernelGGL((preprocess_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)packed_u8,

@@ -12,7 +12,7 @@
 #include "acr_common.h"
 #include "pseudo_select.h"                   // the radix selection shared with pseudo_sal.hip
 
-#define PSEUDO_MAX_LABELS 128            // C + 1 <= 128: labels and plane indices travel as bytes
+#define PSEUDO_MAX_LABELS ACR_PSEUDO_MAX_LABELS
 #define PSEUDO_SEL_NONE 255              // sel map: the pixel is in no selection set and can never be sure
 #define PSEUDO_SEL_BG 254                // sel map: M == 0 and bg > bg_sure (sure iff label 0 occurs in L_la)
 // workspace, in 32-bit words: OCC (128: label l occurs in L_la) | PREFIX (128: bits of v per plane) | RANK (128) |

@@ -17,7 +17,7 @@
 #include "acr_common.h"
 #include "pseudo_select.h"
 
-#define PSAL_MAX_CLASSES 127             // labels c + 1 travel as bytes next to 255
+#define PSAL_MAX_CLASSES ACR_SAL_PSEUDO_MAX_CLASSES
 #define PSAL_MAX_BATCH 65535
 #define PSAL_TILE 64                     // opening: edge of a workgroup's output tile = the lanes of one ballot
 #define PSAL_MAX_K 32

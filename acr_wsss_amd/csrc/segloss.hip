@@ -14,7 +14,7 @@
 #include "acr_reduce.h"
 #include "acr_resample.h"
 
-#define SEGLOSS_MAX_K 128
+#define SEGLOSS_MAX_K ACR_SEG_MAX_K
 #define SEGLOSS_MAX_BLOCKS 256            // partial-sum workgroups per image (and of one energy dot)
 #define SEGLOSS_MAX_B 65535
 #define SEGLOSS_RED_BYTES (256 * (8 + 8 + 4 + 4))

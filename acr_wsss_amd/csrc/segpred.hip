@@ -13,7 +13,7 @@
 // depends on the launch geometry -- bit-identical run to run.
 #include "acr_resample.h"
 
-#define SEGPRED_MAX_K 128
+#define SEGPRED_MAX_K ACR_SEG_MAX_K
 #define SEGPRED_MAX_B 65535
 #define SEGPRED_UNROLL 8                  // planes whose texels are in flight together (K = 21: three batches)
 

@@ -10,10 +10,7 @@
 
 typedef __bf16 bf16_t;
 
-struct WStdDesc {
-    uint64_t p0, p1, p2, p3;
-    int32_t cout, n, ch_start, pad;
-};
+struct WStdDesc : acr_wstd_desc {};   // the header's record under the name the kernels' symbols carry
 
 // not acr_block_sum<256>: the same order, but without its leading `0.f +`, which would turn the -0 of an all -0 row into +0
 __device__ __forceinline__ float wstd_block_sum(float v, float* sh) {

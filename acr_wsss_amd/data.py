@@ -34,16 +34,14 @@ import random as _pyrandom
 import numpy as np
 import torch
 
+from . import _abi
 from . import _args as A
 from . import _lib as L
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
 
-PRE_IMAGE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("rh", "<i4"), ("rw", "<i4"), ("flip", "<i4"),
-                      ("cont_top", "<i4"), ("cont_left", "<i4"), ("img_top", "<i4"), ("img_left", "<i4"), ("ch", "<i4"),
-                      ("cw", "<i4"), ("_pad", "<i4")])      # struct acr_pre_image: 8-byte aligned -> 56 bytes
-assert PRE_IMAGE.itemsize == 56
+PRE_IMAGE = _abi.record_dtype("acr_pre_image")
 
 
 def load_cls_labels(path, names, num_classes=20):
@@ -106,12 +104,18 @@ def _upload_packed(arrays, device):
     return offs[:-1], stage, stage.to(device, non_blocking=True)
 
 
+def table_bytes(records, offsets, extra=()):
+    """The bytes of the record table with its ``offset`` column filled in and, right behind it, the int64 values ``extra``."""
+    table = np.zeros(len(records), PRE_IMAGE)              # not records.copy(): a structured copy leaves the struct's padding unset
+    table[:] = records
+    table["offset"] = offsets
+    return np.concatenate([table.view(np.uint8), np.asarray(extra, dtype=np.int64).view(np.uint8)])
+
+
 def _upload_table(records, offsets, device, extra=()):
-    """The record table with its ``offset`` column filled in and, right behind it, the int64 values ``extra``: one pinned buffer (a
-    pageable source would make the "asynchronous" copy drain the stream on the host), one copy."""
-    records = records.copy()
-    records["offset"] = offsets
-    raw = np.concatenate([records.view(np.uint8).reshape(-1), np.asarray(extra, dtype="<i8").view(np.uint8)])
+    """``table_bytes`` on the device: one pinned buffer (a pageable source would make the "asynchronous" copy drain the stream on
+    the host), one copy."""
+    raw = table_bytes(records, offsets, extra)
     table_host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)
     table_host.numpy()[:] = raw
     return table_host.to(device, non_blocking=True)
@@ -153,7 +157,7 @@ class TrainBatcher:
         target_long = self.pyrandom.randint(int(S * 0.9), int(S / 0.875))
         nh, nw = resize_long_target(h, w, target_long)
         ct, cl, it, il, ch, cw = random_crop_boxes(nh, nw, S, self.pyrandom)
-        return (0, h, w, nh, nw, int(flip_p > 0.5), ct, cl, it, il, ch, cw, 0)
+        return (0, h, w, nh, nw, int(flip_p > 0.5), ct, cl, it, il, ch, cw)
 
     def __call__(self, images_uint8, labels):
         """images_uint8: list of (h,w,3) uint8 RGB arrays; labels: (B,C) tensor.  Returns (img, label) on the device."""
@@ -170,7 +174,7 @@ def val_batch(images_uint8, crop_size, device="cuda", dtype=torch.float32):
     S = crop_size
     rec = np.zeros(len(images_uint8), PRE_IMAGE)
     for i, a in enumerate(images_uint8):
-        rec[i] = (0, int(a.shape[0]), int(a.shape[1]), S, S, 0, 0, 0, 0, 0, S, S, 0)
+        rec[i] = (0, int(a.shape[0]), int(a.shape[1]), S, S, 0, 0, 0, 0, 0, S, S)
     return preprocess_batch(images_uint8, rec, S, device, dtype)
 
 
@@ -242,7 +246,7 @@ class SegTrainBatcher(TrainBatcher):
         target_long = self.pyrandom.randint(*self.long_range)
         nh, nw = resize_long_target(h, w, target_long)
         ct, cl, it, il, ch, cw = random_crop_boxes(nh, nw, self.S, self.pyrandom)
-        return (0, h, w, nh, nw, int(flip_p > 0.5), ct, cl, it, il, ch, cw, 0)
+        return (0, h, w, nh, nw, int(flip_p > 0.5), ct, cl, it, il, ch, cw)
 
     def __call__(self, images_uint8, maps_uint8, labels, with_ori=True):
         """images_uint8: list of (h,w,3) uint8 RGB arrays; maps_uint8: list of (h,w) uint8 maps; labels: (B,C) tensor.  Returns
@@ -311,7 +315,7 @@ def aff_record(h, w, S, cont_top, cont_left, img_top, img_left, ch, cw, flip):
     img_left' = w - img_left - cw."""
     if flip:
         cont_left, img_left = S - cont_left - cw, w - img_left - cw
-    return (0, h, w, h, w, int(bool(flip)), cont_top, cont_left, img_top, img_left, ch, cw, 0)
+    return (0, h, w, h, w, int(bool(flip)), cont_top, cont_left, img_top, img_left, ch, cw)
 
 
 def _check_aff_records(records, shapes, SH, SW):
@@ -335,8 +339,8 @@ def aff_label_launch(scores, records, la_off, ha_off, n_planes, SH, SW):
     B, device = len(records), scores.device
     n32 = np.zeros(B + (B & 1), "<i4")                      # int32 counts, padded to whole int64 words of the table's tail
     n32[:B] = n_planes
-    tail = np.concatenate([np.asarray(la_off, "<i8"), np.asarray(ha_off, "<i8"), n32.view("<i8")])
-    table = _upload_table(records, np.zeros(B, "<i8"), device, extra=tail)
+    tail = np.concatenate([np.asarray(la_off, np.int64), np.asarray(ha_off, np.int64), n32.view(np.int64)])
+    table = _upload_table(records, np.zeros(B, np.int64), device, extra=tail)
     base = B * PRE_IMAGE.itemsize
     label = torch.empty((B, SH // 8, SW // 8), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):

@@ -24,6 +24,7 @@ import os
 
 import numpy as np
 
+from . import _abi
 from . import _args as A
 
 CATEGORIES = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow',
@@ -191,7 +192,7 @@ def evaluate_cam_dir(predict_dir, gt_dir, name_list, thresholds=None, num_cls=21
 
 
 # ---- device side ---------------------------------------------------------------------------------------------------------------
-MAX_CLS, MAX_THRESHOLDS = 128, 256        # limits of the ABI (include/acr_hip.h)
+MAX_CLS, MAX_THRESHOLDS = _abi.constants["ACR_EVAL_MAX_CLS"], _abi.constants["ACR_EVAL_MAX_NT"]        # limits of the ABI
 
 
 def _device(device):

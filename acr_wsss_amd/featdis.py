@@ -10,10 +10,11 @@ The reference hard-codes the classes 1..20 and 1024 channels; here the classes a
 The features are read as they lie (NCHW): no (B N, C) copy and no per-class masked copy exists."""
 import torch
 
+from . import _abi
 from . import _args as A
 from . import _lib as L
 
-MAX_CLASSES = 128                         # 2 <= K <= 128 (include/acr_hip.h)
+MAX_CLASSES = _abi.constants["ACR_FEATDIS_MAX_K"]   # 2 <= K <= 128
 MAX_CHANNELS = 1 << 20
 SLAB = 2048                               # FD_SLAB: pixels of a slab per 32 classes (csrc/featdis.hip)
 

@@ -4,9 +4,11 @@ These are the only places where the Python host surface meets the HIP library.  
 allocations (device memory + stream plumbing); all arithmetic of the hot path happens in the kernels.
 """
 import os
+import numpy as np
 import torch
 from torch.autograd import Function
 
+from . import _abi
 from . import _lib as L
 
 HEAD_DIM = 64
@@ -348,6 +350,19 @@ def wgrad_bias_bf16(dy2, x2):
     return dw, db
 
 
+def transpose_records(srcs, dsts, shapes):
+    """The acr_tr_tensor table of (rows, cols) matrices at addresses ``srcs`` with transposes at ``dsts``, the tensor index of
+    every 64 x 64 tile, and the number of tiles."""
+    rec = np.zeros(len(shapes), _abi.record_dtype("acr_tr_tensor"))
+    bt, t0 = [], 0
+    for i, (src, dst, (rows, cols)) in enumerate(zip(srcs, dsts, shapes)):
+        tr, tc = (rows + 63) // 64, (cols + 63) // 64
+        rec[i] = (src, dst, rows, cols, t0, tc)
+        bt.append(np.full(tr * tc, i, dtype=np.int32))
+        t0 += tr * tc
+    return rec, np.concatenate(bt), t0
+
+
 class WeightTransposes:
     """(in, out) copies of Linear weights for the input-gradient GEMMs, refreshed in ONE launch (acr_transpose_many_bf16 /
     _f32; in fp32 the GEMM on the transposed copy is 12-17 % faster than on W as stored, scripts/lab/gemm_nn_vs_nt.py).
@@ -360,7 +375,6 @@ class WeightTransposes:
     itself (train.refresh_weight_transposes(model)); INTEGRATION.md says so."""
 
     def __init__(self, modules, dtype=torch.bfloat16):
-        import numpy as np
         mult = 8 if dtype == torch.bfloat16 else 4
         self.dtype = dtype
         self.lins = [m for m in modules if isinstance(m, torch.nn.Linear) and m.weight.is_cuda and m.weight.dtype == dtype
@@ -370,22 +384,11 @@ class WeightTransposes:
         if not self.ok:
             return
         dev = self.lins[0].weight.device
-        rec = np.zeros(len(self.lins), dtype=[("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("tile0", "<i4"),
-                                              ("tiles_c", "<i4")])
-        bt, t0 = [], 0
-        self.bufs = []
-        for i, m in enumerate(self.lins):
-            rows, cols = m.weight.shape
-            wt = torch.empty((cols, rows), dtype=dtype, device=dev)
-            self.bufs.append(wt)
-            tr, tc = (rows + 63) // 64, (cols + 63) // 64
-            rec[i] = (m.weight.data_ptr(), wt.data_ptr(), rows, cols, t0, tc)
-            bt.append(np.full(tr * tc, i, dtype=np.int32))
-            t0 += tr * tc
+        self.bufs = [torch.empty(tuple(m.weight.shape)[::-1], dtype=dtype, device=dev) for m in self.lins]
         self._ptrs = [m.weight.data_ptr() for m in self.lins]
+        rec, blk, self.nblocks = transpose_records(self._ptrs, [wt.data_ptr() for wt in self.bufs], [tuple(m.weight.shape) for m in self.lins])
         self.table = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-        self.blk = torch.from_numpy(np.concatenate(bt)).to(dev)
-        self.nblocks = t0
+        self.blk = torch.from_numpy(blk).to(dev)
 
     @torch.no_grad()
     def refresh(self):
@@ -541,7 +544,7 @@ def mlp(x, fc1, fc2, resid=None):
 # ------------------------------------------------------------------------------------------------
 # fp32 (reference precision) Linears on the exact-fp32 MFMA GEMM (acr_gemm_f32)
 # ------------------------------------------------------------------------------------------------
-GEMM_MODES = {"nt": 0, "nn": 1, "tn": 2}
+GEMM_MODES = {m: _abi.constants["ACR_GEMM_" + m.upper()] for m in ("nt", "nn", "tn")}
 
 
 def gemm_f32_raw(mode, a, b, c, bias=None, aux=None, act=0, c2=None, colsum=None, math=0):
@@ -586,11 +589,25 @@ def x3_image_t(x2):
     return img
 
 
+def x3_many_records(srcs, dsts, geoms):
+    """The acr_x3_many_desc table of operands (rows, K, sr, kin, sko, ski) at addresses ``srcs`` with images at ``dsts``, the record
+    index of every workgroup, and the number of workgroups."""
+    rec = np.zeros(len(geoms), _abi.record_dtype("acr_x3_many_desc"))
+    blk, wg0 = [], 0
+    for i, (src, dst, (rows, K, sr, kin, sko, ski)) in enumerate(zip(srcs, dsts, geoms)):
+        assert K % 8 == 0 and kin % 8 == 0, (K, kin)
+        nkb = (K + 15) // 16
+        nwg = ((rows + 127) // 128) * ((nkb + 3) // 4)
+        rec[i] = (src, dst, rows, K, sr, kin, sko, ski, wg0, nkb)
+        blk.append(np.full(nwg, i, dtype=np.int32))
+        wg0 += nwg
+    return rec, np.concatenate(blk), wg0
+
+
 def x3_image_many(specs, device):
     """Split-product images of MANY small operands in one launch (acr_x3_image_many): ``specs`` is a list of
     (src tensor, element offset, rows, K, sr, kin, sko, ski) -- element (r, k) of the rows x K operand is
     src[offset + r*sr + (k // kin)*sko + (k % kin)*ski] (include/acr_hip.h).  Returns the images, views of ONE buffer."""
-    import numpy as np
     lib = L.load()
     if torch.cuda.is_current_stream_capturing():
         # the descriptor table below travels through a temporary pinned buffer: a captured copy node would re-read that (by then
@@ -599,19 +616,12 @@ def x3_image_many(specs, device):
         raise RuntimeError("acr_x3_image_many inside a hipGraph capture: its descriptor table is a one-shot host upload")
     sizes = [int(lib.acr_x3_image_floats(rows, K)) for (_, _, rows, K, _, _, _, _) in specs]
     buf = torch.empty(sum(sizes), dtype=torch.float32, device=device)
-    rec = np.zeros(len(specs), dtype=[("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("K", "<i4"), ("sr", "<i4"), ("kin", "<i4"),
-                                      ("sko", "<i4"), ("ski", "<i4"), ("wg0", "<i4"), ("nkb", "<i4")])
-    blk, wg0, off, imgs = [], 0, 0, []
-    for i, ((src, eoff, rows, K, sr, kin, sko, ski), n) in enumerate(zip(specs, sizes)):
-        assert src.dtype == torch.float32 and K % 8 == 0 and kin % 8 == 0, (K, kin)
-        nkb = (K + 15) // 16
-        nwg = ((rows + 127) // 128) * ((nkb + 3) // 4)
-        rec[i] = (src.data_ptr() + 4 * eoff, buf.data_ptr() + 4 * off, rows, K, sr, kin, sko, ski, wg0, nkb)
-        blk.append(np.full(nwg, i, dtype=np.int32))
-        imgs.append(buf[off:off + n])
-        wg0 += nwg
-        off += n
-    raw = np.concatenate([rec.view(np.uint8), np.concatenate(blk).view(np.uint8)])
+    assert all(sp[0].dtype == torch.float32 for sp in specs)
+    offs = [sum(sizes[:i]) for i in range(len(sizes))]
+    imgs = [buf[o:o + n] for o, n in zip(offs, sizes)]
+    rec, blk, wg0 = x3_many_records([sp[0].data_ptr() + 4 * sp[1] for sp in specs], [buf.data_ptr() + 4 * o for o in offs],
+                                    [sp[2:] for sp in specs])
+    raw = np.concatenate([rec.view(np.uint8), blk.view(np.uint8)])
     host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)          # pinned + asynchronous: no host-side stream drain
     host.numpy()[:] = raw
     table = host.to(device, non_blocking=True)
@@ -1505,16 +1515,20 @@ def groupnorm_act(x, weight, bias, act="relu", resid=None, eps=1e-5):
     return GroupNormActFn.apply(x, weight.to(x.dtype), bias.to(x.dtype), resid, GN_ACT[act], eps)
 
 
-def _wstd_desc(p0s, p1s, p2s, device, p3s=None):
-    import numpy as np
-    rec = np.zeros(len(p0s), dtype=[("p0", "<u8"), ("p1", "<u8"), ("p2", "<u8"), ("p3", "<u8"), ("cout", "<i4"),
-                                    ("n", "<i4"), ("ch_start", "<i4"), ("pad", "<i4")])
+def wstd_records(p0, p1, p2, p3, couts, fan_ins):
+    """The acr_wstd_desc table of weights with ``couts`` output channels of fan-in ``fan_ins`` at the four address lists, and the
+    channel total (``ch_start`` is the running sum)."""
+    rec = np.zeros(len(couts), _abi.record_dtype("acr_wstd_desc"))
     ch = 0
-    for i, w in enumerate(p0s):
-        cout = w.shape[0]
-        rec[i] = (w.data_ptr(), p1s[i].data_ptr(), p2s[i].data_ptr() if p2s is not None else 0,
-                  p3s[i].data_ptr() if (p3s is not None and p3s[i] is not None) else 0, cout, w.numel() // cout, ch, 0)
+    for i, (cout, n) in enumerate(zip(couts, fan_ins)):
+        rec[i] = (p0[i], p1[i], p2[i], p3[i], cout, n, ch, 0)
         ch += cout
+    return rec, ch
+
+
+def _wstd_desc(p0s, p1s, p2s, device, p3s=None):
+    ptrs = lambda ts: [t.data_ptr() if t is not None else 0 for t in (ts if ts is not None else [None] * len(p0s))]
+    rec, ch = wstd_records(ptrs(p0s), ptrs(p1s), ptrs(p2s), ptrs(p3s), [w.shape[0] for w in p0s], [w.numel() // w.shape[0] for w in p0s])
     # pinned staging + asynchronous copy: a pageable .to(device) drains the whole stream on the host (twice per step here --
     # the forward's first and the backward's last launch -- which kept Python from running ahead of the GPU)
     raw = rec.view(np.uint8)

@@ -14,10 +14,11 @@ reference's saliency variants the CRF-based siblings and the COCO ones are not c
 import numpy as np
 import torch
 
+from . import _abi
 from . import _args as A
 from . import _lib as L
 
-MAX_LABELS = 128                          # C + 1 <= 128 (include/acr_hip.h)
+MAX_LABELS = _abi.constants["ACR_PSEUDO_MAX_LABELS"]            # C + 1 <= 128
 _WHAT = "pseudo-label composition"
 
 
@@ -73,7 +74,7 @@ def seg_label(cams, classes, la, ha, *, ignore_uncertain=False, bg_alpha=36, cam
     return out
 
 
-MAX_SAL_CLASSES = 127                     # labels c + 1 next to 255 (include/acr_hip.h)
+MAX_SAL_CLASSES = _abi.constants["ACR_SAL_PSEUDO_MAX_CLASSES"]  # labels c + 1 next to 255
 OPEN_TILE = 64                            # edge of the opening kernel's output tile (PSAL_TILE, csrc/pseudo_sal.hip)
 MAX_OPEN = 32                             # largest opening box
 

@@ -17,10 +17,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import _abi
 from . import _args as A
 from . import _lib as L
 
-_ENERGY_WS_BYTES = 2048                   # ACR_DENSE_ENERGY_WS_BYTES
+_ENERGY_WS_BYTES = _abi.constants["ACR_DENSE_ENERGY_WS_BYTES"]
 
 
 def _logits(logits):

@@ -9,9 +9,18 @@ import os
 import torch
 import torch.nn.functional as F
 
+from . import _abi
 from . import ops
 
 _set_versions = getattr(torch._C._autograd, "_unsafe_set_version_counter", None)
+
+
+def sgd_records(host, grad, master, mom, param, n):
+    """Fill ``host``, the (tensors, 5) int64 array over the pinned table, as acr_sgd_tensor records: addresses and element counts
+    per tensor (a scalar serves all)."""
+    rec = host.view(_abi.record_dtype("acr_sgd_tensor")).reshape(-1)
+    rec["grad"], rec["master"], rec["mom"], rec["param"], rec["n"] = grad, master, mom, param, n
+    return rec
 
 
 def acr_loss(cls_list, attn_list, label, p, alpha):
@@ -110,11 +119,8 @@ class PolyOptimizer(torch.optim.SGD):
             if buf is None:
                 buf = st["momentum_buffer"] = torch.zeros_like(p)      # mu * 0 + g == torch's first-step clone(g)
             moms.append(buf.data_ptr())
-        hn = self._f_host.numpy()
-        hn[:, 0] = [0 if p.grad is None else p.grad.data_ptr() for p in ps]
-        hn[:, 1] = [p.data_ptr() for p in ps]
-        hn[:, 2] = moms
-        hn[:, 4] = sizes
+        sgd_records(self._f_host.numpy(), grad=[0 if p.grad is None else p.grad.data_ptr() for p in ps],
+                    master=[p.data_ptr() for p in ps], mom=moms, param=0, n=sizes)
         grp = self.param_groups[0]
         with torch.cuda.device(dev):
             self._f_tab.copy_(self._f_host, non_blocking=True)
@@ -229,20 +235,15 @@ class MasterWeights:
             self._sgd_bc = torch.from_numpy(np.concatenate(bc)).to(dev)
             self._sgd_host = torch.zeros((len(self.masters), 5), dtype=torch.int64).pin_memory()
             self._sgd_tab = torch.zeros((len(self.masters), 5), dtype=torch.int64, device=dev)
-            for i, (m, p) in enumerate(zip(self.masters, self.model_params)):
+            self._sgd_n = [m.numel() for m in self.masters]
+            for m in self.masters:
                 st = opt.state[m]
                 if "momentum_buffer" not in st or st["momentum_buffer"] is None:
                     st["momentum_buffer"] = torch.zeros_like(m)        # mu*0 + g == torch's first-step clone(g)
-                self._sgd_host[i, 1] = m.data_ptr()
-                self._sgd_host[i, 2] = st["momentum_buffer"].data_ptr()
-                self._sgd_host[i, 4] = m.numel()
         host = self._sgd_host
         # the pinned table is re-filled every step: the previous step's copy must have been consumed
         if getattr(self, "_sgd_evt", None) is not None:
             self._sgd_evt.synchronize()
-        hn = host.numpy()
-        hn[:, 0] = [0 if p.grad is None else p.grad.data_ptr() for p in self.model_params]
-        hn[:, 3] = [p.data_ptr() for p in self.model_params]
         # masters / momentum buffers may have been replaced since the table was built (optimizer.load_state_dict on
         # resume does exactly that): every column is refreshed from the live tensors, so a stale pointer cannot survive
         # one pass over the state dict's items (no tensor hashing): ~0.1 ms for 315 tensors
@@ -253,8 +254,9 @@ class MasterWeights:
             if buf is None:
                 buf = opt.state[m]["momentum_buffer"] = torch.zeros_like(m)
             moms.append(buf)
-        hn[:, 1] = [m.data_ptr() for m in self.masters]
-        hn[:, 2] = [b.data_ptr() for b in moms]
+        sgd_records(host.numpy(), grad=[0 if p.grad is None else p.grad.data_ptr() for p in self.model_params],
+                    master=[m.data_ptr() for m in self.masters], mom=[b.data_ptr() for b in moms],
+                    param=[p.data_ptr() for p in self.model_params], n=self._sgd_n)
         self._sgd_tab.copy_(host, non_blocking=True)
         self._sgd_evt = torch.cuda.Event()
         self._sgd_evt.record()

@@ -283,10 +283,14 @@ int acr_x3_image(const float* x, int64_t ld, int32_t rows, int32_t cols, float* 
 int acr_x3_image_t(const float* x, int64_t ld, int32_t rows, int32_t cols, float* image, void* stream);
 size_t acr_gemm_x3_ws_floats(int32_t mode, int32_t act, int32_t M, int32_t N, int32_t K);
 /* Many small images in ONE launch (the stem's standardised convolution weights: W, W^T and the packed 3x3 forms).  `descs`: device
- * array of 48-byte records {const float* src; void* dst; int32 rows, K, sr, kin, sko, ski, wg0, nkb}: image `dst`
- * (acr_x3_image_floats(rows, K) floats) of the rows x K operand whose element (r, k) is src[r*sr + (k/kin)*sko + (k%kin)*ski]
- * (K, kin multiples of 8; nkb = ceil(K / 16)); record i owns workgroups wg0 .. wg0 + ceil(rows/128) * ceil(nkb/4) - 1 and `blk`
- * (device, nwg int32) maps every workgroup to its record. */
+ * array of acr_x3_many_desc records: image `dst` (acr_x3_image_floats(rows, K) floats) of the rows x K operand whose element
+ * (r, k) is src[r*sr + (k/kin)*sko + (k%kin)*ski] (K, kin multiples of 8; nkb = ceil(K / 16)); record i owns workgroups
+ * wg0 .. wg0 + ceil(rows/128) * ceil(nkb/4) - 1 and `blk` (device, nwg int32) maps every workgroup to its record. */
+typedef struct acr_x3_many_desc {
+    const float* src;
+    void* dst;
+    int32_t rows, K, sr, kin, sko, ski, wg0, nkb;
+} acr_x3_many_desc;
 int acr_x3_image_many(const void* descs, const int32_t* blk, int32_t nwg, void* stream);
 int acr_gemm_x3(int32_t mode, int32_t act, const float* a_img, const float* b_img, const float* bias, const float* aux, int64_t ldaux, float* c,
                 int64_t ldc, float* c2, float* colsum, int32_t M, int32_t N, int32_t K, float* ws, void* stream);
@@ -476,10 +480,14 @@ int acr_groupnorm_bwd_mask_f32(const float* dy, const float* x, const uint8_t* r
                                float* dbeta, int32_t N, int32_t C, int32_t HW, void* stream);
 
 /* Weight standardisation of all StdConv2dSame weights of the stem in one launch (models/layers/std_conv.py:56-59).
- * desc_dev: device array of n_conv records {uint64 p0,p1,p2,p3; int32 cout, n, ch_start, pad} sorted by ch_start
- * (first global output-channel index of the conv), n = fan-in.  forward (backward = 0): p0 = w, p1 = w_hat out, p3
- * (nullable) = w_hat^T (n, cout) out -- the copy a 1x1 convolution's input-gradient GEMM reads;
+ * desc_dev: device array of n_conv acr_wstd_desc records sorted by ch_start (first global output-channel index of the
+ * conv), n = fan-in, p0 .. p3 device addresses.  forward (backward = 0): p0 = w, p1 = w_hat out, p3 (nullable) = w_hat^T
+ * (n, cout) out -- the copy a 1x1 convolution's input-gradient GEMM reads;
  * backward: p0 = w, p1 = dL/dw_hat, p2 = dL/dw out.  bf16 tensors, fp32 statistics. */
+typedef struct acr_wstd_desc {
+    uint64_t p0, p1, p2, p3;
+    int32_t cout, n, ch_start, pad;
+} acr_wstd_desc;
 int acr_weight_std_bf16(const void* desc_dev, int32_t n_conv, int32_t total_channels, float eps, int32_t backward,
                         void* stream);
 int acr_weight_std_f32(const void* desc_dev, int32_t n_conv, int32_t total_channels, float eps, int32_t backward,
@@ -648,6 +656,8 @@ int acr_pamr_propagate(const float* w, const float* mask_in, float* mask_out, in
  * acr_eval_confusion_u8: pred, gt (n_pixels) uint8 on the device; conf (num_cls, num_cls + 1), ACCUMULATED into:
  *   conf[gt][min(pred, num_cls)] += 1 for gt < num_cls (1 <= num_cls <= 128); the last column collects predictions outside
  *   the label range, every other gt is ignored.  T = row sums, P = sums of the first num_cls columns, TP = diagonal. */
+#define ACR_EVAL_MAX_CLS 128           /* num_cls <= 128: labels and class indices travel as bytes */
+#define ACR_EVAL_MAX_NT 256            /* thresholds per sweep */
 int acr_eval_sweep_f32(const float* cams, const int32_t* classes, int32_t n, const uint8_t* gt, int32_t h, int32_t w,
                        const float* thresholds, int32_t nt, int32_t num_cls, int64_t* raw, void* stream);
 int acr_eval_sweep_finish(const int64_t* raw, int32_t nt, int32_t num_cls, int64_t* TP, int64_t* P, void* stream);
@@ -677,6 +687,7 @@ int acr_eval_confusion_u8(const uint8_t* pred, const uint8_t* gt, int64_t n_pixe
  *   only if ignore_uncertain != 0 (else it may be null).
  * acr_pseudo_ws_bytes: host only; negative for arguments outside the supported range.
  * The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+#define ACR_PSEUDO_MAX_LABELS 128      /* C + 1 <= 128: labels and plane indices travel as bytes */
 int64_t acr_pseudo_ws_bytes(int32_t K, int32_t h, int32_t w);
 int acr_pseudo_label_f32(const float* scores, const int32_t* classes, int32_t K, int32_t h, int32_t w, int32_t num_classes,
                          uint8_t* out, void* stream);
@@ -718,6 +729,7 @@ int acr_pseudo_compose(const float* cams, const int32_t* classes, int32_t K, con
  * acr_morph_open_u8 (:254, cv2.morphologyEx(frg, cv2.MORPH_OPEN, np.ones((k, k)))): step 4 alone on B masks (h, w): F = src != 0,
  *   dst = 255 where O else 0 -- for a mask of 0 and 255 the grey-scale opening.  1 <= k <= 32; dst is not src.
  * The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
+#define ACR_SAL_PSEUDO_MAX_CLASSES 127 /* labels c + 1 travel as bytes next to 255 */
 int64_t acr_sal_pseudo_ws_bytes(int32_t B, int32_t C, int32_t h, int32_t w);
 int acr_sal_pseudo_compose(const float* cams, const uint8_t* present, int32_t B, int32_t C, int32_t h, int32_t w, const uint8_t* saliency,
                            double bg_alpha, double cut, int32_t open_size, void* ws, int64_t ws_bytes, uint8_t* label,
@@ -761,6 +773,7 @@ int acr_morph_open_u8(const uint8_t* src, int32_t B, int32_t h, int32_t w, int32
  *   8-byte aligned.
  * The entry points allocate nothing and do not synchronise; they capture into a hipGraph. */
 #define ACR_DENSE_ENERGY_WS_BYTES 2048
+#define ACR_SEG_MAX_K 128              /* 2 <= K <= 128: the logits acr_segloss_* train on and acr_segpred_f32 predicts from */
 int64_t acr_segloss_ws_bytes(int32_t B, int32_t K, int32_t h, int32_t w, int32_t W, int32_t H);
 int acr_segloss_fwd(const float* logits, const uint8_t* label, int32_t B, int32_t K, int32_t h, int32_t w, int32_t W, int32_t H,
                     int32_t batch_average, void* ws, int64_t ws_bytes, float* probs, float* rowstat, float* sums, int64_t* counts,
@@ -1071,6 +1084,7 @@ int acr_aff_label_batch(const void* scores, const void* table, const int64_t* la
  * Contract: 1 <= B <= 65535, 2 <= K <= 128, 1 <= C <= 2^20, h, w >= 1, B h w < 2^31; anything else returns ACR_ERR_INVALID and
  * launches nothing.  No float atomics, fixed orders: bit-identical run to run.  The entry points allocate nothing and do not
  * synchronise. */
+#define ACR_FEATDIS_MAX_K 128
 int64_t acr_featdis_ws_bytes(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w);
 int acr_featdis_fwd(const float* seg, const float* feat, int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, void* ws,
                     int64_t ws_bytes, float* loss, uint8_t* labels, int64_t* counts, double* pix, double* cst, void* stream);

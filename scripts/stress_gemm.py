@@ -1,4 +1,4 @@
-"""Repeated correctness check of acr_linear_bf16 (ACR_GEMM_VARIANT selects the kernel) against fp32 matmul."""
+"""Repeated correctness check of acr_linear_bf16 (the entry point chooses its kernel from the shape) against fp32 matmul."""
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from acr_wsss_amd import ops

@@ -4,12 +4,12 @@ rest on, the ABI's names, and what the host refuses before any device is asked f
 import glob
 import os
 import random
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks
 import affdata_ref as R
 import affinity_ref as AR
 
@@ -81,12 +81,10 @@ def test_uncropped_form_pads_like_block_reduce():
 
 def test_abi_names_in_signatures_header_and_makefile():
     from acr_wsss_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "acr_hip.h")).read()
-    assert "voc12/data.py:241-278" in hdr and "tool/imutils.py:167-190" in hdr
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(acr_[a-z0-9_]+)\s*\(", hdr))
+    assert "voc12/data.py:241-278" in abi_checks.HEADER and "tool/imutils.py:167-190" in abi_checks.HEADER
+    declared = abi_checks.PROTOTYPES
     assert "acr_aff_label_batch" in declared and "acr_aff_label_batch" in _lib.SIGNATURES
-    assert len(_lib.SIGNATURES["acr_aff_label_batch"][1]) == 10
+    assert len(_lib.SIGNATURES["acr_aff_label_batch"][1]) == len(abi_checks.declared("acr_aff_label_batch")[1]) == 10
     assert "acr_aff_label_ws_bytes" not in declared and "acr_aff_label_ws_bytes" not in _lib.SIGNATURES     # the kernel needs no workspace
     assert "affdata.hip" in open(os.path.join(ROOT, "acr_wsss_amd", "csrc", "Makefile")).read()
 
@@ -127,7 +125,7 @@ def test_host_validation_errors_before_any_device():
         b([img[0]], [la], [ha])                            # a refused chunk leaves the generators alone
     assert state == (b.pyrandom.getstate(), b.nprandom.get_state()[1].tolist())
     rec = np.zeros(1, D.PRE_IMAGE)
-    rec[0] = (0, 40, 56, 40, 64, 0, 0, 0, 0, 0, 40, 56, 0)                                              # a resize: not this stage's record
+    rec[0] = (0, 40, 56, 40, 64, 0, 0, 0, 0, 0, 40, 56)                                              # a resize: not this stage's record
     with pytest.raises(D.L.AcrHipError, match="inconsistent geometry"):
         b([img], [la], [ha], records=rec)
     from acr_wsss_amd import affinity as A

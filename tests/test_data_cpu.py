@@ -71,9 +71,9 @@ def test_oracle_train_image_contract():
 def test_record_layout_matches_the_c_struct():
     """acr_pre_image has an int64 first member: the C struct is padded to 56 bytes, and so must the numpy record be
     (a 52-byte record made every image after the first read garbage geometry)."""
-    import re, os
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "acr_hip.h")).read()
-    body = re.search(r"typedef struct acr_pre_image \{(.*?)\} acr_pre_image;", hdr, re.S).group(1)
+    import re
+    import abi_checks
+    body = re.search(r"typedef struct acr_pre_image \{(.*?)\} acr_pre_image;", abi_checks.HEADER, re.S).group(1)
     n64 = len(re.findall(r"int64_t\s+\w+", body))
     n32 = sum(len(m.split(",")) for m in re.findall(r"int32_t\s+([\w,\s]+);", body))
     assert (n64, n32) == (1, 11)
@@ -93,7 +93,7 @@ def test_host_validation_needs_no_gpu():
     from acr_wsss_amd._lib import AcrHipError
     img = np.zeros((30, 40, 3), np.uint8)
     rec = np.zeros(1, data.PRE_IMAGE)
-    rec[0] = (0, 30, 40, 24, 32, 1, 4, 0, 0, 0, 24, 32, 0)      # 24 x 32 resized image at rows 4..27 of a 32 x 32 container
+    rec[0] = (0, 30, 40, 24, 32, 1, 4, 0, 0, 0, 24, 32)      # 24 x 32 resized image at rows 4..27 of a 32 x 32 container
     for bad_img in (img.astype(np.float32), img[:, :, :2], img[:, :, 0]):
         with pytest.raises(ValueError):
             data.preprocess_batch([bad_img], rec, 32, "cuda")
@@ -110,7 +110,7 @@ def test_host_validation_needs_no_gpu():
         with pytest.raises(AcrHipError, match="acr_preprocess_batch: inconsistent geometry"):
             data.preprocess_batch([img], bad, 32, "cuda")
     big = np.zeros(1, data.PRE_IMAGE)                            # 2 * rw * w = 2^31: past the kernel's int32 sample positions
-    big[0] = (0, 1, 32768, 1, 32768, 0, 0, 0, 0, 0, 1, 32768, 0)
+    big[0] = (0, 1, 32768, 1, 32768, 0, 0, 0, 0, 0, 1, 32768)
     with pytest.raises(AcrHipError, match="inconsistent geometry"):
         data.preprocess_batch([np.zeros((1, 32768, 3), np.uint8)], big, 32768, "cuda")
     # well-formed arguments, no GPU device: there is no CPU path

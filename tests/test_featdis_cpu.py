@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_checks
 import featdis_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,13 +67,7 @@ def test_restatement_treats_a_zero_vector_as_torch_norm_does():
 def test_symbols_are_declared_bound_and_exported():
     from acr_wsss_amd import _lib as L
     from acr_wsss_amd import featdis
-    hdr = open(os.path.join(ROOT, "include", "acr_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, hdr) and name in L.SIGNATURES
-        ret, args = re.search(r"(\w+)\s+%s\s*\(([^)]*)\)" % name, hdr).groups()
-        assert len(args.split(",")) == len(L.SIGNATURES[name][1]), name
-        assert (ret == "int64_t") == (L.SIGNATURES[name][0] is L.c_int64)
+    abi_checks.check_bound(NAMES, L.SIGNATURES)
     lib = L.load()
     out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
     for name in NAMES:
@@ -82,7 +77,8 @@ def test_symbols_are_declared_bound_and_exported():
     assert "featdis.hip" in make
     src = open(os.path.join(ROOT, "acr_wsss_amd", "csrc", "featdis.hip")).read()
     assert int(re.search(r"#define FD_SLAB (\d+)", src).group(1)) == featdis.SLAB
-    assert int(re.search(r"#define FD_MAX_K (\d+)", src).group(1)) == featdis.MAX_CLASSES
+    assert "#define FD_MAX_K ACR_FEATDIS_MAX_K\n" in src                          # the kernels' limit is the header's
+    assert int(abi_checks.defined("ACR_FEATDIS_MAX_K")) == featdis.MAX_CLASSES == 128
     assert re.search(r"#define FD_MAX_C \(1 << (\d+)\)", src).group(1) == "20" and featdis.MAX_CHANNELS == 1 << 20
 
 

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import abi_checks
 from conftest import GOLDEN, ROOT, load_golden
 from oracle import acr_oracle as O
 
@@ -33,7 +34,7 @@ def test_library_exports_every_declared_symbol(built):
     lib = built.load()
     for name in declared:
         assert getattr(lib, name) is not None
-    assert lib.acr_version() == 2
+    assert lib.acr_version() == int(abi_checks.defined("ACR_ABI_VERSION"))
     assert lib.acr_consistency_ws_floats(16, 12, 785) > 0          # host-only helper, no GPU touched
     # size queries of the attention entry points per arithmetic (host-only): the split-product dtype keeps the bf16 planes of
     # q, k, v behind the score blocks and those of dO behind delta
@@ -44,6 +45,20 @@ def test_library_exports_every_declared_symbol(built):
     d.dtype = built.ACR_F32_BF16X3
     assert lib.acr_attn_scores_floats(d) == blocks + 9 * (2 * 785 * 768) // 2
     assert lib.acr_attn_bwd_ws_floats(d) == 2 * 12 * 785 + 3 * (2 * 785 * 768) // 2
+
+
+def test_every_prototype_is_bound_with_the_declared_types(built):
+    """Type by type: an int64_t bound as c_int32 or a double bound as c_float would pass a count check and hand the library a
+    wrong stride or a truncated pointer."""
+    assert set(abi_checks.PROTOTYPES) == set(built.SIGNATURES)
+    structs = {"acr_attn_desc": built.AttnDesc}
+    for name in abi_checks.PROTOTYPES:
+        ret, params = abi_checks.declared(name)
+        res, args = built.SIGNATURES[name]
+        assert res is abi_checks.ctype_of(ret, structs, ret=True), (name, ret, res)
+        assert len(params) == len(args), name
+        for p, a in zip(params, args):
+            assert a is abi_checks.ctype_of(p.rsplit(None, 1)[0] if "*" not in p else p[:p.rindex("*") + 1], structs), (name, p, a)
 
 
 def test_state_dict_layout_matches_reference():

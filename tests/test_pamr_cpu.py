@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_checks
 from conftest import GOLDEN
 from pamr_ref import pamr_ref
 
@@ -73,6 +74,7 @@ def test_restatement_gives_uniform_weights_on_a_flat_image():
 def test_module_imports_and_signatures_hold_the_entries():
     from acr_wsss_amd import _lib, pamr
     assert {"acr_pamr_affinity", "acr_pamr_propagate"} <= set(_lib.SIGNATURES)
+    assert [len(abi_checks.declared(n)[1]) for n in ("acr_pamr_affinity", "acr_pamr_propagate")] == [9, 10]
     assert _lib.SIGNATURES["acr_pamr_affinity"][0] is ctypes.c_int32 and len(_lib.SIGNATURES["acr_pamr_affinity"][1]) == 9
     assert _lib.SIGNATURES["acr_pamr_propagate"][0] is ctypes.c_int32 and len(_lib.SIGNATURES["acr_pamr_propagate"][1]) == 10
     sig = inspect.signature(pamr.pamr)

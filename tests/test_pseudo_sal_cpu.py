@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_checks
 import pseudo_sal_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,13 +103,7 @@ def test_an_even_opening_is_shifted_but_never_revives_a_label():
 def test_symbols_are_declared_bound_and_exported():
     from acr_wsss_amd import _lib as L
     from acr_wsss_amd import pseudo
-    hdr = open(os.path.join(ROOT, "include", "acr_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, hdr) and name in L.SIGNATURES
-        ret, args = re.search(r"(\w+)\s+%s\s*\(([^)]*)\)" % name, hdr).groups()
-        assert len(args.split(",")) == len(L.SIGNATURES[name][1]), name
-        assert (ret == "int64_t") == (L.SIGNATURES[name][0] is L.c_int64)
+    abi_checks.check_bound(NAMES, L.SIGNATURES)
     lib = L.load()
     for name in NAMES:
         assert hasattr(lib, name)
@@ -120,7 +115,8 @@ def test_symbols_are_declared_bound_and_exported():
     src = open(os.path.join(ROOT, "acr_wsss_amd", "csrc", "pseudo_sal.hip")).read()
     assert int(re.search(r"#define PSAL_TILE (\d+)", src).group(1)) == pseudo.OPEN_TILE
     assert int(re.search(r"#define PSAL_MAX_K (\d+)", src).group(1)) == pseudo.MAX_OPEN
-    assert int(re.search(r"#define PSAL_MAX_CLASSES (\d+)", src).group(1)) == pseudo.MAX_SAL_CLASSES
+    assert "#define PSAL_MAX_CLASSES ACR_SAL_PSEUDO_MAX_CLASSES\n" in src         # the kernels' limit is the header's
+    assert int(abi_checks.defined("ACR_SAL_PSEUDO_MAX_CLASSES")) == pseudo.MAX_SAL_CLASSES == 127
 
 
 def test_ws_bytes_is_a_host_only_query():

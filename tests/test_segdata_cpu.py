@@ -2,14 +2,13 @@
 the REFERENCE's own get_data_from_chunk_v4 / _v3 (tests/golden/make_segdata_golden.py), ``data.SegTrainBatcher`` draws the geometry
 those fixtures encode, the C ABI is declared, bound and exported, and the product judges its arguments before the device is asked
 for and refuses to run without a GPU."""
-import os
 import random
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks
 import segdata_ref as R
 from conftest import ROOT
 from segdata_ref import FIXTURES, load_fixture
@@ -98,12 +97,10 @@ def test_symbol_is_declared_bound_and_exported():
     import __graft_entry__ as g
     g.build()
     from acr_wsss_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "acr_hip.h")).read()
+    hdr = abi_checks.HEADER
     assert "myTool.py:1257-1310" in hdr and "UNPINNED" in hdr and "map_fill" in hdr
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bacr_preprocess_seg_batch\s*\(([^)]*)\)", code)
-    assert m and "acr_preprocess_seg_batch" in L.SIGNATURES
-    assert len(m.group(1).split(",")) == len(L.SIGNATURES["acr_preprocess_seg_batch"][1]) == 14
+    assert "acr_preprocess_seg_batch" in L.SIGNATURES
+    assert len(abi_checks.declared("acr_preprocess_seg_batch")[1]) == len(L.SIGNATURES["acr_preprocess_seg_batch"][1]) == 14
     lib = L.load()
     assert getattr(lib, "acr_preprocess_seg_batch") is not None
     # the C ABI refuses bad arguments on the host (the pointers are never dereferenced)
@@ -124,7 +121,7 @@ def _good():
     img = np.zeros((30, 40, 3), np.uint8)
     m = np.zeros((30, 40), np.uint8)
     rec = np.zeros(1, data.PRE_IMAGE)
-    rec[0] = (0, 30, 40, 24, 32, 1, 4, 0, 0, 0, 24, 32, 0)      # 24 x 32 resized image at rows 4..27 of a 32 x 32 container
+    rec[0] = (0, 30, 40, 24, 32, 1, 4, 0, 0, 0, 24, 32)      # 24 x 32 resized image at rows 4..27 of a 32 x 32 container
     return img, m, rec
 
 

@@ -51,7 +51,7 @@ def case(S, kind):
     rec = np.zeros(len(imgs), data.PRE_IMAGE)
     for i, (a, g) in enumerate(zip(imgs, ref["geoms"])):
         rec[i] = (0, a.shape[0], a.shape[1], g["rh"], g["rw"], g["flip"], g["cont_top"], g["cont_left"], g["img_top"], g["img_left"],
-                  g["ch"], g["cw"], 0)
+                  g["ch"], g["cw"])
     flips = [g["flip"] for g in ref["geoms"]]
     assert 0 < sum(flips) < len(flips), flips                 # a batch with flips both on and off
     return imgs, maps, ref, rec

@@ -4,13 +4,13 @@ exactly under that function's parameters, the C ABI is declared, bound and expor
 product judges its arguments before the device is asked for and refuses to run without a GPU."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import abi_checks
 import segval_ref as R
 from oracle import crf_oracle as C
 
@@ -77,12 +77,9 @@ def test_restated_crf_reproduces_the_oracle_under_its_parameters():
 
 def test_segpred_symbol_is_declared_bound_and_exported():
     from acr_wsss_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "acr_hip.h")).read()
-    assert "myTool.py:1826-1895" in hdr
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bacr_segpred_f32\s*\(([^)]*)\)", code)
-    assert m and "acr_segpred_f32" in L.SIGNATURES
-    assert len(m.group(1).split(",")) == len(L.SIGNATURES["acr_segpred_f32"][1]) == 12
+    assert "myTool.py:1826-1895" in abi_checks.HEADER
+    assert "acr_segpred_f32" in L.SIGNATURES
+    assert len(abi_checks.declared("acr_segpred_f32")[1]) == len(L.SIGNATURES["acr_segpred_f32"][1]) == 12
     assert getattr(L.load(), "acr_segpred_f32") is not None
     assert "segpred.hip" in open(os.path.join(ROOT, "acr_wsss_amd", "csrc", "Makefile")).read()
 

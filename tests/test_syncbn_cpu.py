@@ -5,7 +5,6 @@ host; the gather helper on two gloo ranks; and torch's ``convert_sync_batchnorm`
 import ctypes
 import datetime
 import os
-import re
 import socket
 
 import numpy as np
@@ -14,6 +13,7 @@ import torch
 import torch.multiprocessing as mp
 import torch.nn as nn
 
+import abi_checks
 import decoder_ref as R
 import syncbn_ref as S
 from conftest import ROOT
@@ -92,13 +92,9 @@ def test_merge_is_the_pairwise_update_in_rank_order():
 
 def test_new_symbols_are_declared_bound_and_exported():
     from acr_wsss_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "acr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = L.load()
     for name, nargs in NEW.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, code)
-        assert m and name in L.SIGNATURES, name
-        params = [p.strip() for p in m.group(1).split(",")]
+        params = abi_checks.declared(name)[1]
         res, args = L.SIGNATURES[name]
         assert len(params) == len(args) == nargs and res is ctypes.c_int32, name
         for p, a in zip(params, args):                       # one ctypes type per declared parameter, of the declared kind
