@@ -352,16 +352,25 @@ __global__ __launch_bounds__(256) void crf_norm_kernel(float* __restrict__ norm,
     if (i < n) norm[i] = 1.0f / sqrtf(norm[i] + 1e-20f);
 }
 
-// q[:, p] = softmax_k(-unary[:, p] + msg0[:, p] + msg1[:, p])   (DenseCRF::inference + expAndNormalize)
-__global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict__ unary, const float* __restrict__ msg0,
-                                                         const float* __restrict__ msg1, float* __restrict__ q, int n, int K) {
+// The mean-field logit of plane k at pixel p, -unary + msg0 + msg1 in that order (msg0 / msg1 nullable): every update kernel's.
+__device__ __forceinline__ float crf_logit(const float* unary, const float* msg0, const float* msg1, int64_t i) {
+    float t = -unary[i];
+    if (msg0) t = __fadd_rn(t, msg0[i]);
+    if (msg1) t = __fadd_rn(t, msg1[i]);
+    return t;
+}
+
+// The per-pixel softmax of the mean field (expAndNormalize), written once for every kernel that normalises, for the pixel
+// p = blockIdx.x * 256 + threadIdx.x of the calling thread (every caller launches 256-thread blocks over the pixels):
+// q[k][p] = exp(t_k - max_k t_k) / sum_k exp(t_k - max_k t_k) with t_k = crf_logit(k), the sum taken in the order k = 0 .. K-1, over
+// stacks of K planes of n pixels.  q holds the t_k and then the exponentials between the passes (any K, no register array), so
+// the owning thread stores each q element three times.
+__device__ __forceinline__ void crf_softmax_pixel(const float* unary, const float* msg0, const float* msg1, float* q, int n, int K) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     float mx = -INFINITY;
     for (int k = 0; k < K; ++k) {
-        float t = -unary[(int64_t)k * n + p];
-        if (msg0) t = __fadd_rn(t, msg0[(int64_t)k * n + p]);
-        if (msg1) t = __fadd_rn(t, msg1[(int64_t)k * n + p]);
+        const float t = crf_logit(unary, msg0, msg1, (int64_t)k * n + p);
         q[(int64_t)k * n + p] = t;
         mx = fmaxf(mx, t);
     }
@@ -372,6 +381,80 @@ __global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict
         sum += e;
     }
     for (int k = 0; k < K; ++k) q[(int64_t)k * n + p] = q[(int64_t)k * n + p] / sum;
+}
+
+// q[:, p] = softmax_k(-unary[:, p] + msg0[:, p] + msg1[:, p])   (DenseCRF::inference + expAndNormalize)
+__global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict__ unary, const float* __restrict__ msg0,
+                                                         const float* __restrict__ msg1, float* __restrict__ q, int n, int K) {
+    crf_softmax_pixel(unary, msg0, msg1, q, n, K);
+}
+
+// crf_update_kernel for G groups of K consecutive planes: blockIdx.y is the group, whose sub-stacks start at g * K * n.
+__global__ __launch_bounds__(256) void crf_update_groups_kernel(const float* __restrict__ unary, const float* __restrict__ msg0,
+                                                                const float* __restrict__ msg1, float* __restrict__ q, int n, int K) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int64_t base = (int64_t)blockIdx.y * K * n;
+    const float* u = unary + base;
+    const float* m0 = msg0 ? msg0 + base : nullptr;
+    const float* m1 = msg1 ? msg1 + base : nullptr;
+    crf_softmax_pixel(u, m0, m1, q + base, n, K);
+}
+
+// The last update of a run that only wants the label map: the first index of the largest logit; no exp, no Q.
+__global__ __launch_bounds__(256) void crf_update_argmax_kernel(const float* __restrict__ unary, const float* __restrict__ msg0,
+                                                                const float* __restrict__ msg1, uint8_t* __restrict__ label, int n,
+                                                                int K) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    float best = crf_logit(unary, msg0, msg1, p);
+    int arg = 0;
+    for (int k = 1; k < K; ++k) {
+        const float t = crf_logit(unary, msg0, msg1, (int64_t)k * n + p);
+        if (t > best) { best = t; arg = k; }
+    }
+    label[p] = (uint8_t)arg;
+}
+
+// Scores, unaries and the initial Q of A background alphas from one stack of C CAM planes.  One thread per pixel: each CAM
+// element is read once (its unary does not depend on alpha); group a = planes [a (C + 1), (a + 1)(C + 1)).
+__global__ __launch_bounds__(256) void crf_alpha_unary_kernel(const float* __restrict__ cams, int C, int n,
+                                                              const float* __restrict__ alphas, int A, float clip,
+                                                              float* __restrict__ scores, float* __restrict__ unary,
+                                                              float* __restrict__ q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int64_t group = (int64_t)(C + 1) * n;
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) {
+        const float v = cams[(int64_t)c * n + p];
+        mx = fmaxf(mx, v);
+        const float u = -logf(fminf(fmaxf(v, clip), 1.0f));       // crf_unary_kernel's expression
+        for (int a = 0; a < A; ++a) {
+            const int64_t i = a * group + (int64_t)(c + 1) * n + p;
+            if (scores) scores[i] = v;
+            unary[i] = u;
+        }
+    }
+    const float top = __fsub_rn(1.0f, mx);
+    for (int a = 0; a < A; ++a) {
+        const float bg = powf(top, alphas[a]);
+        if (scores) scores[a * group + p] = bg;
+        unary[a * group + p] = -logf(fminf(fmaxf(bg, clip), 1.0f));
+        crf_softmax_pixel(unary + a * group, nullptr, nullptr, q + a * group, n, C + 1);     // reads back what this thread stored
+    }
+}
+
+// unary_from_labels(zero_unsure=False) with the three energies evaluated by the host, and the initial Q.  A label >= K is unsure.
+__global__ __launch_bounds__(256) void crf_label_unary_kernel(const uint8_t* __restrict__ labels, int n, int K, float e_label,
+                                                              float e_other, float e_unsure, float* __restrict__ unary,
+                                                              float* __restrict__ q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int lab = labels[p];
+    const float other = lab >= K ? e_unsure : e_other, own = lab >= K ? e_unsure : e_label;
+    for (int k = 0; k < K; ++k) unary[(int64_t)k * n + p] = k == lab ? own : other;
+    crf_softmax_pixel(unary, nullptr, nullptr, q, n, K);                                     // reads back what this thread stored
 }
 
 }  // namespace
@@ -507,4 +590,40 @@ extern "C" int acr_crf_update(const void* unary, const void* msg0, const void* m
     hipLaunchKernelGGL(crf_update_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)unary, (const float*)msg0,
                        (const float*)msg1, (float*)q, n_pixels, K);
     return acr_check_launch("acr_crf_update");
+}
+
+extern "C" int acr_crf_alpha_unary(const void* cams, int32_t n_cls, int32_t n_pixels, const void* alphas, int32_t n_alpha, float clip,
+                                   void* scores, void* unary, void* q, void* stream) {
+    ACR_CHECK_ARG(cams && alphas && unary && q && n_cls > 0 && n_pixels > 0 && n_alpha > 0, "acr_crf_alpha_unary: bad arguments");
+    ACR_CHECK_ARG((int64_t)n_alpha * (n_cls + 1) * n_pixels < (1ll << 31), "acr_crf_alpha_unary: %d alphas x %d planes x %d pixels exceed 2^31 - 1",
+                  n_alpha, n_cls + 1, n_pixels);
+    hipLaunchKernelGGL(crf_alpha_unary_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)cams, n_cls, n_pixels,
+                       (const float*)alphas, n_alpha, clip, (float*)scores, (float*)unary, (float*)q);
+    return acr_check_launch("acr_crf_alpha_unary");
+}
+
+extern "C" int acr_crf_update_groups(const void* unary, const void* msg0, const void* msg1, void* q, int32_t n_pixels, int32_t K, int32_t G,
+                                     void* stream) {
+    ACR_CHECK_ARG(unary && q && n_pixels > 0 && K > 0 && G > 0 && G <= 65535, "acr_crf_update_groups: bad arguments (1 <= G <= 65535)");
+    hipLaunchKernelGGL(crf_update_groups_kernel, dim3((n_pixels + 255) / 256, G), dim3(256), 0, (hipStream_t)stream, (const float*)unary,
+                       (const float*)msg0, (const float*)msg1, (float*)q, n_pixels, K);
+    return acr_check_launch("acr_crf_update_groups");
+}
+
+extern "C" int acr_crf_label_unary(const uint8_t* labels_u8, int32_t n_pixels, int32_t n_labels, float e_label, float e_other, float e_unsure,
+                                   void* unary, void* q, void* stream) {
+    ACR_CHECK_ARG(labels_u8 && unary && q && n_pixels > 0, "acr_crf_label_unary: bad arguments");
+    ACR_CHECK_ARG(n_labels >= 2 && n_labels <= 255, "acr_crf_label_unary: n_labels = %d outside 2..255", n_labels);
+    hipLaunchKernelGGL(crf_label_unary_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, labels_u8, n_pixels, n_labels,
+                       e_label, e_other, e_unsure, (float*)unary, (float*)q);
+    return acr_check_launch("acr_crf_label_unary");
+}
+
+extern "C" int acr_crf_update_argmax(const void* unary, const void* msg0, const void* msg1, int32_t n_pixels, int32_t K, uint8_t* label_u8,
+                                     void* stream) {
+    ACR_CHECK_ARG(unary && label_u8 && n_pixels > 0, "acr_crf_update_argmax: bad arguments");
+    ACR_CHECK_ARG(K >= 1 && K <= 256, "acr_crf_update_argmax: K = %d outside 1..256 (the label is a uint8)", K);
+    hipLaunchKernelGGL(crf_update_argmax_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)unary,
+                       (const float*)msg0, (const float*)msg1, label_u8, n_pixels, K);
+    return acr_check_launch("acr_crf_update_argmax");
 }

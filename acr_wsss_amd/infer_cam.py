@@ -249,7 +249,8 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
     ends at a shape change; if a batch does not fit in memory the batch size is halved for the rest of the list (down to 1 =
     the reference's ``chunker(img_list, 1)``, infer_cam.py:123).
     ``out_crf`` (infer_cam.py:68,218-225, defaults of --low_alpha / --high_alpha :72-73): also run the dense CRF on every
-    cam_dict at both alphas, on the GPU (crf.crf_with_alpha), and write ``<out_crf>_<alpha>/<name>.npy``; needs the
+    cam_dict at both alphas, on the GPU (crf.crf_with_alphas_device: one pair of lattices per image, every plane with the bits of
+    crf.crf_with_alpha at its alpha), and write ``<out_crf>_<alpha>/<name>.npy``; needs the
     original image as the fifth item element.
     ``out_pamr`` mirrors ``out_crf`` with pixel-adaptive mask refinement (pamr.pamr_with_alpha; the reference imports pamr.py at
     infer_cam.py:14 but never calls it) as the refinement: ``<out_pamr>_<alpha>/<name>.npy`` for both alphas, same
@@ -296,11 +297,11 @@ def infer_cam_list(model, items, out_cam=None, rank=0, world=1, batch_size=8, ou
             if (out_crf is not None or pseudo_crf) and cam_dict:
                 if len(items[i]) < 5:
                     raise ValueError("out_crf needs the original uint8 image as items[i][4] (infer_cam.py:217)")
-                from .crf import crf_with_alpha_device, score_dict
-                on_dev = []
-                for alpha in (low_alpha, high_alpha):
-                    classes, scores = crf_with_alpha_device(cam_dict, alpha, np.asarray(items[i][4]), device=dev)
-                    on_dev.append(scores)
+                from .crf import crf_with_alphas_device, score_dict
+                # both alphas through one pair of lattices; every plane has the bits of crf_with_alpha_device at its alpha
+                classes, both = crf_with_alphas_device(cam_dict, (low_alpha, high_alpha), np.asarray(items[i][4]), device=dev)
+                on_dev = [both[:1 + len(classes)], both[1 + len(classes):]]
+                for alpha, scores in zip((low_alpha, high_alpha), on_dev):
                     if out_crf is not None:
                         folder = out_crf + ("_%s" % alpha)
                         os.makedirs(folder, exist_ok=True)

@@ -9,8 +9,9 @@ raises IndexError there).
 
 ``seg_label_saliency`` is the saliency-guided rule the reference marks "# use this" (``compute_seg_label_3``, myTool.py:188-264;
 ``bg_alpha=32`` gives the label ``compute_seg_label_two_step`` composes, :313-367): a whole batch at once in csrc/pseudo_sal.hip
-behind ``acr_sal_pseudo_compose``, its 10 x 10 opening also on its own as ``morph_open`` (``acr_morph_open_u8``).  Of the
-reference's saliency variants the CRF-based siblings and the COCO ones are not covered, nor ``two_step``'s resize and PNG writes."""
+behind ``acr_sal_pseudo_compose``, its 10 x 10 opening also on its own as ``morph_open`` (``acr_morph_open_u8``).  The
+CRF-based siblings (``compute_seg_label`` / ``compute_seg_label_2``, :57-185) are ``segtrain.crf_labels`` (without their saliency
+line); of the reference's saliency variants the COCO ones are not covered, nor ``two_step``'s resize and PNG writes."""
 import numpy as np
 import torch
 

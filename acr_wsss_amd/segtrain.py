@@ -6,7 +6,9 @@ together: the composition below is this project's.  It ties ``segval.forward_seg
 ``segloss.joint_loss`` and the optimizer together in the order ``train.train_step`` uses for the classification step, and takes the
 tensors ``data.ChunkLoader.get_data_from_chunk_v4`` returns as they are -- nothing leaves the device.  With ``_v3``, which brings a
 saliency map instead of a label, ``saliency_labels`` makes the label on the way (``compute_seg_label_3``, :188-264, the call the
-reference's ``_v3`` loader is written for)."""
+reference's ``_v3`` loader is written for), and ``crf_labels`` from the CAMs through the dense CRF (``compute_seg_label`` /
+``compute_seg_label_2``, :57-185)."""
+import numpy as np
 import torch
 
 from . import featdis, ops, pseudo, segloss, segval
@@ -124,6 +126,47 @@ def joint_train_step(model, head, optimizer, images, ori_images, croppings, labe
     ops.invalidate_weight_images(head)
     terms = dict(terms, acr_loss=acr, celoss=celoss, dloss=dloss, loss=loss, seg_label=seg_label, saliency_out=saliency_out)
     return loss, terms
+
+
+def crf_labels(norm_cam, labels, ori_images, *, low_alpha=4, high_alpha=32, t=10, **seg_label_kw):
+    """The CRF-based pseudo-labels of a training batch, the label source of ``compute_seg_label`` / ``compute_seg_label_2``
+    (myTool.py:57-185) without their saliency line (``crf_label[saliency == 0] = 0``): norm_cam (B, C, S, S) float32 normalised
+    CAMs on the GPU (``traincam.training_cams``), labels (B, C) the image-level labels (any real dtype; the reference's
+    ``cam_label.astype(np.uint8) > 1e-5`` decides which classes are present), ori_images (B, 3, S, S) uint8 on the GPU.  Per image
+    the CAMs of the present classes go through ``crf.crf_with_alphas_device`` in its device form -- both alphas in one mean field
+    of ``t`` iterations, nothing leaves the device -- and ``pseudo.seg_label`` composes the label.  Returns the (B, S, S) uint8
+    label on the GPU that ``segloss.joint_loss`` / ``seg_train_step`` take as ``seg_label``; an image with no present class is 0
+    everywhere.  The CAMs are targets, not part of the graph: they are detached.
+    ``seg_label_kw`` goes to ``pseudo.seg_label``.  The reference's constants are ``low_alpha=8`` (``compute_seg_label``) or 4
+    (``compute_seg_label_2``, the default here), ``high_alpha=32``, and, for its confidence rule, ``ignore_uncertain=True,
+    bg_alpha=32, cam_floor=0.1, fg_quantile=0.6, bg_sure=0.8, crf_sure=0.8``; ``seg_label``'s own defaults are those of
+    ``compute_seg_label_rrm``.  ``compute_seg_label`` itself does not run (``for class_i in 20``), so no fixture pins this
+    composition.  Reading which classes are present costs one host copy of ``labels`` per call (a synchronisation when they
+    sit on the GPU); each image's two lattices synchronise once each (``acr_lattice_info``)."""
+    from . import _args as A
+    from . import crf
+    norm_cam = A.tensor_arg(norm_cam.detach() if torch.is_tensor(norm_cam) else norm_cam, "norm_cam", torch.float32,
+                            shape=("B", "C", "S", "S2"), on_gpu=False)
+    b, c, h, w = norm_cam.shape
+    ori_images = A.tensor_arg(ori_images, "ori_images", torch.uint8, shape=(b, 3, h, w), on_gpu=False)
+    present = torch.as_tensor(labels).detach().to("cpu").numpy()
+    if present.shape != (b, c):
+        raise ValueError("labels must be (%d, %d) like the CAMs, got %s" % (b, c, present.shape))
+    present = present.astype(np.uint8) > 1e-5
+    norm_cam = A.on_device(norm_cam, "norm_cam")
+    ori_images = A.on_device(ori_images, "ori_images", norm_cam.device)
+    seg_label_kw.setdefault("num_classes", c)
+    with torch.cuda.device(norm_cam.device):
+        out = torch.zeros((b, h, w), dtype=torch.uint8, device=norm_cam.device)
+        for i in range(b):
+            classes = [int(j) for j in np.flatnonzero(present[i])]
+            if not classes:
+                continue
+            cams = norm_cam[i, classes].contiguous()
+            img = ori_images[i].permute(1, 2, 0).contiguous()
+            _, refined = crf.crf_with_alphas_device(cams, (low_alpha, high_alpha), img, classes=classes, t=t)
+            out[i] = pseudo.seg_label(cams, classes, refined[:len(classes) + 1], refined[len(classes) + 1:], **seg_label_kw)
+    return out
 
 
 def saliency_labels(norm_cam, labels, saliency, **kw):

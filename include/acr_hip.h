@@ -607,6 +607,34 @@ int acr_lattice_filter(const void* ws, int32_t n_pixels, int32_t d, int32_t n_po
 int acr_crf_unary(const void* probs, void* unary, int64_t n, float clip, void* stream);
 int acr_crf_norm(void* norm, int32_t n_pixels, void* stream);
 int acr_crf_update(const void* unary, const void* msg0, const void* msg1, void* q, int32_t n_pixels, int32_t K, void* stream);
+/* Several score stacks through one mean field (crf.crf_with_alphas_device) and the label-map CRF (tool/imutils.py:387-400
+ * crf_inference_label).  Planes of a lattice filter call are independent, so G groups of K planes filtered in one call and
+ * normalised by acr_crf_update_groups hold, plane for plane, the bits of G separate runs.  All buffers are the caller's, on the
+ * device, fp32 unless named _u8; nothing allocates or synchronises.
+ * acr_crf_alpha_unary: cams = n_cls planes of n_pixels, alphas = n_alpha floats on the device.  With n = 1 + n_cls, group a is
+ *   planes [a n, (a + 1) n) of scores (nullable), unary and q (each n_alpha * n planes):
+ *     scores[a n] = powf(1.0f - max_c cams[c], alphas[a]) (the subtraction in fp32, infer_cam.py:31-33);  scores[a n + 1 + c] = cams[c]
+ *     unary = -logf(clamp(scores, clip, 1))  (acr_crf_unary's expression);  q = softmax over the group's planes of -unary (what
+ *     acr_crf_update gives with null messages).  Each CAM element is read once; scores and unary are stored once, q by its
+ *     owning thread as in acr_crf_update (it holds the softmax's intermediate values).  Requires n_alpha * n * n_pixels < 2^31.
+ * acr_crf_update_groups: acr_crf_update on each of G groups of K consecutive planes (unary, msg0, msg1, q: G * K planes; the
+ *   messages nullable), one launch; per group the operation order is acr_crf_update's, so the result equals G calls on the
+ *   sub-stacks bit for bit.  1 <= G <= 65535.
+ * acr_crf_label_unary: pydensecrf's unary_from_labels(labels, n_labels, gt_prob, zero_unsure=False) with the energies evaluated by
+ *   the caller (in double, rounded to float, so the unary has numpy's bits and the device takes no log): unary[k][p] = e_label
+ *   where k == labels_u8[p] and e_other elsewhere, e_label = -log(gt_prob), e_other = -log((1 - gt_prob) / (n_labels - 1)).
+ *   THIS PROJECT'S EXTENSION: a label >= n_labels (255 included) is "unsure" and gets e_unsure = -log(1 / n_labels) on all
+ *   planes; the reference raises an IndexError there.  q = softmax over the n_labels planes of -unary.  2 <= n_labels <= 255.
+ * acr_crf_update_argmax: the last update of a run that only returns labels: label_u8[p] = the FIRST k with the largest
+ *   -unary[k][p] + msg0[k][p] + msg1[k][p] (additions in acr_crf_update's order; messages nullable), no exp, no Q.  1 <= K <= 256.
+ *   It equals np.argmax of acr_crf_update's Q except where two DISTINCT logits give probabilities that round to the same float:
+ *   np.argmax(Q) then takes the lower index, this the larger logit. */
+int acr_crf_alpha_unary(const void* cams, int32_t n_cls, int32_t n_pixels, const void* alphas, int32_t n_alpha, float clip, void* scores,
+                        void* unary, void* q, void* stream);
+int acr_crf_update_groups(const void* unary, const void* msg0, const void* msg1, void* q, int32_t n_pixels, int32_t K, int32_t G, void* stream);
+int acr_crf_label_unary(const uint8_t* labels_u8, int32_t n_pixels, int32_t n_labels, float e_label, float e_other, float e_unsure, void* unary,
+                        void* q, void* stream);
+int acr_crf_update_argmax(const void* unary, const void* msg0, const void* msg1, int32_t n_pixels, int32_t K, uint8_t* label_u8, void* stream);
 
 /* ---- CAM read-outs ----
  * Patch-token -> class activation (DPT/ACR.py:133-134): out[n][c] = relu(x[n,:] . w[c,:] + bias[c]),
