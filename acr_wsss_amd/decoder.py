@@ -11,7 +11,13 @@ two products on the fp32 GEMMs and the token-major -> NCHW depth-to-space shuffl
 ``reassemble``; ``acr_reassemble_*``).
 There is no CPU path: a CPU tensor raises ``AcrHipError``.  Forward and backward are bit-identical run to run.
 
-Precision: fp32 tensors under ``math="f32"`` and ``math="f32_split"``; bf16 is not built (``decode`` raises).
+Precision: fp32 tensors under ``math="f32"`` and ``math="f32_split"``; under ``math="bf16"`` (bf16 input or taps AND bf16 weights,
+``vitb_hybrid`` only) every map of the decoder is stored in bf16 and the norm, ReLU and upsampling run on the ``*_bf16`` entry
+points, each defined as its fp32 twin's result rounded to bf16 (all sums stay double; the statistics equal the fp32 kernels' bit
+for bit).  The 3x3 convolutions are torch's (MIOpen) in bf16, the 1x1 ones ``acr_conv1x1_bf16`` where the channel counts are on
+its tile.  The running statistics stay fp32 (``train.MasterWeights`` keeps a norm's buffers fp32); the head casts its classifier
+output to fp32 once, so logits, losses and predictions are fp32 in every mode.  A mixed pair (bf16 input with fp32 weights or the
+reverse) and bf16 with a plain ViT backbone raise NotImplementedError.
 Multi-GPU: ``torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)`` (train_acr.py:95), verbatim, is the switch.  A converted norm
 in training mode, inside an initialised process group of more than one rank, normalises with the statistics of ALL ranks' values
 and its backward uses all ranks' gradient sums.  Per layer and direction one fixed-size double tensor is exchanged -- forward
@@ -35,12 +41,26 @@ from . import ops
 
 
 def _dev32(t, what):
+    """a non-empty (N, C, H, W) float32 or bfloat16 tensor on the GPU (the name is older than the bf16 entry points)"""
     if not torch.is_tensor(t):
         raise ValueError("%s must be a torch tensor on the GPU, got %s" % (what, type(t).__name__))
     L.require_gpu(t)
-    if t.dtype != torch.float32 or t.dim() != 4 or t.numel() == 0:
-        raise ValueError("%s must be a non-empty (N, C, H, W) float32 tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    if t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 4 or t.numel() == 0:
+        raise ValueError("%s must be a non-empty (N, C, H, W) float32 or bfloat16 tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
     return t
+
+
+def _entry(name, dtype):
+    """the entry point ``name`` for tensors stored as ``dtype``: (function, its name).  The bf16 twin of acr_X is acr_X_bf16
+    (acr_relu_*_f32: acr_relu_*_bf16); include/acr_hip.h defines it as the fp32 result rounded to bf16."""
+    if dtype == torch.bfloat16:
+        name = (name[:-4] if name.endswith("_f32") else name) + "_bf16"
+    return getattr(L.load(), name), name
+
+
+def _param_grad(g, like):
+    """a parameter gradient the kernels wrote in fp32, in the parameter's dtype (bf16: one rounding)"""
+    return g if g is None or g.dtype == like.dtype else g.to(like.dtype)
 
 
 def _c16(t):
@@ -57,7 +77,6 @@ def _c16(t):
 class _BatchNormAct(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, relu, resid, resid2):
-        lib = L.load()
         x, resid, resid2 = _c16(x), _c16(resid), _c16(resid2)
         n, c, h, w = x.shape
         dev = x.device
@@ -65,9 +84,10 @@ class _BatchNormAct(Function):
             ws, nbytes = L.workspace("acr_bn2d_ws_bytes", n, c, h * w, device=dev)
             stats = torch.empty((c, 2), dtype=torch.float64, device=dev)
             y = torch.empty_like(x)
-            L.check(lib.acr_bn2d_fwd(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
-                                     L.ptr(resid2), n, c, h * w, 1 if training else 0, float(eps), float(momentum), 1 if relu else 0,
-                                     L.ptr(ws), nbytes, L.ptr(stats), L.ptr(y), L.stream_ptr()), "acr_bn2d_fwd")
+            fwd, name = _entry("acr_bn2d_fwd", x.dtype)
+            L.check(fwd(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
+                        L.ptr(resid2), n, c, h * w, 1 if training else 0, float(eps), float(momentum), 1 if relu else 0,
+                        L.ptr(ws), nbytes, L.ptr(stats), L.ptr(y), L.stream_ptr()), name)
         ctx.save_for_backward(x, weight, stats, y if relu else None)
         ctx.training, ctx.relu, ctx.ws = bool(training), bool(relu), ws
         ctx.nres = (resid is not None) + (resid2 is not None)
@@ -75,27 +95,27 @@ class _BatchNormAct(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = L.load()
         x, weight, stats, y = ctx.saved_tensors
         n, c, h, w = x.shape
         dev = x.device
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         need_r = ctx.nres and (ctx.needs_input_grad[9] or ctx.needs_input_grad[10])
         with torch.cuda.device(dev):
-            dy = _c16(dy.to(torch.float32))
+            dy = _c16(dy.to(x.dtype))
             dx = torch.empty_like(x) if need_x else None
             dgamma = torch.empty(c, dtype=torch.float32, device=dev) if need_w else None
             dbeta = torch.empty(c, dtype=torch.float32, device=dev) if need_b else None
             dres = torch.empty_like(x) if (need_r and ctx.relu) else None
             if need_x or need_w or need_b or dres is not None:
-                L.check(lib.acr_bn2d_bwd(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(weight), L.ptr(stats), n, c, h * w, 1 if ctx.training else 0,
-                                         1 if ctx.relu else 0, L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta),
-                                         L.ptr(dres), L.stream_ptr()), "acr_bn2d_bwd")
+                bwd, name = _entry("acr_bn2d_bwd", x.dtype)
+                L.check(bwd(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(weight), L.ptr(stats), n, c, h * w, 1 if ctx.training else 0,
+                            1 if ctx.relu else 0, L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta),
+                            L.ptr(dres), L.stream_ptr()), name)
         if need_r and not ctx.relu:
             dres = dy                                       # without a ReLU the addends' gradient is dy itself
         d1 = dres if (ctx.nres >= 1 and ctx.needs_input_grad[9]) else None
         d2 = dres if (ctx.nres >= 2 and ctx.needs_input_grad[10]) else None
-        return dx, dgamma, dbeta, None, None, None, None, None, None, d1, d2
+        return dx, _param_grad(dgamma, weight), _param_grad(dbeta, weight), None, None, None, None, None, None, d1, d2
 
 
 def gather_rows(t, group=None):
@@ -113,21 +133,21 @@ class _SyncBatchNormAct(Function):
     sums -> gather -> merged backward"""
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, resid, resid2, group):
-        lib = L.load()
         x, resid, resid2 = _c16(x), _c16(resid), _c16(resid2)
         n, c, h, w = x.shape
         dev = x.device
         with torch.cuda.device(dev):
             ws = L.workspace("acr_bn2d_ws_bytes", n, c, h * w, device=dev)[0]
             moments = torch.empty((c, 3), dtype=torch.float64, device=dev)
-            L.check(lib.acr_bn2d_moments(L.ptr(x), n, c, h * w, L.ptr(ws), ws.numel(), L.ptr(moments), L.stream_ptr()), "acr_bn2d_moments")
+            mom, name = _entry("acr_bn2d_moments", x.dtype)
+            L.check(mom(L.ptr(x), n, c, h * w, L.ptr(ws), ws.numel(), L.ptr(moments), L.stream_ptr()), name)
             gathered = gather_rows(moments, group)
             stats = torch.empty(3 * c, dtype=torch.float64, device=dev)          # (C, 2) mean / invstd, then the C merged counts
             y = torch.empty_like(x)
-            L.check(lib.acr_bn2d_fwd_merged(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
-                                            L.ptr(resid2), n, c, h * w, L.ptr(gathered), gathered.shape[0], float(eps), float(momentum),
-                                            1 if relu else 0, L.ptr(ws), ws.numel(), L.ptr(stats), L.ptr(y), L.stream_ptr()),
-                    "acr_bn2d_fwd_merged")
+            fwd, name = _entry("acr_bn2d_fwd_merged", x.dtype)
+            L.check(fwd(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(resid),
+                        L.ptr(resid2), n, c, h * w, L.ptr(gathered), gathered.shape[0], float(eps), float(momentum),
+                        1 if relu else 0, L.ptr(ws), ws.numel(), L.ptr(stats), L.ptr(y), L.stream_ptr()), name)
         ctx.save_for_backward(x, weight, stats, y if relu else None)
         ctx.relu, ctx.ws, ctx.group = bool(relu), ws, group
         ctx.nres = (resid is not None) + (resid2 is not None)
@@ -135,7 +155,6 @@ class _SyncBatchNormAct(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = L.load()
         x, weight, stats, y = ctx.saved_tensors
         n, c, h, w = x.shape
         dev = x.device
@@ -143,26 +162,27 @@ class _SyncBatchNormAct(Function):
         need_r = ctx.nres and (ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
         relu = 1 if ctx.relu else 0
         with torch.cuda.device(dev):
-            dy = _c16(dy.to(torch.float32))
+            dy = _c16(dy.to(x.dtype))
             dx = torch.empty_like(x) if need_x else None
             dgamma = torch.empty(c, dtype=torch.float32, device=dev) if need_w else None
             dbeta = torch.empty(c, dtype=torch.float32, device=dev) if need_b else None
             dres = torch.empty_like(x) if (need_r and ctx.relu) else None
             if need_x or need_w or need_b or dres is not None:
                 sums = torch.empty((c, 2), dtype=torch.float64, device=dev)
-                L.check(lib.acr_bn2d_bwd_sums(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(stats), n, c, h * w, relu, L.ptr(ctx.ws), ctx.ws.numel(),
-                                              L.ptr(sums), L.ptr(dgamma), L.ptr(dbeta), L.stream_ptr()), "acr_bn2d_bwd_sums")
+                bsum, name = _entry("acr_bn2d_bwd_sums", x.dtype)
+                L.check(bsum(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(stats), n, c, h * w, relu, L.ptr(ctx.ws), ctx.ws.numel(),
+                             L.ptr(sums), L.ptr(dgamma), L.ptr(dbeta), L.stream_ptr()), name)
                 if need_x or dres is not None:
                     # the exchange happens exactly when x needs a gradient, as in torch; dres alone is the masked dy, no sums in it
                     rows = gather_rows(sums, ctx.group) if need_x else sums.unsqueeze(0)
-                    L.check(lib.acr_bn2d_bwd_merged(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(weight), L.ptr(stats), L.ptr(rows), rows.shape[0],
-                                                    n, c, h * w, relu, L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(dx), L.ptr(dres),
-                                                    L.stream_ptr()), "acr_bn2d_bwd_merged")
+                    bmer, name = _entry("acr_bn2d_bwd_merged", x.dtype)
+                    L.check(bmer(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(weight), L.ptr(stats), L.ptr(rows), rows.shape[0],
+                                 n, c, h * w, relu, L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(dx), L.ptr(dres), L.stream_ptr()), name)
         if need_r and not ctx.relu:
             dres = dy                                       # without a ReLU the addends' gradient is dy itself
         d1 = dres if (ctx.nres >= 1 and ctx.needs_input_grad[8]) else None
         d2 = dres if (ctx.nres >= 2 and ctx.needs_input_grad[9]) else None
-        return dx, dgamma, dbeta, None, None, None, None, None, d1, d2, None
+        return dx, _param_grad(dgamma, weight), _param_grad(dbeta, weight), None, None, None, None, None, d1, d2, None
 
 
 def _sync_group(bn):
@@ -182,7 +202,11 @@ def batch_norm_act(x, bn, act="none", resid=None, resid2=None):
     ``nn.BatchNorm2d`` uses this process's batch alone.  An ``nn.SyncBatchNorm`` that trains inside a process group of more than
     one rank uses every rank's values (the module docstring says what is exchanged); then one value per channel on a rank is
     legal, an empty batch on a rank is not (every rank must call with N >= 1, or the others wait in the gather).  Anywhere else -- eval mode, no process group, a one-rank group -- it computes the bits of an ``nn.BatchNorm2d`` with
-    the same state.  Differentiable in x, the affine parameters and the addends."""
+    the same state.  Differentiable in x, the affine parameters and the addends.
+    Storage: x, the addends and the norm's weight / bias are all float32 or all bfloat16 (a mix raises ValueError); bf16 takes the
+    ``acr_bn2d_*_bf16`` entry points, whose outputs are the fp32 ones rounded to bf16, and returns parameter gradients in bf16.  The
+    running statistics are float32 in either case: bf16 ones raise ValueError in training mode (keep them fp32, as
+    ``train.MasterWeights`` does) and are upcast into a temporary in eval mode, which is exact and leaves the module as it is."""
     if act not in ("none", "relu"):
         raise ValueError("act must be \"none\" or \"relu\", got %r" % (act,))
     if not isinstance(bn, (nn.BatchNorm2d, nn.SyncBatchNorm)) or not bn.affine:
@@ -197,13 +221,20 @@ def batch_norm_act(x, bn, act="none", resid=None, resid2=None):
     for r in (resid, resid2):
         if r is not None and (_dev32(r, "resid").shape != x.shape or r.device != x.device):
             raise ValueError("an addend %s on %s does not match x %s on %s" % (tuple(r.shape), r.device, tuple(x.shape), x.device))
-    if bn.weight.dtype != torch.float32 or bn.weight.device != x.device:
-        raise ValueError("the norm's parameters must be float32 on %s" % x.device)
+        if r is not None and r.dtype != x.dtype:
+            raise ValueError("an addend is %s, x %s: one storage type per call" % (r.dtype, x.dtype))
+    if bn.weight.dtype != x.dtype or bn.bias.dtype != x.dtype or bn.weight.device != x.device:
+        raise ValueError("the norm's parameters must be %s, as x, on %s (got %s / %s)" % (x.dtype, x.device, bn.weight.dtype, bn.bias.dtype))
     training = bn.training or bn.running_mean is None
     sync, group = _sync_group(bn)
     if training and not sync and x.shape[0] * x.shape[2] * x.shape[3] < 2:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
     rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32):
+        if training:
+            raise ValueError("the running statistics are %s / %s: keep them float32 (a bf16 running_var updated with momentum 0.1 "
+                             "stops moving); train.MasterWeights leaves a norm's buffers fp32" % (rm.dtype, rv.dtype))
+        rm, rv = rm.float(), rv.float()                      # eval mode reads them only: an exact upcast into a temporary
     if bn.training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     if sync:
@@ -217,23 +248,26 @@ class _Relu(Function):
         x = _c16(x)
         y = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            L.check(L.load().acr_relu_fwd_f32(L.ptr(x), x.numel(), L.ptr(y), L.stream_ptr()), "acr_relu_fwd_f32")
+            fwd, name = _entry("acr_relu_fwd_f32", x.dtype)
+            L.check(fwd(L.ptr(x), x.numel(), L.ptr(y), L.stream_ptr()), name)
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         y, = ctx.saved_tensors
-        dy = _c16(dy.to(torch.float32))
+        dy = _c16(dy.to(y.dtype))
         dx = torch.empty_like(y)
         with torch.cuda.device(y.device):
-            L.check(L.load().acr_relu_bwd_f32(L.ptr(y), L.ptr(dy), y.numel(), L.ptr(dx), L.stream_ptr()), "acr_relu_bwd_f32")
+            bwd, name = _entry("acr_relu_bwd_f32", y.dtype)
+            L.check(bwd(L.ptr(y), L.ptr(dy), y.numel(), L.ptr(dx), L.stream_ptr()), name)
         return dx
 
 
 def relu(x):
     """``max(x, 0)`` as a new tensor: the leading ``activation(x)`` of a residual unit (blocks.py:330), whose raw ``x`` stays
-    untouched for the skip (:343).  (The reference's own ``nn.ReLU(False)`` is out of place for the same reason.)"""
+    untouched for the skip (:343).  (The reference's own ``nn.ReLU(False)`` is out of place for the same reason.)  float32 or
+    bfloat16; the gradient has x's dtype."""
     return _Relu.apply(_dev32(x, "x"))
 
 
@@ -242,24 +276,27 @@ class _Upsample2x(Function):
     def forward(ctx, x):
         x = x.contiguous()
         n, c, h, w = x.shape
-        y = torch.empty((n, c, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+        y = torch.empty((n, c, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
         with torch.cuda.device(x.device):
-            L.check(L.load().acr_upsample2x_fwd(L.ptr(x), n * c, h, w, 2 * h, 2 * w, L.ptr(y), L.stream_ptr()), "acr_upsample2x_fwd")
-        ctx.shape = (n, c, h, w)
+            fwd, name = _entry("acr_upsample2x_fwd", x.dtype)
+            L.check(fwd(L.ptr(x), n * c, h, w, 2 * h, 2 * w, L.ptr(y), L.stream_ptr()), name)
+        ctx.shape, ctx.dtype = (n, c, h, w), x.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
         n, c, h, w = ctx.shape
-        dy = dy.to(torch.float32).contiguous()
-        dx = torch.empty((n, c, h, w), dtype=torch.float32, device=dy.device)
+        dy = dy.to(ctx.dtype).contiguous()
+        dx = torch.empty((n, c, h, w), dtype=ctx.dtype, device=dy.device)
         with torch.cuda.device(dy.device):
-            L.check(L.load().acr_upsample2x_bwd(L.ptr(dy), n * c, h, w, 2 * h, 2 * w, L.ptr(dx), L.stream_ptr()), "acr_upsample2x_bwd")
+            bwd, name = _entry("acr_upsample2x_bwd", ctx.dtype)
+            L.check(bwd(L.ptr(dy), n * c, h, w, 2 * h, 2 * w, L.ptr(dx), L.stream_ptr()), name)
         return dx
 
 
 def upsample2x(x):
-    """``F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)`` (blocks.py:407-409) with its backward."""
+    """``F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)`` (blocks.py:407-409) with its backward.  float32, or bfloat16:
+    the fp32 result rounded to bf16."""
     return _Upsample2x.apply(_dev32(x, "x"))
 
 
@@ -309,6 +346,8 @@ def reassemble(y2d, bias, B, T, start, gh, gw, C, s):
     if min(B, gh, gw, C) < 1 or not 0 <= start <= 8 or T != start + gh * gw:
         raise ValueError("need B, gh, gw, C >= 1, 0 <= start <= 8 and T == start + gh * gw, got B=%d T=%d start=%d gh=%d gw=%d C=%d"
                          % (B, T, start, gh, gw, C))
+    if y2d.dtype == torch.bfloat16:
+        raise NotImplementedError("reassemble is not built in bf16 (the plain ViT read-outs are fp32 only)")
     if y2d.dtype != torch.float32 or y2d.dim() != 2 or tuple(y2d.shape) != (B * T, C * s * s) or y2d.stride(1) != 1 or y2d.stride(0) < C * s * s:
         raise ValueError("y2d must be a (B * T, C * s * s) = (%d, %d) float32 matrix with a unit inner stride, got %s %s strides %s"
                          % (B * T, C * s * s, y2d.dtype, tuple(y2d.shape), y2d.stride() if y2d.dim() == 2 else None))
@@ -322,6 +361,8 @@ class _DeconvProduct(Function):
     'nn', input gradient 'nt', weight gradient 'tn' of acr_gemm_f32 -- the weight is neither copied nor transposed"""
     @staticmethod
     def forward(ctx, z, weight, math):
+        if z.dtype != torch.float32 or weight.dtype != torch.float32:
+            raise NotImplementedError("the read-out's second product is not built in bf16 (fp32 only), got %s / %s" % (z.dtype, weight.dtype))
         f = weight.shape[0]
         w2 = weight.view(f, -1)
         y2 = torch.empty((z.shape[0], w2.shape[1]), dtype=torch.float32, device=z.device)
@@ -358,6 +399,9 @@ def readout(tok, start, gh, gw, conv1, deconv, math=0):
     if not torch.is_tensor(tok):
         raise ValueError("tok must be a torch tensor on the GPU, got %s" % type(tok).__name__)
     L.require_gpu(tok)
+    if tok.dtype == torch.bfloat16:
+        raise NotImplementedError("the read-outs of the plain ViT backbones are not built in bf16 (fp32 only; bf16 decode takes "
+                                  "vitb_hybrid)")
     if tok.dtype != torch.float32 or tok.dim() != 3 or tok.numel() == 0:
         raise ValueError("tok must be a non-empty (B, T, D) float32 tensor, got %s %s" % (tok.dtype, tuple(tok.shape)))
     B, T, D = tok.shape
@@ -478,13 +522,21 @@ class SegmentationHead(nn.Sequential):
 
     def forward(self, x):
         x = batch_norm_act(conv(self[0], x, self.acr_math), self[1], "relu")
-        return self[5](conv(self[4], self[3](x), self.acr_math))
+        return self[5](self._f32(conv(self[4], self[3](x), self.acr_math)))
+
+    @staticmethod
+    def _f32(logits_half):
+        """bf16 mode: the classifier's output (B, K + 1, h / 2, w / 2), the smallest tensor of the stage, is cast to fp32 once; the
+        final x2 upsampling and everything behind it (segloss, segpred, featdis' ``seg``) are fp32.  fp32: the tensor itself."""
+        return logits_half.float() if logits_half.dtype == torch.bfloat16 else logits_half
 
     def forward_features(self, x):
         """(logits, feat, logits_half): ``forward``'s logits by the same calls, ``feat`` the tensor the 1x1 classifier ``self[4]``
         reads and ``logits_half`` that classifier's output before the x2 upsampling -- what ``featdis.feature_distance_loss`` takes."""
         feat = self[3](batch_norm_act(conv(self[0], x, self.acr_math), self[1], "relu"))
-        logits_half = conv(self[4], feat, self.acr_math)
+        logits_half = self._f32(conv(self[4], feat, self.acr_math))
+        if feat.dtype == torch.bfloat16:
+            feat = feat.float()              # featdis is fp32: a differentiable copy of (B, features, h / 2, w / 2); cost unmeasured
         return self[5](logits_half), feat, logits_half
 
 
@@ -496,6 +548,18 @@ def make_fusion_block(features, use_bn):
 # ------------------------------------------------------------------------------------------------
 # the decoder pass
 # ------------------------------------------------------------------------------------------------
+def check_precision(model, act_dtype, what, hybrid):
+    """The decoder's one precision rule: activations and weights are both float32 or both bfloat16, and bf16 is built for the
+    hybrid backbone only (the plain ViT read-outs need the fp32 GEMMs: tap 1 of ``vitb`` has f = 96, off the bf16 GEMM's K % 64)"""
+    wd = model.cls_head.weight.dtype
+    if act_dtype != wd or wd not in (torch.float32, torch.bfloat16):
+        raise NotImplementedError("decode takes fp32 tensors with fp32 weights (math \"f32\" and \"f32_split\") or bf16 tensors with bf16 "
+                                  "weights (math \"bf16\"), got %s %s / %s weights" % (act_dtype, what, wd))
+    if wd == torch.bfloat16 and not hybrid:
+        raise NotImplementedError("bf16 decode is built for the hybrid backbone (vitb_hybrid) only: the read-outs of the plain ViT "
+                                  "backbones (readout, reassemble) are fp32, got %s" % model.cur_backbone)
+
+
 def layers_rn(model, x):
     """``forward_vit`` (DPT/vit.py:103-148) and ``scratch.layerN_rn`` (DPT/DPT.py:274-281) of a ``seg=True`` model:
     the four (B, features, h / 4 .. h / 32, ...) maps the fusion blocks take.  Hybrid: taps 1 and 2 are the stem stages the
@@ -512,9 +576,7 @@ def layers_rn(model, x):
     if not torch.is_tensor(x):
         raise ValueError("x must be a torch tensor on the GPU, got %s" % type(x).__name__)
     L.require_gpu(x)
-    if x.dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
-        raise NotImplementedError("decode is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s input / %s weights"
-                                  % (x.dtype, model.cls_head.weight.dtype))
+    check_precision(model, x.dtype, "input", hybrid)
     model._encode(x)
     return layers_rn_taps(model, model.pretrained.activations, x.shape[2:])
 
@@ -574,20 +636,19 @@ def decode(model, x):
     """x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> ``path_1`` (B, features, h / 2, w / 2) of an
     ``ACR(..., seg=True)`` with any of the reference's backbones -- vitb_hybrid, vitb, deit, deit_distilled, vitl --
     (DPT/DPT.py:274-286); ``SegmentationHead`` turns it into (B, num_classes + 1, h, w) logits.  A model without read-out heads
-    (``vit_tiny``) and bf16 raise NotImplementedError.  BatchNorm statistics are per process, or those of all ranks after
+    (``vit_tiny``) raises NotImplementedError; bf16 x with bf16 weights is built for vitb_hybrid, a mixed pair is not.  BatchNorm statistics are per process, or those of all ranks after
     ``nn.SyncBatchNorm.convert_sync_batchnorm`` (see the module docstring)."""
     return fuse(model, *layers_rn(model, x))
 
 
 def decode_taps(model, taps, hw, rows=None):
     """``decode`` from an encoder pass that has already run: ``taps`` = ``model.pretrained.activations`` after ``model._encode(x)``
-    (``forward_cls``, ``forward_cam``, ``forward_mirror``) on a float32 x of spatial size ``hw``; ``rows`` as in
+    (``forward_cls``, ``forward_cam``, ``forward_mirror``) on an x (float32, or bfloat16 as the weights) of spatial size ``hw``; ``rows`` as in
     ``layers_rn_taps``.  On the taps of ``decode``'s own pass the result is ``decode``'s, bit for bit."""
     if not hasattr(model.scratch, "refinenet1"):
         raise ValueError("decode needs a model built with seg=True")
     if any(k not in taps for k in ("1", "2", "3", "4")):
         raise ValueError("taps holds %s: run the encoder pass first (the four taps \"1\" .. \"4\")" % sorted(taps))
-    if taps["4"].dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
-        raise NotImplementedError("decode is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s taps / %s weights"
-                                  % (taps["4"].dtype, model.cls_head.weight.dtype))
+    from .backbone import HybridEmbed
+    check_precision(model, taps["4"].dtype, "taps", isinstance(model.pretrained.model.patch_embed, HybridEmbed))
     return fuse(model, *layers_rn_taps(model, taps, hw, rows))

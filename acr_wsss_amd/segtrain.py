@@ -18,8 +18,9 @@ from .train import refresh_weight_transposes
 def seg_train_step(model, head, optimizer, images, ori_images, croppings, seg_label, dense_energy_layer, *, batch_average=False,
                    grad_sync=None, dis_weight=0.0):
     """``optimizer.zero_grad`` -> ``forward_seg(model, head, images)`` -> ``joint_loss`` -> ``loss = celoss + dloss`` -> backward ->
-    ``optimizer.step``.  images (B,3,S,S) float32 on the GPU (S a multiple of 32), ori_images (B,3,S,S) values 0..255, croppings
-    (S,S,B), seg_label (B,S,S) uint8 (255 = ignore) -- the loader's tuple; ``optimizer`` holds the parameters of ``model`` and
+    ``optimizer.step``.  images (B,3,S,S) float32 on the GPU (S a multiple of 32; or bfloat16 with a bf16 model and head under
+    ``train.MasterWeights(nn.ModuleList([model, head]), ...)``, whose BatchNorm buffers stay fp32), ori_images (B,3,S,S) values
+    0..255, croppings (S,S,B), seg_label (B,S,S) uint8 (255 = ignore) -- the loader's tuple; ``optimizer`` holds the parameters of ``model`` and
     ``head`` that are to train.  ``dense_energy_layer``: a ``segloss.DenseEnergyLoss``, or None for the cross-entropy alone (dloss
     is then 0).  ``batch_average`` is ``joint_loss``'s ``criterion_batch_average``.  ``grad_sync`` (``dp.GradSync``) all-reduces the
     gradients while backward runs, as in ``train.train_step``.  After the update the cached split-product weight images and weight
@@ -65,7 +66,10 @@ def joint_targets(model, labels, saliency, hw, *, cam_kw=None, label_kw=None):
         tok = model.pretrained.activations["4"].detach()           # (2B, T, D), contiguous
         n2, T, D = tok.shape
         B = n2 // 2
-        cams = ops.patch_cam(tok.reshape(n2 * T, D), model.cls_head.weight.detach(), model.cls_head.bias.detach()).view(n2, T, -1)
+        w, b = model.cls_head.weight.detach(), model.cls_head.bias.detach()
+        if tok.dtype != torch.float32:                              # bf16 mode: the targets are computed in fp32 whatever the mode
+            tok, w, b = tok.float(), w.float(), b.float()           # (exact upcasts; 2B x T x D values once per step)
+        cams = ops.patch_cam(tok.reshape(n2 * T, D), w, b).view(n2, T, -1)
         skip = vit.num_tokens
         norm_cam = traincam.training_cams(cams[:B, skip:], labels, hw, patch_cam_flipped=cams[B:, skip:],
                                           grid=(hw[0] // vit.patch_size[1], hw[1] // vit.patch_size[0]), **(cam_kw or {}))
@@ -85,18 +89,19 @@ def joint_train_step(model, head, optimizer, images, ori_images, croppings, labe
       ``refresh_weight_transposes(model)``, ``ops.invalidate_weight_images(head)``.
     images (B,3,S,S) float32 on the GPU (S a multiple of 32), ori_images, croppings as in ``seg_train_step``; labels (B,C) the
     image-level labels; saliency (B,S,S) uint8.  ``cam_kw`` goes to ``training_cams`` (eps), ``label_kw`` to ``saliency_labels``
-    (bg_alpha, cut, open_size).  bf16 raises NotImplementedError as ``decode`` does.  ``dis_weight`` > 0 adds
+    (bg_alpha, cut, open_size).  bf16 images with a bf16 model and head (vitb_hybrid; ``train.MasterWeights`` over
+    ``nn.ModuleList([model, head])`` as the optimizer, which keeps the BatchNorm buffers fp32) run the whole step in bf16 storage
+    with fp32 targets, logits and losses; a mixed pair raises NotImplementedError as ``decode`` does.  ``dis_weight`` > 0 adds
     ``dis_weight * featdis.feature_distance_loss(logits_half, feat)`` (``head.forward_features``) to the loss, beside the
     ``seg_weight`` term; at 0 the step makes the calls it made without the argument.  Returns (loss, terms): the four ACR terms
     (cls_loss_1, cls_loss_2, cls_align, aff_align), acr_loss, celoss, dloss, loss, disloss when ``dis_weight`` > 0, and seg_label /
     saliency_out for inspection."""
     from . import decoder
     from .train import acr_loss
-    if images.dtype != torch.float32 or model.cls_head.weight.dtype != torch.float32:
-        raise NotImplementedError("joint_train_step is built for fp32 tensors (math \"f32\" and \"f32_split\"), got %s input / %s weights"
-                                  % (images.dtype, model.cls_head.weight.dtype))
     if not hasattr(model.scratch, "refinenet1"):
         raise ValueError("joint_train_step needs a model built with seg=True")
+    from .backbone import HybridEmbed
+    decoder.check_precision(model, images.dtype, "input", isinstance(model.pretrained.model.patch_embed, HybridEmbed))
     hw = tuple(images.shape[2:])
     optimizer.zero_grad(set_to_none=True)
     cls_list, attn_list = model.forward_mirror(images, images.flip(-1))

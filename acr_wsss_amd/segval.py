@@ -23,7 +23,8 @@ from .infer_cam import shard_indices
 
 def forward_seg(model, head, x):
     """The reference's ``forward_seg`` (:1869): x (B, 3, h, w) float32 on the GPU, h and w multiples of 32 -> the logits
-    (B, num_classes + 1, h, w) of an ``ACR(..., seg=True)`` (any of the reference's backbones) and its ``decoder.SegmentationHead``."""
+    (B, num_classes + 1, h, w) of an ``ACR(..., seg=True)`` (any of the reference's backbones) and its ``decoder.SegmentationHead``.
+    A bf16 x with a bf16 model and head (vitb_hybrid) runs the pass in bf16 storage; the logits are float32 in either mode."""
     return head(decoder.decode(model, x))
 
 
@@ -97,6 +98,8 @@ def _predict_group(model, head, imgs, sizes, flip, use_crf, dev):
     for n, (size, flipped) in enumerate(passes):
         if at != size:
             x, at = data.val_batch(imgs, size, dev), size
+            if model.cls_head.weight.dtype == torch.bfloat16:
+                x = x.bfloat16()                             # a bf16 model (model.bfloat16()) takes bf16 images; the logits come back fp32
         logits = forward_seg(model, head, x.flip(-1).contiguous() if flipped else x)
         last = n == len(passes) - 1
         for i, img in enumerate(imgs):

@@ -140,7 +140,9 @@ class MasterWeights:
     optimizer -- the reference's PolyOptimizer, quirk included -- runs on fp32 master copies, which are cast
     back into the module after every step.  Compared with autocast this removes the fp32<->bf16 cast kernels
     around every Linear / norm and halves the elementwise and RCCL bytes.  ``optimizer_factory(params)`` must
-    build the optimizer over the list of fp32 masters it is given."""
+    build the optimizer over the list of fp32 masters it is given.  Floating-point buffers become bf16 too, except those of
+    BatchNorm modules (the decoder's and the segmentation head's running statistics), which stay fp32.  For the segmentation
+    steps pass model and head as one module, ``MasterWeights(torch.nn.ModuleList([model, head]), factory)``."""
 
     def __init__(self, model, optimizer_factory):
         self.model_params = [p for p in model.parameters() if p.requires_grad]
@@ -149,8 +151,11 @@ class MasterWeights:
             m.requires_grad_(True)
         for p in self.model_params:
             p.data = p.data.to(torch.bfloat16)
+        # a BatchNorm's running statistics stay fp32: a bf16 running_var updated with momentum 0.1 stops moving (the step is below
+        # half an ulp), and decoder.batch_norm_act refuses bf16 ones in training mode
+        keep = {id(b) for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for b in m.buffers(recurse=False)}
         for b in model.buffers():
-            if b.is_floating_point():
+            if b.is_floating_point() and id(b) not in keep:
                 b.data = b.data.to(torch.bfloat16)
         self.optimizer = optimizer_factory(self.masters)
         self.param_groups = self.optimizer.param_groups

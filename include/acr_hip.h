@@ -888,6 +888,44 @@ int acr_relu_bwd_f32(const float* y, const float* dy, int64_t n, float* dx, void
 int acr_upsample2x_fwd(const float* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* y, void* stream);
 int acr_upsample2x_bwd(const float* dy, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, float* dx, void* stream);
 
+/* ---- the same ten entry points on bf16 STORAGE (the decoder under math "bf16") ----
+ * The argument lists are the fp32 ones; x, y, resid, resid2, dy, dx, dres, gamma and beta are bf16 (spelled void*, as every bf16
+ * pointer of this header), running_mean / running_var / dgamma / dbeta stay float, stats / moments / gathered / sums /
+ * gathered_sums stay double, ws is sized by acr_bn2d_ws_bytes.  Bases 16-byte aligned as above (acr_upsample2x_fwd_bf16: y
+ * 4-byte aligned); any HW >= 1.
+ * Definition.  A bf16 input stands for its exact fp32 value.  Every bf16 output is the fp32 value that the fp32 entry point of
+ * the same name defines for those inputs, rounded to bf16 by round-to-nearest-even.  That fp32 value is the double expression
+ * rounded to fp32 once, so the chain is double -> fp32 -> bf16, deliberately: the fp32 entry point on the upcast inputs is the
+ * yardstick, y_bf16 == bf16(y_fp32) at every element.  Every float and double output is defined exactly as for fp32.
+ * The kernels are the fp32 kernels instantiated on the storage type with the SAME assignment of values to lanes (a lane takes 4
+ * consecutive values: 8-byte loads here, 16-byte there), so every double sum adds the same numbers in the same order and
+ * stats, moments, sums, dgamma, dbeta and the running statistics equal the fp32 entry point's bit for bit.
+ * The ReLU mask of the backward is y > 0 on the STORED bf16 y; it equals the fp32 mask, because a positive normal fp32 never
+ * rounds to a bf16 zero (the two formats share the exponent range).  dres is the masked dy, a copy of bf16 values.
+ * As above: all sums in double in a fixed order (thread, LDS tree, slabs ascending), no float atomics, bit-identical run to run,
+ * nothing outside a plane read or written, nothing allocated or read back, capturable; the same error codes (n < 2 in training
+ * mode, a merged count < 2: ACR_ERR_INVALID; OH != 2 H or OW != 2 W: ACR_ERR_UNSUPPORTED). */
+int acr_bn2d_fwd_bf16(const void* x, const void* gamma, const void* beta, float* running_mean, float* running_var, const void* resid,
+                      const void* resid2, int32_t N, int32_t C, int32_t HW, int32_t training, double eps, double momentum, int32_t relu,
+                      void* ws, int64_t ws_bytes, double* stats, void* y, void* stream);
+int acr_bn2d_bwd_bf16(const void* x, const void* y, const void* dy, const void* gamma, const double* stats, int32_t N, int32_t C,
+                      int32_t HW, int32_t training, int32_t relu, void* ws, int64_t ws_bytes, void* dx, float* dgamma, float* dbeta,
+                      void* dres, void* stream);
+int acr_bn2d_moments_bf16(const void* x, int32_t N, int32_t C, int32_t HW, void* ws, int64_t ws_bytes, double* moments, void* stream);
+int acr_bn2d_fwd_merged_bf16(const void* x, const void* gamma, const void* beta, float* running_mean, float* running_var,
+                             const void* resid, const void* resid2, int32_t N, int32_t C, int32_t HW, const double* gathered, int32_t W,
+                             double eps, double momentum, int32_t relu, void* ws, int64_t ws_bytes, double* stats, void* y,
+                             void* stream);
+int acr_bn2d_bwd_sums_bf16(const void* x, const void* y, const void* dy, const double* stats, int32_t N, int32_t C, int32_t HW,
+                           int32_t relu, void* ws, int64_t ws_bytes, double* sums, float* dgamma, float* dbeta, void* stream);
+int acr_bn2d_bwd_merged_bf16(const void* x, const void* y, const void* dy, const void* gamma, const double* stats,
+                             const double* gathered_sums, int32_t W, int32_t N, int32_t C, int32_t HW, int32_t relu, void* ws,
+                             int64_t ws_bytes, void* dx, void* dres, void* stream);
+int acr_relu_fwd_bf16(const void* x, int64_t n, void* y, void* stream);
+int acr_relu_bwd_bf16(const void* y, const void* dy, int64_t n, void* dx, void* stream);
+int acr_upsample2x_fwd_bf16(const void* x, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, void* y, void* stream);
+int acr_upsample2x_bwd_bf16(const void* dy, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, void* dx, void* stream);
+
 /* ---- read-out reassembly of the plain ViT backbones under seg=True (vitb, deit, deit_distilled, vitl) ----
  * The read-out of tap i (DPT/vit.py:263-341, run by forward_vit :117-146; start_index = 2 for the distilled DeiT, :617-632) is
  * Slice(start) -> Transpose -> Unflatten -> Conv2d(D, f, 1) -> ConvTranspose2d(f, f, s, stride = s) (s = 4, 2; tap 3 has none:

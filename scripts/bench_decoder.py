@@ -2,7 +2,7 @@
 """Micro-benchmark of the DPT decoder kernels (csrc/decoder.hip) and of one fusion block, forward and backward, at the decoder's
 production width: 16 x 256 x {28^2, 112^2} fp32.
 
-    python scripts/bench_decoder.py [--sizes 28 112] [--repeats 7] [--iters 10] [--sync W]
+    python scripts/bench_decoder.py [--sizes 28 112] [--repeats 7] [--iters 10] [--sync W | --readout | --bf16]
 
 Each entry is timed with device events around ``iters`` calls that ROTATE over enough buffer sets to exceed the 256 MiB Infinity
 Cache (so a 13 MB tensor at 28^2 is not served from cache), repeated ``repeats`` times: the median and the [min, max] range are
@@ -19,7 +19,10 @@ cannot be measured on one GPU.
 
 ``--readout [--math f32|f32_split]`` times the read-out heads of the plain ViT backbones instead (``readout_mode``): the two
 csrc/reassemble.hip kernels next to a ``copy_`` of the same size, and ``decoder.readout`` forward + backward next to torch's
-operators, per tap shape of vitb and vitl at 384^2, batch 16."""
+operators, per tap shape of vitb and vitl at 384^2, batch 16.
+
+``--bf16`` times each of the ten bf16-storage entry points (``acr_bn2d_*_bf16``, ``acr_relu_*_bf16``, ``acr_upsample2x_*_bf16``) next
+to its fp32 twin at the same shapes (``bf16_mode``)."""
 import argparse
 import os
 import statistics
@@ -133,6 +136,61 @@ def sync_mode(args):
         torch.cuda.empty_cache()
 
 
+def bf16_mode(args):
+    """Each of the ten ``*_bf16`` entry points next to its fp32 twin, through the C ABI on preallocated buffers, alternating inside
+    every repeat.  Both walk the same number of values with the same lane assignment; the bf16 one moves half the bytes.  The two
+    storage types rotate over the same number of buffer sets, sized so that the bf16 sets alone exceed the Infinity Cache."""
+    from acr_wsss_amd import _lib as L
+    lib, st, p = L.load(), L.stream_ptr(), L.ptr
+    print("%-22s %12s %12s %8s" % ("entry point", "fp32 us", "bf16 us", "bf16/fp32"))
+    for s in args.sizes:
+        hw, n = s * s, N * C * s * s
+        R = rotation(3 * 2 * n)
+        print("\n== %d x %d x %d x %d (%.1f MB fp32, %.1f MB bf16 per tensor, %d rotating buffer sets) ==" % (N, C, s, s, 4 * n / 1e6, 2 * n / 1e6, R))
+        ws = torch.empty(lib.acr_bn2d_ws_bytes(N, C, hw), dtype=torch.uint8, device=DEV)
+        nb = ws.numel()
+        f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=DEV)
+        stats, stats3, moments, sums = f64(C, 2), f64(3 * C), f64(C, 3), f64(1, C, 2)
+        rm, rv, dgamma, dbeta = torch.zeros(C, device=DEV), torch.ones(C, device=DEV), torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+        R4 = max(2, R // 4)
+        sets = {}
+        for tag, dt in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+            mk = lambda k, *shape: [torch.randn(*shape, device=DEV).to(dt) for _ in range(k)]
+            sets[tag] = dict(x=mk(R, N, C, s, s), g=mk(R, N, C, s, s), y=torch.empty(N, C, s, s, device=DEV, dtype=dt),
+                             dx=torch.empty(N, C, s, s, device=DEV, dtype=dt), big=mk(R4, N, C, 2 * s, 2 * s),
+                             gamma=torch.ones(C, device=DEV, dtype=dt), beta=torch.zeros(C, device=DEV, dtype=dt))
+
+        def entries(tag):
+            b, sfx = sets[tag], "" if tag == "f32" else "_bf16"
+            f = lambda name: getattr(lib, (name[:-4] if sfx and name.endswith("_f32") else name) + sfx)
+            x, g, big = (lambda i: p(b["x"][i % R])), (lambda i: p(b["g"][i % R])), (lambda i: p(b["big"][i % R4]))
+            y, dx, ga, be = p(b["y"]), p(b["dx"]), p(b["gamma"]), p(b["beta"])
+            return {
+                "bn2d_fwd": lambda i: f("acr_bn2d_fwd")(x(i), ga, be, p(rm), p(rv), None, None, N, C, hw, 1, 1e-5, 0.1, 0, p(ws), nb, p(stats), y, st),
+                "bn2d_bwd": lambda i: f("acr_bn2d_bwd")(x(i), None, g(i), ga, p(stats), N, C, hw, 1, 0, p(ws), nb, dx, p(dgamma), p(dbeta), None, st),
+                "bn2d_moments": lambda i: f("acr_bn2d_moments")(x(i), N, C, hw, p(ws), nb, p(moments), st),
+                "bn2d_fwd_merged": lambda i: f("acr_bn2d_fwd_merged")(x(i), ga, be, p(rm), p(rv), None, None, N, C, hw, p(moments), 1, 1e-5, 0.1, 0,
+                                                                      p(ws), nb, p(stats3), y, st),
+                "bn2d_bwd_sums": lambda i: f("acr_bn2d_bwd_sums")(x(i), None, g(i), p(stats3), N, C, hw, 0, p(ws), nb, p(sums), p(dgamma), p(dbeta), st),
+                "bn2d_bwd_merged": lambda i: f("acr_bn2d_bwd_merged")(x(i), None, g(i), ga, p(stats3), p(sums), 1, N, C, hw, 0, p(ws), nb, dx, None, st),
+                "relu_fwd": lambda i: f("acr_relu_fwd_f32")(x(i), n, y, st),
+                "relu_bwd": lambda i: f("acr_relu_bwd_f32")(x(i), g(i), n, dx, st),
+                "upsample2x_fwd": lambda i: f("acr_upsample2x_fwd")(x(i), N * C, s, s, 2 * s, 2 * s, big(i + 1), st),
+                "upsample2x_bwd": lambda i: f("acr_upsample2x_bwd")(big(i), N * C, s, s, 2 * s, 2 * s, dx, st)}
+        e32, e16 = entries("f32"), entries("bf16")
+        for name in e32:                                         # in this order: moments and sums are filled before the merged halves read them
+            def checked(fn, name=name):
+                def run(i):
+                    L.check(fn(i), name)
+                return run
+            times = timed({"f32": checked(e32[name]), "bf16": checked(e16[name])}, args.iters, args.repeats)
+            m32, m16 = statistics.median(times["f32"]), statistics.median(times["bf16"])
+            print("%-22s %12.1f %12.1f %8.2f   [fp32 %.1f .. %.1f, bf16 %.1f .. %.1f]" % (name, m32, m16, m16 / m32, min(times["f32"]),
+                                                                                         max(times["f32"]), min(times["bf16"]), max(times["bf16"])))
+        del sets
+        torch.cuda.empty_cache()
+
+
 READOUT_SHAPES = {"vitb": (768, [(96, 4), (192, 2), (384, 1), (768, 1)]), "vitl": (1024, [(256, 4), (512, 2), (1024, 1), (1024, 1)])}
 
 
@@ -213,9 +271,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sync", type=int, default=0, metavar="W", help="time the cross-rank norm's halves for W ranks instead")
+    ap.add_argument("--bf16", action="store_true", help="time each *_bf16 entry point next to its fp32 twin instead")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_decoder.py needs a GPU"
     print("device: %s   N x C = %d x %d fp32   repeats %d x iters %d" % (torch.cuda.get_device_name(0), N, C, args.repeats, args.iters))
+    if args.bf16:
+        return bf16_mode(args)
     if args.sync:
         return sync_mode(args)
     if args.readout:
