@@ -24,7 +24,9 @@ from ONE launch (`acr_preprocess_seg_batch`), on the device and shaped for `segl
 Affinity training (voc12/data.py:222-278 `VOC12AffDataset`: image + the two CRF score dumps) crops and flips the 2n score planes with
 the image, pools them 8 x 8 and reduces them to the label grid the pair masks are cut from: `preprocess_aff_batch`, `AffTrainBatcher`
 and `ChunkLoader.get_data_from_chunk_aff` give images (the existing `acr_preprocess_batch`) and that label (ONE launch of
-`acr_aff_label_batch`), shaped for `affinity.aff_train_step`.
+`acr_aff_label_batch`), shaped for `affinity.aff_train_step`.  PSA's transform list puts torchvision's ColorJitter in front of all that,
+on the PIL image: `ColorJitter` draws its parameters, `acr_color_jitter_batch` (include/acr_hip.h, "colour jitter") applies them to the
+packed uint8 pixels on the device, between the H2D copy and `acr_preprocess_batch`, bit for bit what Pillow computes.
 """
 import concurrent.futures
 import ctypes
@@ -121,12 +123,136 @@ def _upload_table(records, offsets, device, extra=()):
     return table_host.to(device, non_blocking=True)
 
 
-def preprocess_batch(images_uint8, records, S, device, dtype=torch.float32):
+# ------------------------------------------------------------------------------------------------------------------
+# Colour jitter on the packed uint8 batch (PSA's transform list in front of VOC12AffDataset, voc12/data.py:241-278)
+# ------------------------------------------------------------------------------------------------------------------
+JITTER_OPS = ("brightness", "contrast", "saturation", "hue")      # the operation codes ACR_JITTER_* of the header, in order
+assert [_abi.constants["ACR_JITTER_" + k.upper()] for k in JITTER_OPS] == [0, 1, 2, 3] and _abi.constants["ACR_JITTER_NONE"] == -1
+
+
+def _jitter_range(name, value):
+    """torchvision's ``ColorJitter._check_input``: a number v is [max(0, 1 - v), 1 + v] ([-v, v] for the hue), a pair is the range
+    itself; the hue lies within [-0.5, 0.5], the others are >= 0.  None for a range that disables the operation."""
+    hue = name == "hue"
+    center, lo_bound, hi_bound = (0.0, -0.5, 0.5) if hue else (1.0, 0.0, float("inf"))
+    if isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool):
+        v = float(value)
+        if not 0 <= v < float("inf"):
+            raise ValueError("%s=%r: a single number must be finite and non-negative" % (name, value))
+        lo, hi = center - v, center + v
+        if not hue:
+            lo = max(lo, 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        lo, hi = float(value[0]), float(value[1])
+    else:
+        raise ValueError("%s=%r must be a number or a (min, max) pair" % (name, value))
+    if not lo_bound <= lo <= hi <= hi_bound or hi == float("inf"):
+        raise ValueError("%s range (%r, %r) must be ordered and lie within [%s, %s]" % (name, lo, hi, lo_bound, hi_bound))
+    return None if lo == hi == center else (lo, hi)
+
+
+class ColorJitter:
+    """torchvision's ``ColorJitter(brightness, contrast, saturation, hue)`` as a drawer of parameters; PSA's affinity stage uses
+    (0.3, 0.3, 0.3, 0.1).  It owns its OWN ``np.random.RandomState(seed)``, so a batcher's geometry for a given seed is the same with
+    and without jitter.  The stream is this project's: torchvision draws from torch's global generator (``randperm(4)``, then
+    ``Tensor.uniform_``), and no parity of streams is claimed -- only the ranges, the order of the draws and what the drawn
+    parameters do to the pixels (include/acr_hip.h, "colour jitter") are torchvision's."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, seed=None):
+        self.ranges = tuple(_jitter_range(k, v) for k, v in zip(JITTER_OPS, (brightness, contrast, saturation, hue)))
+        self.nprandom = np.random.RandomState(seed)
+
+    def draw(self):
+        """One image's parameters ``(order, b, c, s, hue_factor)``: ``permutation(4)``, then one ``uniform(lo, hi)`` per enabled
+        operation in the order b, c, s, h; None for a disabled one, which draws nothing."""
+        order = tuple(int(k) for k in self.nprandom.permutation(4))
+        return (order,) + tuple(None if r is None else float(self.nprandom.uniform(r[0], r[1])) for r in self.ranges)
+
+
+def jitter_tables(params, n_images):
+    """The per-image tables of ``acr_color_jitter_batch`` from one ``(order, b, c, s, hue_factor)`` per image, judged on the host:
+    -> (order (B, 4) int32, slot 0 first and ACR_JITTER_NONE behind the enabled ones; factors (B, 3) float32; hue_shift (B) int32).
+    A factor of None disables its operation.  ``order`` is a permutation of the enabled operations' codes or of all four (the
+    disabled ones are then skipped)."""
+    if params is None or len(params) != n_images or n_images == 0:
+        raise ValueError("need one set of jitter parameters per image (got %d images, %s sets)" % (n_images, "no" if params is None else len(params)))
+    order, factors, shift = np.full((n_images, 4), -1, np.int32), np.zeros((n_images, 3), np.float32), np.zeros(n_images, np.int32)
+    for i, p in enumerate(params):
+        if not isinstance(p, (tuple, list)) or len(p) != 5:
+            raise ValueError("jitter parameters %d must be (order, brightness, contrast, saturation, hue), got %r" % (i, p))
+        enabled = [k for k in range(4) if p[1 + k] is not None]
+        try:
+            codes = [int(k) for k in p[0]]
+        except (TypeError, ValueError):
+            raise ValueError("jitter parameters %d: order %r is not a sequence of operation codes" % (i, p[0])) from None
+        if sorted(codes) != enabled and sorted(codes) != [0, 1, 2, 3]:
+            raise ValueError("jitter parameters %d: order %r is no permutation of the enabled operations %s" % (i, p[0], enabled))
+        for k in enabled:
+            v = float(p[1 + k])
+            lo, hi = (-0.5, 0.5) if k == 3 else (0.0, float(np.finfo(np.float32).max))
+            if not lo <= v <= hi:                           # a NaN fails too
+                raise ValueError("jitter parameters %d: %s factor %r outside [%s, %s]" % (i, JITTER_OPS[k], p[1 + k], lo, hi))
+            if k == 3:
+                shift[i] = int(v * 255) % 256               # trunc(hue_factor * 255) mod 256: -0.05 -> 244
+            else:
+                factors[i, k] = v                           # Pillow narrows the Python float to a C float
+        codes = [k for k in codes if k in enabled]
+        order[i, :len(codes)] = codes
+    return order, factors, shift
+
+
+def _check_jitter_images(images_uint8):
+    if len(images_uint8) == 0:
+        raise ValueError("need at least one image")
+    for i, a in enumerate(images_uint8):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise ValueError("image %d must be a (h, w, 3) uint8 RGB array, got %s %s" % (i, getattr(a, "dtype", type(a)), getattr(a, "shape", "")))
+
+
+def color_jitter_launch(packed, offsets, shapes, tables):
+    """Run acr_color_jitter_batch IN PLACE on ``packed``, a uint8 device buffer (16-byte aligned) that holds image b, ``shapes[b]`` =
+    (h, w) and h w 3 bytes, at the byte offset ``offsets[b]`` (a multiple of 16: what ``_upload_packed`` produces).  ``tables``: what
+    ``jitter_tables`` returned.  The five per-image arrays go up in one pinned copy; the mean pass and its workspace are left out
+    when no image has contrast.  The callers have validated images and parameters.  Returns what must outlive the launches."""
+    order, factors, shift = tables
+    B, device = len(shapes), packed.device
+    hw = np.asarray([(int(h), int(w)) for h, w in shapes], np.int32).reshape(B, 2)
+    raw = np.concatenate([np.asarray(offsets, np.int64).view(np.uint8), hw.view(np.uint8).reshape(-1), order.view(np.uint8).reshape(-1),
+                          factors.view(np.uint8).reshape(-1), shift.view(np.uint8)])
+    host = torch.empty(raw.size, dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:] = raw
+    table = host.to(device, non_blocking=True)
+    with torch.cuda.device(device):
+        ws = L.workspace("acr_color_jitter_ws_bytes", B, device=device)[0] if bool((order == 1).any()) else None
+        L.check(L.load().acr_color_jitter_batch(L.ptr(packed), L.ptr(table), L.ptr(table[8 * B:]), L.ptr(table[16 * B:]), L.ptr(table[32 * B:]),
+                                                L.ptr(table[44 * B:]), B, L.ptr(ws), L.stream_ptr()), "acr_color_jitter_batch")
+    return host, table, ws
+
+
+def color_jitter_batch(images_uint8, params, device="cuda"):
+    """The colour jitter alone: ``images_uint8`` = list of (h, w, 3) uint8 RGB arrays, ``params`` = one ``(order, b, c, s,
+    hue_factor)`` per image (``ColorJitter.draw``) -> the list of jittered (h, w, 3) uint8 arrays, on the host again.  One H2D copy
+    of the packed pixels, the two launches of ``acr_color_jitter_batch``, one copy back."""
+    _check_jitter_images(images_uint8)
+    tables = jitter_tables(params, len(images_uint8))
+    device = A.gpu_device(device, "acr_color_jitter_batch")
+    offs, stage, packed = _upload_packed(images_uint8, device)
+    keep = color_jitter_launch(packed, offs, [a.shape[:2] for a in images_uint8], tables)
+    out = packed.cpu().numpy()                              # synchronises: stage and keep have done their work
+    del keep, stage
+    return [out[o:o + a.size].reshape(a.shape).copy() for o, a in zip(offs, images_uint8)]
+
+
+def preprocess_batch(images_uint8, records, S, device, dtype=torch.float32, jitter=None):
     """Run acr_preprocess_batch: ``images_uint8`` = list of (h,w,3) uint8 RGB arrays, ``records`` = PRE_IMAGE array with
-    everything but ``offset`` filled in.  One pinned staging buffer, one H2D copy, one launch."""
+    everything but ``offset`` filled in.  One pinned staging buffer, one H2D copy, one launch.  ``jitter``: one ``(order, b, c, s,
+    hue_factor)`` per image (``ColorJitter.draw``); the colour jitter then runs on the packed uint8 pixels on the device
+    (``acr_color_jitter_batch``) between the copy and the launch.  With None nothing of it is called."""
     _check_images("acr_preprocess_batch", images_uint8, records, S)
+    tables = None if jitter is None else jitter_tables(jitter, len(images_uint8))
     device = A.gpu_device(device, "acr_preprocess_batch")
     offs, stage, packed = _upload_packed(images_uint8, device)
+    keep = () if tables is None else color_jitter_launch(packed, offs, [a.shape[:2] for a in images_uint8], tables)
     table = _upload_table(records, offs, device)
     out = torch.empty((len(images_uint8), 3, S, S), dtype=dtype, device=device)
     mean = (ctypes.c_float * 3)(*MEAN)
@@ -136,7 +262,7 @@ def preprocess_batch(images_uint8, records, S, device, dtype=torch.float32):
                                               if dtype != torch.bfloat16 else L.ACR_BF16, L.ptr(out), L.stream_ptr()),
                 "acr_preprocess_batch")
     # the staging buffer and the table must outlive the asynchronous copies: tie them to the output
-    out._acr_keep = (stage, packed, table)
+    out._acr_keep = (stage, packed, table) + tuple(keep)
     return out
 
 
@@ -350,13 +476,14 @@ def aff_label_launch(scores, records, la_off, ha_off, n_planes, SH, SW):
     return label
 
 
-def preprocess_aff_batch(images_uint8, la, ha, records, S, device, dtype=torch.float32):
+def preprocess_aff_batch(images_uint8, la, ha, records, S, device, dtype=torch.float32, jitter=None):
     """The affinity stage's batch under given geometry records (PRE_IMAGE, no resize: rh = h, rw = w; ``aff_record`` writes them):
     ``images_uint8`` = list of (h, w, 3) uint8 RGB arrays, ``la`` / ``ha`` = per image the low- / high-alpha score dict or (n, h, w)
     float32 stack.  Images go through the existing ``preprocess_batch`` (an identity resize has integer sample positions and weights
     0 / 1, hence exact values; the zero padding after the normalisation is the recipe's fill), all scores through ONE pinned
     staging buffer, one H2D copy and one ``acr_aff_label_batch`` launch (include/acr_hip.h, "affinity-stage input").  Returns
     ``(images (B, 3, S, S), label (B, S / 8, S / 8) uint8)`` on the device; ``label`` is a stride-1 grid for ``affinity.pair_codes``.
+    ``jitter``: per image the colour-jitter parameters ``preprocess_batch`` takes; they change the image alone, never the label.
     Everything is validated on the host before any device is asked for."""
     if not (len(images_uint8) == len(la) == len(ha)):
         raise ValueError("need one low- and one high-alpha dump per image (got %d images, %d, %d)" % (len(images_uint8), len(la), len(ha)))
@@ -365,8 +492,10 @@ def preprocess_aff_batch(images_uint8, la, ha, records, S, device, dtype=torch.f
     _check_images("acr_aff_label_batch", images_uint8, records, S)
     stacks = [score_pair(l, h, a.shape[:2], "image %d" % i) for i, (a, l, h) in enumerate(zip(images_uint8, la, ha))]
     _check_aff_records(records, [a.shape[:2] for a in images_uint8], S, S)
+    if jitter is not None:
+        jitter_tables(jitter, len(images_uint8))
     device = A.gpu_device(device, "acr_aff_label_batch")
-    images = preprocess_batch(images_uint8, records, S, device, dtype)
+    images = preprocess_batch(images_uint8, records, S, device, dtype, jitter)
     flat = [s.view(np.uint8).reshape(-1) for pair in stacks for s in pair]
     offs, stage, packed = _upload_packed(flat, device)
     label = aff_label_launch(packed, records, offs[0::2], offs[1::2], [p[0].shape[0] for p in stacks], S, S)
@@ -379,25 +508,37 @@ class AffTrainBatcher(TrainBatcher):
     Normalize + HWC_to_CHW on the image, AvgPool2d(8) on the scores -- for a chunk of decoded images and their two score dumps.
     Flip and box are drawn as ``TrainBatcher`` draws them, without its resize draw: per image ``uniform(0, 1) > 0.5`` from the numpy
     generator, then ``random_crop_boxes`` (w before h) from Python's; the box is mirrored where a flip was drawn (``aff_record``).
-    ColorJitter is not part of this."""
+    ``color_jitter``: a ``ColorJitter``, PSA's first transform; its parameters are drawn per image from ITS generator, so the geometry
+    of a seed does not depend on it."""
+
+    def __init__(self, crop_size, device="cuda", seed=None, dtype=torch.float32, color_jitter=None):
+        super().__init__(crop_size, device, seed, dtype)
+        if color_jitter is not None and not isinstance(color_jitter, ColorJitter):
+            raise ValueError("color_jitter must be a data.ColorJitter or None, got %s" % type(color_jitter).__name__)
+        self.color_jitter, self.last_jitter = color_jitter, None
 
     def draw(self, h, w):
         flip_p = self.nprandom.uniform(0, 1)
         return aff_record(h, w, self.S, *random_crop_boxes(h, w, self.S, self.pyrandom), flip_p > 0.5)
 
-    def __call__(self, images_uint8, la, ha, records=None):
+    def __call__(self, images_uint8, la, ha, records=None, jitter=None):
         """images_uint8: list of (h, w, 3) uint8 RGB arrays; la, ha: per image the low- / high-alpha {key: (h, w)} dict or (n, h, w)
-        float32 stack.  ``records``: a PRE_IMAGE array to replay instead of drawing.  Returns (images (B, 3, S, S), label
-        (B, S / 8, S / 8) uint8) on the device."""
+        float32 stack.  ``records``: a PRE_IMAGE array to replay instead of drawing; ``jitter``: per image the colour-jitter parameters
+        to replay instead of drawing (``last_jitter`` of an earlier call).  Returns (images (B, 3, S, S), label (B, S / 8, S / 8) uint8)
+        on the device."""
+        if jitter is not None and len(jitter) != len(images_uint8):      # before any draw: a refused chunk leaves the generators alone
+            raise ValueError("need one set of jitter parameters per image (got %d images, %d sets)" % (len(images_uint8), len(jitter)))
         if records is None:
-            for a in images_uint8:                           # before any draw: a refused chunk leaves the generators alone
+            for a in images_uint8:
                 if getattr(a, "ndim", 0) != 3:
                     raise ValueError("every image must be a (h, w, 3) array, got %s" % (getattr(a, "shape", None),))
             records = np.zeros(len(images_uint8), PRE_IMAGE)
             for i, a in enumerate(images_uint8):
                 records[i] = self.draw(int(a.shape[0]), int(a.shape[1]))
-        self.last_records = records
-        return preprocess_aff_batch(images_uint8, la, ha, records, self.S, self.device, self.dtype)
+        if jitter is None and self.color_jitter is not None:
+            jitter = [self.color_jitter.draw() for _ in images_uint8]
+        self.last_records, self.last_jitter = records, jitter
+        return preprocess_aff_batch(images_uint8, la, ha, records, self.S, self.device, self.dtype, jitter)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -444,13 +585,18 @@ class ChunkLoader:
     With `la_dir` and `ha_dir` (the ``<out_crf>_<low_alpha>`` / ``<out_crf>_<high_alpha>`` folders ``infer_cam_list`` writes) it serves
     the affinity stage (voc12/data.py:222-278 VOC12AffDataset; `cls_labels` is not read on this path):
         images, label, names = loader.get_data_from_chunk_aff(chunk)
-        for images, label, names in loader.iterate(chunks, kind="aff"): ..."""
+        for images, label, names in loader.iterate(chunks, kind="aff"): ...
+    and `color_jitter` (a ``ColorJitter``; PSA's is ``ColorJitter(0.3, 0.3, 0.3, 0.1)``) is applied to that stage's images, on the
+    device; the other loaders' recipes have none."""
 
     def __init__(self, img_dir, cls_labels, crop_size, device="cuda", seed=None, workers=8, dtype=torch.float32, ext=".jpg",
-                 with_ori=False, map_dir=None, map_ext=".png", map_fill=0, la_dir=None, ha_dir=None):
+                 with_ori=False, map_dir=None, map_ext=".png", map_fill=0, la_dir=None, ha_dir=None, color_jitter=None):
         self.img_dir, self.S, self.ext, self.with_ori = img_dir, crop_size, ext, with_ori
         self.map_dir, self.map_ext, self.map_fill = map_dir, map_ext, map_fill
         self.la_dir, self.ha_dir, self._aff = la_dir, ha_dir, None
+        if color_jitter is not None and not isinstance(color_jitter, ColorJitter):
+            raise ValueError("color_jitter must be a data.ColorJitter or None, got %s" % type(color_jitter).__name__)
+        self.color_jitter = color_jitter
         self._seg_batchers = {}
         self.device, self.dtype = torch.device(device), dtype
         if isinstance(cls_labels, (str, os.PathLike)):
@@ -537,7 +683,7 @@ class ChunkLoader:
         if self.la_dir is None or self.ha_dir is None:
             raise ValueError("get_data_from_chunk_aff needs ChunkLoader(la_dir=..., ha_dir=...)")
         if self._aff is None:
-            self._aff = AffTrainBatcher(self.S, self.device, None, self.dtype)
+            self._aff = AffTrainBatcher(self.S, self.device, None, self.dtype, self.color_jitter)
             self._aff.pyrandom, self._aff.nprandom = self.batcher.pyrandom, self.batcher.nprandom
         return self._aff
 

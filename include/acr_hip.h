@@ -1113,6 +1113,56 @@ int acr_aff_walk(const float* wt, const float* scores, float* out, int32_t B, in
 int acr_aff_label_batch(const void* scores, const void* table, const int64_t* la_off, const int64_t* ha_off, const int32_t* n_planes,
                         int32_t batch, int32_t SH, int32_t SW, uint8_t* label_u8, void* stream);
 
+/* ---- colour jitter (the affinity stage reads VOC12AffDataset, voc12/data.py:241-278, through PSA's transform list, which begins
+ * with torchvision's ColorJitter(brightness=0.3, contrast=0.3, saturation=0.3, hue=0.1) on the PIL image, before np.asarray,
+ * Normalize and the joint crop) ----
+ * torchvision's ColorJitter on a PIL image is Pillow's ImageEnhance.Brightness, ImageEnhance.Contrast, ImageEnhance.Color and an
+ * HSV round trip: uint8 in, uint8 out, so the result is defined bit for bit.  Images are (h, w, 3) uint8 RGB.  Every operation
+ * below is of the type written, with no contraction and IEEE division.
+ *   gray(r, g, b) = (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16, in integers.
+ *   blend(deg, img, a), a an fp32 value:  t = (float)deg + a * (float)(img - deg) -- an fp32 product, then an fp32 sum; img - deg is
+ *     formed as an int.  For 0 <= a <= 1: out = (uint8)(int)t.  Otherwise: out = 0 if t <= 0, 255 if t >= 255, else (uint8)(int)t.
+ *     a == 0 gives deg, a == 1 gives img.
+ *   brightness(f) = blend(0, img, f) per channel.        saturation(f) = blend(gray(pixel), channel, f).
+ *   contrast(f)   = blend(m, channel, f), m = int(sum of gray / (h w) + 0.5) over the WHOLE image as it is when the contrast
+ *     operation is reached (operations earlier in the order change m).  The sum is an exact integer and
+ *     m = (2 sum + n) / (2 n) in integers, n = h w.
+ *   hue(shift): RGB -> HSV, H = (H + shift) mod 256, HSV -> RGB; shift = trunc(hue_factor * 255) mod 256 with the product in double
+ *     (-0.05 gives 244).  Always the round trip, also at shift 0: it is lossy.
+ *     RGB -> HSV (Pillow's rgb2hsv_row): maxc, minc uint8, V = maxc.  minc == maxc: H = S = 0.  Otherwise cr = (float)(maxc - minc),
+ *       s = cr / (float)maxc, rc, gc, bc = (float)(maxc - x) / cr;  h = bc - gc if r == maxc (an fp32 difference), else
+ *       h = 2.0 + rc - bc if g == maxc, else h = 4.0 + gc - rc (double literals: double arithmetic); h is stored as float;
+ *       h = (float)fmod((double)h / 6.0 + 1.0, 1.0);  H = clip((int)((double)h * 255.0), 0, 255),
+ *       S = clip((int)((double)s * 255.0), 0, 255).
+ *     HSV -> RGB (hsv2rgb_row): S == 0: r = g = b = V.  Otherwise hf = (double)(float)H * 6.0 / 255.0, i = (float)floor(hf),
+ *       f = (float)(hf - (double)i), fs = (float)((double)(float)S / 255.0);  p = round((double)V * (1.0 - (double)fs)),
+ *       q = round((double)V * (1.0 - (double)(fs * f))) with fs * f an fp32 product,
+ *       t = round((double)V * (1.0 - (double)fs * (1.0 - (double)f))); round is C's (half away from zero), clipped to 0..255;
+ *       (r, g, b) by (int)i % 6: 0 (V, t, p), 1 (q, V, p), 2 (p, V, t), 3 (p, q, V), 4 (t, p, V), 5 (V, p, q); H = 255 gives
+ *       i = 6, which is case 0.
+ *   The jitter applies an image's operations in its own order to the whole image.
+ * acr_color_jitter_batch works IN PLACE on packed_u8, the packed uint8 batch acr_preprocess_batch reads: image b is h w 3 bytes
+ * at BYTE offset offsets[b], a multiple of 16 (packed_u8 itself 16-byte aligned); the bytes between images are neither read nor
+ * written.  Device arrays: offsets (batch) int64; hw (batch, 2) int32 = (h, w), h w >= 1; order (batch, 4) int32 operation codes,
+ * executed slot 0 first, ACR_JITTER_NONE = slot unused, no code twice; factors (batch, 3) fp32 indexed by the operation code
+ * (brightness, contrast, saturation; an unused one is not read); hue_shift (batch) int32 in 0..255.  The kernels trust these tables:
+ * the caller validates them.
+ * Two launches for the whole batch, whatever the image sizes: a mean pass (only images whose order names contrast: every pixel
+ * through the operations in front of contrast, then gray, then an exact 64-bit integer sum per image, merged from per-workgroup
+ * partials in ws) and an apply pass (every pixel through its whole sequence, stored once).  ws: acr_color_jitter_ws_bytes(batch)
+ * bytes on the device, 8-byte aligned, contents arbitrary (host only; negative for a batch outside the contract); it may be null
+ * when NO order names contrast, and then the mean pass is not launched.  Contract: 1 <= batch <= 65535; anything else returns
+ * ACR_ERR_INVALID and launches nothing.  No atomics, integer sums: bit-identical run to run.  The entry point allocates nothing and
+ * does not synchronise; it captures into a hipGraph. */
+#define ACR_JITTER_NONE -1
+#define ACR_JITTER_BRIGHTNESS 0
+#define ACR_JITTER_CONTRAST 1
+#define ACR_JITTER_SATURATION 2
+#define ACR_JITTER_HUE 3
+int64_t acr_color_jitter_ws_bytes(int32_t batch);
+int acr_color_jitter_batch(uint8_t* packed_u8, const int64_t* offsets, const int32_t* hw, const int32_t* order, const float* factors,
+                           const int32_t* hue_shift, int32_t batch, void* ws, void* stream);
+
 /* ---- class-centre feature-distance loss (myTool.py:1616-1710 compute_dis_no_batch with compute_cos: the feature-clustering term
  * of the single-stage recipe) ----
  * seg (B, K, h, w) fp32 logits and feat (B, C, h, w) fp32, both contiguous; N = h w, eps = 1e-7.  The reference hard-codes the
