@@ -4,14 +4,30 @@
 // A (sample, group) of the fp32 stem is up to 401 KB (8 channels x 112^2 x 4 B): it does not fit the register file the way
 // the bf16 kernel (groupnorm.hip) keeps it, so these kernels STREAM it twice -- the second pass re-reads what the first
 // just pulled through L2 / Infinity Cache:
-//   forward : pass 1 x -> mean, rstd (shifted sums: sum(x - x0), sum((x - x0)^2) with x0 = the group's first element, fp32,
-//             no catastrophic cancellation); pass 2 x (+ resid) -> y.        2 reads (+1) + 1 write
+//   forward : pass 1 x -> mean, rstd (see "statistics" below); pass 2 x (+ resid) -> y.        2 reads (+1) + 1 write
 //             (stock: row-moments + normalise + clamp kernels = 3 reads + 2 writes, plus the residual add's 2 reads + 1 write)
 //   backward: pass 1 dy, x (+ resid for the ReLU mask) -> per-channel sum(dy), sum(dy * xhat) and the two group sums;
 //             pass 2 dy, x (+ resid) -> dx (+ dresid).                        4 (6) reads + 1 (2) writes
 //             (stock: threshold-backward, internal-gradients, elementwise backward, gamma/beta kernels, the add's backward)
 // Deterministic: every sum is a fixed-order block reduction (no atomics); d(gamma), d(beta) per (sample, channel) are summed
 // over samples in order by a second kernel.  HW must be a multiple of 4 (16-byte vectors inside a channel).
+//
+// Statistics.  The variance is never formed as a difference of two sums that one element can make large.  Every lane sums
+// (x - k) and (x - k)^2 over its own elements about a shift k of its OWN -- the mean of one 16-byte vector of the group -- and
+// turns them into its count n_l, its mean m_l and M2_l = sum (x - m_l)^2 (gnf_lane_moments).  The workgroup then takes two
+// fixed-order sums: mean0 = x0 + sum n_l (m_l - x0) / n, where the group's first element x0 enters linearly only (an outlier
+// there costs |x0 - mean| * 2^-24 in mean0, nothing in the variance), and then sum (M2_l + n_l (m_l - mean0)^2), a sum of
+// non-negative terms, together with the residual sum n_l (m_l - mean0): mean = mean0 + residual / n takes that cost out of the
+// mean again (the backward's sum(dy xhat) feels a mean that is off), var = sum / n - (residual / n)^2.  A common offset of the data cancels in x - k exactly as it did in x - x0; an outlier spoils at most the
+// shift of the one lane that drew it as part of its vector (k off by a quarter of the outlier, in 1 lane of 256 or 1024), and
+// anywhere else it is one large term of a sum of squares.  The register-resident kernel, which runs every group of a
+// training step, keeps the shifted sums about x0 while they are good -- m2 - m1^2 keeps 1 - m1^2 / m2 of its digits, and up to
+// m1^2 = GNF_SHIFT_FAR m2 (x0 within 4.9 sigma of the mean) that costs a factor 25 on the rounding of two sums, 2e-6 of the
+// largest y -- so ordinary groups get the bits they always got; beyond it, it lets its registers go, reads the group again and sums
+// (x - mean)^2: the two-pass.  Its mean stays x0 + m1 (within
+// |x0 - mean| 2^-24 times a small factor of the mean: 1e-5 sigma for an outlier of 100 sigma).  (Until this was written the three forward
+// variants summed (x - x0) and (x - x0)^2 for the whole group and took m2 - m1^2: accurate against a common offset, but with
+// an outlier as the first element both terms are (x0 - mean)^2 and the difference loses its digits.)
 #include "acr_reduce.h"
 
 #define GNF_GROUPS 32
@@ -56,13 +72,21 @@ __device__ __forceinline__ f32x4 gnf_apply_bits(const f32x4& gy, uint32_t bits) 
     return o;
 }
 
+// the shift of a lane: the mean of one vector (exact for a constant group)
+__device__ __forceinline__ float gnf_shift(const f32x4& q) { return 0.25f * ((q[0] + q[1]) + (q[2] + q[3])); }
+// A lane's shifted sums s1 = sum(x - k), s2 = sum((x - k)^2) over nl elements as a = m_l - k and M2_l (nl = 0: both 0)
+__device__ __forceinline__ void gnf_lane_moments(float s1, float s2, float nl, float& a, float& m2) {
+    a = nl > 0.f ? s1 / nl : 0.f;
+    m2 = fmaxf(s2 - s1 * a, 0.f);
+}
+
 template <int NT, int ACT>
 __global__ __launch_bounds__(NT) void gnf_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float* __restrict__ y, float* __restrict__ stats, int C, int HW, int cg, float eps,
                                                      GnfUnits un, uint8_t* __restrict__ mk) {
     constexpr int NW = NT / 64;
-    __shared__ float sh[2 * NW];
+    __shared__ float sh[3 * NW];
     const int g = blockIdx.x % GNF_GROUPS, n = blockIdx.x / GNF_GROUPS;
     const int64_t base = ((int64_t)n * C + (int64_t)g * cg) * HW;
     const int vpc = HW >> 2;
@@ -70,25 +94,38 @@ __global__ __launch_bounds__(NT) void gnf_fwd_kernel(const float* __restrict__ x
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float x0 = x[base];
+    const float k = gnf_shift(reinterpret_cast<const f32x4*>(x + base)[min(tid, cg * vpc - 1)]);      // this lane's shift
     float s1 = 0.f, s2 = 0.f;
+    int cnt = 0;                                            // vectors of this lane
     for (int u = wave; u < un.units; u += NW) {
         const int cl = u / un.S, seg = u - cl * un.S;
         const int v0 = seg * un.segv, v1 = min(vpc, v0 + un.segv);
         const f32x4* xv = reinterpret_cast<const f32x4*>(x + base + (int64_t)cl * HW);
-#define GNF_B1(v, a) { _Pragma("unroll") for (int e = 0; e < 4; ++e) { const float d = a[e] - x0; s1 += d; s2 = fmaf(d, d, s2); } }
+        cnt += max(v1 - v0 - lane + 63, 0) >> 6;
+#define GNF_B1(v, a) { _Pragma("unroll") for (int e = 0; e < 4; ++e) { const float d = a[e] - k; s1 += d; s2 = fmaf(d, d, s2); } }
         GNF_FOR4(xv, v0, v1, lane, GNF_LD1, GNF_B1)
 #undef GNF_B1
     }
-    s1 = acr_wave_sum(s1);
-    s2 = acr_wave_sum(s2);
-    if (lane == 0) { sh[wave] = s1; sh[NW + wave] = s2; }
+    const float nl = (float)(4 * cnt);
+    float am, q;
+    gnf_lane_moments(s1, s2, nl, am, q);
+    const float ta = acr_wave_sum(nl * ((k - x0) + am));
+    if (lane == 0) sh[wave] = ta;
     __syncthreads();
-    float t1 = 0.f, t2 = 0.f;
+    float t1 = 0.f;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) { t1 += sh[w]; t2 += sh[NW + w]; }      // wave order, every thread alike
-    const float m1 = t1 * inv_n, m2 = t2 * inv_n;
-    const float mean = x0 + m1;
-    const float rstd = rsqrtf(fmaxf(m2 - m1 * m1, 0.f) + eps);
+    for (int w = 0; w < NW; ++w) t1 += sh[w];               // wave order, every thread alike
+    const float mean0 = x0 + t1 * inv_n;                    // within |x0 - mean| 2^-24 or so of the mean ...
+    const float dm = (k - mean0) + am;
+    const float tb = acr_wave_sum(fmaf(nl * dm, dm, q)), tc = acr_wave_sum(nl * dm);
+    if (lane == 0) { sh[NW + wave] = tb; sh[2 * NW + wave] = tc; }
+    __syncthreads();
+    float t2 = 0.f, t3 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { t2 += sh[NW + w]; t3 += sh[2 * NW + w]; }
+    const float dmean = t3 * inv_n;                         // ... and the residual sum(x - mean0) / n puts it right
+    const float mean = mean0 + dmean;
+    const float rstd = rsqrtf(fmaxf(t2 * inv_n - dmean * dmean, 0.f) + eps);
     for (int u = wave; u < un.units; u += NW) {
         const int cl = u / un.S, seg = u - cl * un.S;
         const int v0 = seg * un.segv, v1 = min(vpc, v0 + un.segv);
@@ -262,9 +299,12 @@ __global__ __launch_bounds__(NT) void gnf_bwd_kernel(const float* __restrict__ d
 // A (sample, group) of up to NT * 32 floats is read ONCE: every lane keeps its (up to) eight 16-byte vectors of x -- in the
 // backward also of dy and of the residual -- in registers across the reduction, all loads of the group in flight at once (the
 // streamed kernels above re-read the group for their second pass and, on these small groups, spend their time in load latency:
-// 1.1-1.6 TB/s on the 28 x 28 maps).  Same units, same shifted sums; slot i of a lane = (unit wave + NW (i / ch), 64-vector chunk
+// 1.1-1.6 TB/s on the 28 x 28 maps).  Same units; shifted sums about x0 and, where x0 lies far from the data, sum((x - mean)^2) over a second read
+// (the two-pass: see "statistics" in the file header); slot i of a lane = (unit wave + NW (i / ch), 64-vector chunk
 // i % ch of that unit), wave-uniform; per-slot wave sums meet in LDS and are added in (channel, segment, chunk) order.
 #define GNF_RV 8
+// m1^2 / m2 above which the register-resident forward does not trust m2 - m1^2 (the shift x0 is 4.9 sigma or more from the mean)
+#define GNF_SHIFT_FAR 0.96f
 // Slots of a wave, walked in order without divisions (all wave-uniform, scalar unit): slot = (unit wave + NW k, chunk j of it)
 struct GnfWalk {
     int k, j, cl, seg, dq, dr;
@@ -299,13 +339,71 @@ __device__ __forceinline__ uint32_t gnf_off(const GnfWalk& wk, int lane, const G
     return (uint32_t)(wk.cl * HW + 4 * max(v, 0)) * 4u;
 }
 
+// one vector of the register-resident forward's output: normalise, (+ residual, mask byte), ReLU, store
+template <int ACT>
+__device__ __forceinline__ void gnf_fin(const f32x4& a, uint32_t off, float ga, float be, const float* rb, float* yb, uint8_t* mk, int64_t base) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = fmaf(a[e], ga, be);
+    if (ACT == GNF_ADD_RELU) o += GNF_LD2(GNF_AT(const f32x4, rb, off));
+    if (ACT == GNF_ADD_RELU && mk) mk[(base >> 2) + (off >> 4)] = gnf_relu_bits(o);
+    if (ACT != GNF_NONE) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+    }
+    GNF_ST(GNF_AT(f32x4, yb, off), o);
+}
+
+// The rest of gnf_fwd_reg_kernel for a group whose shift x0 lies far from its data (an outlier as the first element; rare): the
+// group is streamed twice more over the same walk in rolled loops -- (x - mean)^2 for the variance (the two-pass; the mean is within
+// 1e-5 sigma even at 100 sigma, its square is nothing against the variance: no correction term), then the output.  Not inlined:
+// as a branch inside the kernel it made the 25-slot instance, at 124 of its 128 registers, spill in the common path.
+template <int ACT>
+__device__ __noinline__ void gnf_fwd_far(const float* xb, const float* rb, const float* gamma, const float* beta, float* yb, float* stats,
+                                         uint8_t* mk, int64_t base, int g, int cg, int HW, int NW, GnfUnits un, int upw, int ch, float inv_n,
+                                         float eps, float mean, float* sh) {
+    const int vpc = HW >> 2, RVmax = upw * ch;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float q2 = 0.f;
+    GnfWalk wk(wave, NW, un);
+#pragma unroll 1
+    for (int i = 0; i < RVmax; ++i, wk.next(un, ch)) {
+        if (!wk.valid(wave, NW, un, upw)) break;
+        bool ok;
+        const uint32_t off = gnf_off(wk, lane, un, vpc, HW, ok);
+        if (ok) {
+            const f32x4 a = GNF_AT(const f32x4, xb, off);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float d = a[e] - mean; q2 = fmaf(d, d, q2); }
+        }
+    }
+    q2 = acr_wave_sum(q2);
+    if (lane == 0) sh[wave] = q2;
+    __syncthreads();
+    float u2 = 0.f;
+    for (int w = 0; w < NW; ++w) u2 += sh[w];               // wave order, every thread alike
+    const float rstd = rsqrtf(u2 * inv_n + eps);
+    wk = GnfWalk(wave, NW, un);
+#pragma unroll 1
+    for (int i = 0; i < RVmax; ++i, wk.next(un, ch)) {
+        if (!wk.valid(wave, NW, un, upw)) break;
+        const int c = g * cg + wk.cl;
+        const float ga = gamma[c] * rstd;
+        bool ok;
+        const uint32_t off = gnf_off(wk, lane, un, vpc, HW, ok);
+        if (ok) gnf_fin<ACT>(GNF_LD2(GNF_AT(const f32x4, xb, off)), off, ga, beta[c] - mean * ga, rb, yb, mk, base);
+    }
+    if (tid == 0) { stats[2 * blockIdx.x] = mean; stats[2 * blockIdx.x + 1] = rstd; }
+}
+
 template <int NT, int ACT, int RV>
 __global__ __launch_bounds__(NT, 4) void gnf_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          float* __restrict__ y, float* __restrict__ stats, int C, int HW, int cg, float eps,
                                                          GnfUnits un, int upw, int ch, uint8_t* __restrict__ mk) {
     constexpr int NW = NT / 64;
-    __shared__ float sh[2 * NW];
+    __shared__ float sh[3 * NW];
     const int g = blockIdx.x % GNF_GROUPS, n = blockIdx.x / GNF_GROUPS;
     const int64_t base = ((int64_t)n * C + (int64_t)g * cg) * HW;
     const int vpc = HW >> 2;
@@ -343,7 +441,15 @@ __global__ __launch_bounds__(NT, 4) void gnf_fwd_reg_kernel(const float* __restr
 #pragma unroll
     for (int w = 0; w < NW; ++w) { t1 += sh[w]; t2 += sh[NW + w]; }
     const float m1 = t1 * inv_n, m2 = t2 * inv_n;
-    const float mean = x0 + m1;
+    const float mean = x0 + m1;                             // within |x0 - mean| 2^-24 times a small factor of the mean
+    // m2 - m1^2 keeps 1 - m1^2 / m2 of its digits.  While the shift lies within GNF_SHIFT_FAR of the data (|x0 - mean| < 4.9 sigma:
+    // at most a factor 25 on the rounding of the two sums) that is the variance.  Beyond it -- rare -- the workgroup lets its
+    // registers go and streams the group twice more (gnf_fwd_far).  Every thread holds the same m1, m2, so the branch and the
+    // barrier behind it are uniform over the workgroup.
+    if (__builtin_amdgcn_readfirstlane((int)(m1 * m1 > GNF_SHIFT_FAR * m2))) {
+        gnf_fwd_far<ACT>(xb, rb, gamma, beta, yb, stats, mk, base, g, cg, HW, NW, un, upw, ch, inv_n, eps, mean, sh + 2 * NW);
+        return;
+    }
     const float rstd = rsqrtf(fmaxf(m2 - m1 * m1, 0.f) + eps);
     wk = GnfWalk(wave, NW, un);
 #pragma unroll
@@ -355,18 +461,7 @@ __global__ __launch_bounds__(NT, 4) void gnf_fwd_reg_kernel(const float* __restr
         const float be = beta[c] - mean * ga;
         bool ok;
         const uint32_t off = gnf_off(wk, lane, un, vpc, HW, ok);
-        if ((okm >> i) & 1) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = fmaf(xr[i][e], ga, be);
-            if (ACT == GNF_ADD_RELU) o += GNF_LD2(GNF_AT(const f32x4, rb, off));
-            if (ACT == GNF_ADD_RELU && mk) mk[(base >> 2) + (off >> 4)] = gnf_relu_bits(o);
-            if (ACT != GNF_NONE) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
-            }
-            GNF_ST(GNF_AT(f32x4, yb, off), o);
-        }
+        if ((okm >> i) & 1) gnf_fin<ACT>(xr[i], off, ga, be, rb, yb, mk, base);
     }
     if (tid == 0) { stats[2 * blockIdx.x] = mean; stats[2 * blockIdx.x + 1] = rstd; }
 }
@@ -497,8 +592,9 @@ static GnfUnits gnf_units(int cg, int HW, int nwaves) {
 }
 
 // ---- small launches (CAM generation: two views of one image = 64 (sample, group) pairs on 256 CUs) ---------------------------------
-// A (sample, group) is cut into P parts: gnf_part_kernel reduces each part to shifted sums (same shift x0 = the group's first
-// element), gnf_apply_kernel combines the P partials in part order (deterministic) and normalises its own part.  Two launches
+// A (sample, group) is cut into P parts: gnf_part_kernel reduces each part to its mean and M2 = sum (x - mean)^2 (lane moments
+// about per-lane shifts, as in gnf_fwd_kernel; the part's first element takes x0's place), gnf_apply_kernel merges the P
+// (count, mean, M2) in part order (deterministic; about part 0's mean) and normalises its own part.  Two launches
 // of N * 32 * P workgroups instead of one of N * 32: 27 -> ~10 us for the 1024-channel maps of a 384^2 image.
 __global__ __launch_bounds__(256) void gnf_part_kernel(const float* __restrict__ x, float* __restrict__ parts, int C, int HW, int cg, int P, int vper) {
     __shared__ float sh[4];
@@ -508,16 +604,25 @@ __global__ __launch_bounds__(256) void gnf_part_kernel(const float* __restrict__
     const int nvec = (cg * HW) >> 2;
     const int v0 = part * vper, v1 = min(nvec, v0 + vper);
     const f32x4* xv = reinterpret_cast<const f32x4*>(x + base);
-    const float x0 = x[base];
+    const float p0 = x[base + 4 * (int64_t)v0];             // the part's first element: enters the part's mean linearly only
+    const float k = gnf_shift(xv[min(v0 + (int)threadIdx.x, v1 - 1)]);
     float s1 = 0.f, s2 = 0.f;
+    int cnt = 0;
     for (int v = v0 + threadIdx.x; v < v1; v += 256) {
         const f32x4 a = xv[v];
+        ++cnt;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = a[e] - x0; s1 += d; s2 = fmaf(d, d, s2); }
+        for (int e = 0; e < 4; ++e) { const float d = a[e] - k; s1 += d; s2 = fmaf(d, d, s2); }
     }
-    s1 = acr_block_sum<256>(s1, sh);
-    s2 = acr_block_sum<256>(s2, sh);
-    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = s1; parts[2 * blockIdx.x + 1] = s2; }
+    const float nl = (float)(4 * cnt);
+    float am, q;
+    gnf_lane_moments(s1, s2, nl, am, q);
+    const float np = (float)(4 * (v1 - v0));
+    const float mean0 = p0 + acr_block_sum<256>(nl * ((k - p0) + am), sh) / np;
+    const float dm = (k - mean0) + am;
+    const float m20 = acr_block_sum<256>(fmaf(nl * dm, dm, q), sh);
+    const float dmean = acr_block_sum<256>(nl * dm, sh) / np;           // the residual puts the part's mean right
+    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = mean0 + dmean; parts[2 * blockIdx.x + 1] = fmaxf(m20 - np * dmean * dmean, 0.f); }
 }
 template <int ACT>
 __global__ __launch_bounds__(256) void gnf_apply_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
@@ -528,12 +633,16 @@ __global__ __launch_bounds__(256) void gnf_apply_kernel(const float* __restrict_
     const int64_t base = ((int64_t)n * C + (int64_t)g * cg) * HW;
     const int nvec = (cg * HW) >> 2, vpc = HW >> 2;
     const float inv_n = 1.f / (float)(cg * HW);
+    const float* pp = parts + 2 * (int64_t)ng * P;          // per part: mean, M2; its count follows from its index
+    const float m0 = pp[0];
     float s1 = 0.f, s2 = 0.f;
-    for (int p = 0; p < P; ++p) { s1 += parts[2 * (ng * P + p)]; s2 += parts[2 * (ng * P + p) + 1]; }      // part order, every thread alike
-    const float x0 = x[base];
-    const float m1 = s1 * inv_n, m2 = s2 * inv_n;
-    const float mean = x0 + m1;
-    const float rstd = rsqrtf(fmaxf(m2 - m1 * m1, 0.f) + eps);
+    for (int p = 0; p < P; ++p) s1 += (float)(4 * (min(nvec, (p + 1) * vper) - p * vper)) * (pp[2 * p] - m0);      // part order, every thread alike
+    const float mean = m0 + s1 * inv_n;
+    for (int p = 0; p < P; ++p) {
+        const float d = pp[2 * p] - mean;
+        s2 += fmaf((float)(4 * (min(nvec, (p + 1) * vper) - p * vper)) * d, d, pp[2 * p + 1]);
+    }
+    const float rstd = rsqrtf(s2 * inv_n + eps);
     const f32x4* xv = reinterpret_cast<const f32x4*>(x + base);
     const f32x4* rv = reinterpret_cast<const f32x4*>(res + (ACT == GNF_ADD_RELU ? base : 0));
     f32x4* yv = reinterpret_cast<f32x4*>(y + base);

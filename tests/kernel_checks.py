@@ -5,7 +5,7 @@ distributions) and the launch census (tests/launch_census.py: the shapes the mod
 hand what went in and what came out to the ``verify_*`` function of that entry.  It rebuilds the computation in float64 torch
 math, takes the same seeds through the reference's backward and compares output and gradients through ``Cmp`` -- which also
 proves every comparison can fail.  A tolerance is written once, in ``TOL`` below; a caller that needs another value says so at its
-call site.
+call site (``tols`` of the norm checks: name of a compared quantity -> keywords of ``Cmp.check`` that replace its ``TOL`` entry).
 
 Conventions: ``got`` is the list of the kernel's gradients, one per input that requires grad, in the order the function names its
 inputs (``grads_of(x, w, ...)`` for a test that called ``backward()``).  A seed of ``None`` means that output took no part in the
@@ -33,6 +33,7 @@ class Cmp:
         self.compared = 0
         self.where = ""
         self.grad_mode = True
+        self.log = []                                        # (label, max |err|, max |reference|) of every value comparison
 
     def fail(self, msg):
         self.failures.append("%s: %s" % (self.where, msg))
@@ -62,6 +63,7 @@ class Cmp:
         exact = tol == 0 and rtol == 0 and atol == 0
         bound = None if exact else atol + tol * scale + rtol * want.abs()
         r = self._ratio(got, want, bound)
+        self.log.append((label, float((got - want).abs().max()), scale))
         if not r <= 1.0:
             err = float((got - want).abs().max()) if torch.isfinite(got).all() else float("nan")
             self.fail("%s: max |err| %.3e, %.2fx the tolerance (tol %g, rtol %g, atol %.3e, max|ref| %.3e)"
@@ -214,7 +216,7 @@ def verify_maxpool(cmp, x, pt, pl, ph, pw, y, dy, got):
 # ------------------------------------------------------------------------------------------------
 # norms, weight standardisation, token assembly
 # ------------------------------------------------------------------------------------------------
-def verify_groupnorm(cmp, x, w, b, r, act, y, dy, got, eps=1e-5):
+def verify_groupnorm(cmp, x, w, b, r, act, y, dy, got, eps=1e-5, tols=None):
     """GroupNorm(32) [+ residual] [+ ReLU].  The value is compared with the float64 ReLU; the backward goes through the kernel's own
     mask (elements within rounding of 0 may fall on either side, and the gradient follows the side the kernel took).  Without any
     gradient (CAM generation's split small launches) the forward-only bound applies.  Returns the reference output."""
@@ -225,8 +227,8 @@ def verify_groupnorm(cmp, x, w, b, r, act, y, dy, got, eps=1e-5):
     ref = pre if act == "none" else F.relu(pre)
     routed = pre if act == "none" else pre * (y.detach() > 0).double()
     want = _grads([routed], [dy], _leaves(xr, wr, br, rr))
-    t = TOL["groupnorm"][x.dtype]
-    if _leaves(x, w, b, r):
+    t = dict(TOL["groupnorm"][x.dtype], **(tols or {}))
+    if _leaves(x, w, b, r) or (tols and "y" in tols):
         cmp.check("y", y, ref, **t["y"])
     else:
         cmp.check("y", y, ref, atol=TOL["groupnorm_forward_only"] * max(1.0, float(ref.abs().max())))
@@ -234,18 +236,23 @@ def verify_groupnorm(cmp, x, w, b, r, act, y, dy, got, eps=1e-5):
     return ref.detach()
 
 
-def verify_weight_std(cmp, ws, outs, gs, got, eps=1e-5):
-    """(w - mean) / (std + eps) per output channel (std_conv.py:56-59), per weight of the launch."""
+def verify_weight_std(cmp, ws, outs, gs, got, eps=1e-5, tols=None, keep=None):
+    """(w - mean) / (std + eps) per output channel (std_conv.py:56-59), per weight of the launch.  ``keep``: per weight, the
+    output channels that are compared (all by default; their gradients are those of the kept channels' outputs alone)."""
     wr = [_double_leaf(w) for w in ws]
+    keep = keep if keep is not None else [slice(None)] * len(ws)
     refs = []
     for w in wr:
         std, mean = torch.std_mean(w, dim=[1, 2, 3], keepdim=True, unbiased=False)
         refs.append((w - mean) / (std + eps))
-    want = _grads(refs, gs, _leaves(*wr))
-    t = TOL["weight_std"][ws[0].dtype]
+    want = _grads([r[k] for r, k in zip(refs, keep)], [g[k] if g is not None else None for g, k in zip(gs, keep)], _leaves(*wr))
+    t, tols = TOL["weight_std"][ws[0].dtype], tols or {}
     for i, (o, r) in enumerate(zip(outs, refs)):
-        cmp.check("w_hat[%d]" % i, o, r, **t["w_hat"])
-    _named(cmp, ws, ["dw[%d]" % i for i in range(len(ws))], [t["dw"]] * len(ws), got, want)
+        cmp.check("w_hat[%d]" % i, o[keep[i]], r[keep[i]], **tols.get("w_hat[%d]" % i, t["w_hat"]))
+    names = ["dw[%d]" % i for i in range(len(ws))]
+    kept = iter(keep[i] for i, w in enumerate(ws) if w.requires_grad)
+    sel = [(a[k] if a is not None else None, b[k] if b is not None else None) for (a, b), k in zip(zip(got, want), kept)] if got else []
+    _named(cmp, ws, names, [tols.get(n, t["dw"]) for n in names], [a for a, _ in sel], [b for _, b in sel])
 
 
 def verify_tokens(cmp, y, bias, prefix, pos, tok, dt, got):
@@ -265,7 +272,7 @@ def verify_tokens(cmp, y, bias, prefix, pos, tok, dt, got):
     _named(cmp, [y, bias, prefix, pos], ["dy", "dbias", "dprefix", "dpos"], [EXACT, s, s, s], got, want)
 
 
-def verify_layernorm(cmp, x, weight, bias, eps, y, skip, dy, ds, got):
+def verify_layernorm(cmp, x, weight, bias, eps, y, skip, dy, ds, got, tols=None):
     """LayerNorm over the last dimension (``skip``: the residual stream's view of x, its seed ``ds`` is the fused skip gradient;
     None for the plain form)."""
     xr, wr, br = _double_leaf(x), _double_leaf(weight), _double_leaf(bias)
@@ -279,11 +286,12 @@ def verify_layernorm(cmp, x, weight, bias, eps, y, skip, dy, ds, got):
             if by.get(id(p)) is not None:
                 room = (t["dparam_of_max"] - tp[i]["tol"]) * float(by[id(p)].abs().max())
                 tp[i] = dict(tp[i], atol=min(tp[i]["atol"], room))
-    cmp.check("y", y, ref, **t["y"])
-    _named(cmp, [x, weight, bias], ["dx", "dgamma", "dbeta"], [t["dx"]] + tp, got, want)
+    tols = tols or {}
+    cmp.check("y", y, ref, **tols.get("y", t["y"]))
+    _named(cmp, [x, weight, bias], ["dx", "dgamma", "dbeta"], [tols.get("dx", t["dx"]), tols.get("dgamma", tp[0]), tols.get("dbeta", tp[1])], got, want)
 
 
-def verify_ln_consumer(cmp, x, ln, kind, params, out, dz, skip, ds, got, math=1):
+def verify_ln_consumer(cmp, x, ln, kind, params, out, dz, skip, ds, got, math=1, tols=None):
     """LayerNorm leaving as its consumer's operand image, checked as the composite it is: ``kind`` "linear": Linear(LN(x)) with
     ``params`` (W, b); "mlp": x + fc2(GELU(fc1(LN(x)))) with (W1, b1, W2, b2).  ``ds`` seeds the skip output where the caller used
     it on its own.  ``got``: gradients of x, gamma, beta, then the consumer's parameters."""
@@ -296,9 +304,11 @@ def verify_ln_consumer(cmp, x, ln, kind, params, out, dz, skip, ds, got, math=1)
         ref, names = xr + F.linear(F.gelu(F.linear(hr, pr[0], pr[1])), pr[2], pr[3]), ["dW1", "db1", "dW2", "db2"]
     want = _grads([ref, xr if ds is not None else None], [dz, ds], _leaves(xr, wr, br, *pr))
     tol = TOL["mlp"][2] if (kind == "mlp" and math == 2) else TOL["ln_image"][kind]
-    cmp.check("y", out, ref, **tol)
+    tols = tols or {}
+    cmp.check("y", out, ref, **tols.get("y", tol))
     inputs = [x, ln.weight, ln.bias] + list(params)
-    _named(cmp, inputs, ["dx", "dgamma", "dbeta"] + names, [tol] * len(inputs), got, want)
+    names = ["dx", "dgamma", "dbeta"] + names
+    _named(cmp, inputs, names, [tols.get(n, tol) for n in names], got, want)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -115,21 +115,29 @@ def same_bits(a, b):
 # ------------------------------------------------------------------------------------------------
 # BatchNorm2d, fused
 # ------------------------------------------------------------------------------------------------
-def bn_inputs(shape, nres, seed):
+def bn_inputs(shape, nres, seed, first=0.0):
+    """``first`` > 0: every channel's first value, the shift of the kernel's sums, lies at least that many standard deviations
+    above the mean of the channel's other values"""
     n, c, hw = shape
     rng = np.random.default_rng(1000 * seed + 31 * n + 7 * c + hw + nres)
     full = (n, c, hw, 1)
-    return dict(x=bf16_values(rng, full, 0.5), dy=bf16_values(rng, full), res=[bf16_values(rng, full) for _ in range(nres)],
+    x = bf16_values(rng, full, 0.5)
+    if first:
+        rest = x.astype(np.float64).transpose(1, 0, 2, 3).reshape(c, -1)[:, 1:]
+        v = (rest.mean(1) + first * rest.std(1)).astype(np.float32)
+        x[0, :, 0, 0] = K.bf16_to_f32(K.bf16_rne(v * np.float32(1 + 2.0 ** -7)))       # rounding to bf16 moves a value by at most 2^-8 of it
+        assert ((x[0, :, 0, 0] - rest.mean(1)) / rest.std(1)).min() >= first
+    return dict(x=x, dy=bf16_values(rng, full), res=[bf16_values(rng, full) for _ in range(nres)],
                 gamma=bf16_values(rng, c, 1.0, 0.1), beta=bf16_values(rng, c, 0.0, 0.1),
                 rm=(0.2 * rng.standard_normal(c)).astype(np.float32), rv=(0.5 + rng.random(c)).astype(np.float32))
 
 
 @functools.lru_cache(maxsize=None)
-def bn_case(shape, relu, nres, training):
+def bn_case(shape, relu, nres, training, first=0.0):
     """the inputs at the first seed whose restatement keeps the window share of y and dx under the cap, and the bounds of the
     double outputs from those inputs; treat as read-only"""
     for seed in range(64):
-        c = bn_inputs(shape, nres, seed)
+        c = bn_inputs(shape, nres, seed, first)
         f = R.bn_fwd(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], training, MOMENTUM, EPS, relu, *(c["res"] + [None, None])[:2])
         dx, dgamma, dbeta, g = R.bn_bwd(c["x"], c["gamma"], f["mean"], f["invstd"], c["dy"], training, mask=(f["pre"] > 0) if relu else None)
         shares = (K.window_share(f["y"]), K.window_share(dx))
@@ -190,6 +198,19 @@ def test_bn2d_bf16_is_the_rounded_fp32_entry_point(shape, relu, nres, training):
     check_outputs("bn %s" % (shape,), got, ref, dict(stats=b["stats"]))
     if not training:                                         # nothing is updated in eval mode
         assert np.array_equal(got["running_mean"], case["rm"]) and np.array_equal(got["running_var"], case["rv"])
+
+
+@pytest.mark.parametrize("relu,nres", [(False, 0), (True, 2)])
+@pytest.mark.parametrize("shape", [(2, 5, 8), (3, 2, 467)], ids=lambda s: "x".join(map(str, s)))
+def test_bn2d_bf16_first_value_outlier(shape, relu, nres):
+    """Every channel's first value -- the shift of the kernel's (double) sums -- at 100 standard deviations, by the rule above."""
+    case = bn_case(shape, relu, nres, True, 100.0)
+    print("\nbn %s relu%d res%d, first value at 100 sigma: seed %d, window share of y %.1e, dx %.1e (restatement)"
+          % (shape, relu, nres, case["seed"], case["shares"][0], case["shares"][1]))
+    ref = run_bn("f32", case, shape, relu, True)
+    got = run_bn("bf16", case, shape, relu, True)
+    same_bits(got, run_bn("bf16", case, shape, relu, True))
+    check_outputs("bn %s first value at 100 sigma" % (shape,), got, ref, dict(stats=case["bounds"]["stats"]))
 
 
 def test_bn2d_bf16_refuses_one_value_per_channel():

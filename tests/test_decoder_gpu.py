@@ -31,9 +31,12 @@ ULPS = 4 * 2.0 ** -23
 MARGIN = 8.0
 MOMENTUM, EPS = 0.1, 1e-5
 # tag -> (shape, mean of x): odd planes; the smallest legal channel; general odd sizes; more channels than workgroups in a grid
-# row, tiny planes; several slabs (partial sums) per channel; the aligned wide path; cancellation in the variance
+# row, tiny planes; several slabs (partial sums) per channel; the aligned wide path; cancellation in the variance; every channel's
+# first value -- the shift of the kernel's sums -- an outlier at FIRST_SIGMAS standard deviations (the sums are double)
+FIRST_SIGMAS = 100.0
 BN_SHAPES = {"odd": ((2, 16, 5, 7), 0.0), "min": ((1, 1, 1, 2), 0.0), "gen": ((3, 5, 9, 4), 0.0), "chan": ((2, 300, 1, 3), 0.0),
-             "slabs": ((2, 16, 70, 33), 0.0), "wide": ((4, 64, 16, 16), 0.0), "mean1000": ((2, 16, 5, 7), 1000.0)}
+             "slabs": ((2, 16, 70, 33), 0.0), "wide": ((4, 64, 16, 16), 0.0), "mean1000": ((2, 16, 5, 7), 1000.0),
+             "first100": ((2, 16, 5, 7), 0.0)}
 # seeds for which the ReLU inputs are decisive (found on the CPU with bn_case; asserted in every test that fuses a ReLU)
 BN_SEEDS = {("mean1000", True, 1, True): 1, ("wide", True, 2, True): 1, ("slabs", True, 2, False): 1}
 UP_SHAPES = [(1, 1, 1, 1), (2, 3, 5, 7), (2, 5, 1, 9), (2, 5, 9, 1), (1, 16, 16, 20), (1, 2, 33, 70)]
@@ -67,6 +70,9 @@ def bn_case(tag, relu, nres, training=True, seed=None):
     rng = np.random.default_rng(100 * seed + len(tag) + 7 * nres)
     c = shape[1]
     x = (mean + rng.standard_normal(shape)).astype(np.float32)
+    if tag == "first100":
+        rest = x.astype(np.float64).transpose(1, 0, 2, 3).reshape(c, -1)[:, 1:]      # all but x[0, c, 0, 0]
+        x[0, :, 0, 0] = rest.mean(1) + (FIRST_SIGMAS + 0.01) * rest.std(1)
     dy = rng.standard_normal(shape).astype(np.float32)
     res = [rng.standard_normal(shape).astype(np.float32) for _ in range(nres)]
     gamma, beta = (1 + 0.1 * rng.standard_normal(c)).astype(np.float32), (0.1 * rng.standard_normal(c)).astype(np.float32)
@@ -139,6 +145,9 @@ def test_batchnorm_forward_and_backward(tag, relu, nres):
     case, dev = check_bn(tag, relu, nres)
     if tag == "mean1000":                                    # a plain fp32 E[x^2] - E[x]^2 would lose the variance: 1e6 * 2^-24 ~ 0.06
         assert abs(float(case["x"].mean()) - 1000) < 1 and 0.5 < float(case["x"].var()) < 2
+    if tag == "first100":                                    # fp32 sums about x[0, c, 0, 0] would lose it as well
+        rest = case["x"].astype(np.float64).reshape(2, 16, -1).transpose(1, 0, 2).reshape(16, -1)[:, 1:]
+        assert ((case["x"][0, :, 0, 0] - rest.mean(1)) / rest.std(1)).min() >= FIRST_SIGMAS
 
 
 @pytest.mark.parametrize("relu,nres", [(False, 0), (True, 2)])

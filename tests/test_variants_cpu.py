@@ -37,6 +37,8 @@ def test_restated_predicate_lines_stand_in_the_source(rule):
 
 def test_every_rule_function_has_its_source_lines():
     fns = {c[1].__name__ for c in G.claims()} | {"gemm_tail_plan", "c3_fwd_ksplit", "conv1x1_ksplit"}
+    # the fp32 GroupNorm's plans: their cases are the shapes of tests/test_norm_conditions_gpu.py
+    fns |= {"gnf_units", "gnf_reg_plan", "gnf_fwd_parts", "gnf_fwd_variant", "gnf_bwd_variant"}
     assert fns == set(VR.SOURCE)
     for name in fns:
         assert callable(getattr(VR, name))

@@ -196,6 +196,79 @@ def sal_pseudo_variant(hw, cams, saliency, saliency_out, label):
 
 
 # ------------------------------------------------------------------------------------------------
+# acr_groupnorm_fwd_f32 / acr_groupnorm_bwd_f32: which kernel family a (sample, group) of cg channels x HW pixels takes
+# ------------------------------------------------------------------------------------------------
+GNF_GROUPS, GNF_MAXU, GNF_RV, GNF_RV_FWD_MAX, GNF_RV_BWD_MAX = 32, 64, 8, 25, 13
+GNF_SHIFT_FAR = 0.96          # m1^2 / m2 above which the register-resident forward sums the group again about its mean
+
+
+def gnf_units(cg, HW, nwaves):
+    """(S, segv, units) of gnf_units"""
+    vpc = HW >> 2
+    S = 1 if cg >= nwaves else _cdiv(nwaves, cg)
+    segv = _cdiv(_cdiv(vpc, S), 64) * 64
+    S = _cdiv(vpc, segv)
+    return S, segv, cg * S
+
+
+def gnf_reg_plan_nt(cg, HW, nt):
+    """(ok, nt, slots) of gnf_reg_plan_nt"""
+    nw = nt // 64
+    S, segv, units = gnf_units(cg, HW, nw)
+    ch = _cdiv(segv, 64)
+    upw = _cdiv(units, nw)
+    return units <= GNF_MAXU, nt, upw * ch
+
+
+def gnf_reg_plan(cg, HW, max_slots, backward):
+    """(ok, nt, slots) of gnf_reg_plan"""
+    if not backward:
+        ok, nt, slots = gnf_reg_plan_nt(cg, HW, 1024 if cg * (HW >> 2) > 2048 else 256)
+        return ok and slots <= max_slots and (slots <= GNF_RV or nt == 1024), nt, slots
+    for nt in (256, 512, 1024):
+        ok, nt, slots = gnf_reg_plan_nt(cg, HW, nt)
+        if ok and slots <= max_slots:
+            return True, nt, slots
+    return False, 1024, slots
+
+
+def gnf_fwd_parts(N, C, HW):
+    """parts a (sample, group) is cut into by the small-launch forward (1: one workgroup per group)"""
+    groups, nvec = N * GNF_GROUPS, (C // GNF_GROUPS) * HW // 4
+    if groups > 128 or nvec < 4096:
+        return 1
+    P = min(512 // groups, 8)
+    while P > 1 and nvec // P < 1024:
+        P -= 1
+    return P
+
+
+def _gnf_reg_template(slots):
+    return GNF_RV if slots <= GNF_RV else GNF_RV_BWD_MAX if slots <= GNF_RV_BWD_MAX else GNF_RV_FWD_MAX
+
+
+def gnf_fwd_variant(N, C, HW, ws):
+    """("parts", P), ("reg", threads, slot template) or ("streamed", threads); ``ws``: the small-launch workspace was passed"""
+    cg = C // GNF_GROUPS
+    P = gnf_fwd_parts(N, C, HW) if ws else 1
+    if P > 1:
+        return "parts", P
+    ok, nt, slots = gnf_reg_plan(cg, HW, GNF_RV_FWD_MAX, False)
+    if ok:
+        return "reg", nt, GNF_RV if nt == 256 else _gnf_reg_template(slots)
+    return "streamed", 1024 if cg * HW >= 32768 else 256
+
+
+def gnf_bwd_variant(N, C, HW):
+    """("reg", threads, slot template) or ("streamed", threads)"""
+    cg = C // GNF_GROUPS
+    ok, nt, slots = gnf_reg_plan(cg, HW, GNF_RV_BWD_MAX, True)
+    if ok:
+        return "reg", nt, GNF_RV if slots <= GNF_RV else GNF_RV_BWD_MAX
+    return "streamed", 1024 if HW >= 4096 else 256
+
+
+# ------------------------------------------------------------------------------------------------
 # the source lines each restatement stands for: rule -> [(file under acr_wsss_amd/csrc, line)]
 # ------------------------------------------------------------------------------------------------
 SOURCE = {
@@ -305,5 +378,51 @@ SOURCE = {
     "sal_pseudo_variant": [
         ("pseudo_sal.hip", "const bool vec = hw % 4 == 0 && ((uintptr_t)cams & 15) == 0 && "
                            "(((uintptr_t)saliency | (uintptr_t)saliency_out | (uintptr_t)label) & 3) == 0;"),
+    ],
+    "gnf_units": [
+        ("groupnorm_f32.hip", "u.S = cg >= nwaves ? 1 : (nwaves + cg - 1) / cg;"),
+        ("groupnorm_f32.hip", "u.segv = ((vpc + u.S - 1) / u.S + 63) / 64 * 64;"),
+        ("groupnorm_f32.hip", "u.S = (vpc + u.segv - 1) / u.segv;"),
+        ("groupnorm_f32.hip", "u.units = cg * u.S;"),
+    ],
+    "gnf_reg_plan": [
+        ("groupnorm_f32.hip", "#define GNF_RV 8"),
+        ("groupnorm_f32.hip", "#define GNF_MAXU 64 // units per (sample, group): max(channels per group, waves) <= 64"),
+        ("groupnorm_f32.hip", "p.ch = (p.un.segv + 63) / 64;"),
+        ("groupnorm_f32.hip", "p.upw = (p.un.units + nw - 1) / nw;"),
+        ("groupnorm_f32.hip", "p.slots = p.upw * p.ch;"),
+        ("groupnorm_f32.hip", "p.ok = p.un.units <= GNF_MAXU;"),
+        ("groupnorm_f32.hip", "p = gnf_reg_plan_nt(cg, HW, cg * (HW >> 2) > 2048 ? 1024 : 256);"),
+        ("groupnorm_f32.hip", "p.ok = p.ok && p.slots <= max_slots && (p.slots <= GNF_RV || p.nt == 1024);"),
+        ("groupnorm_f32.hip", "for (int nt = 256; nt <= 1024; nt *= 2) {"),
+        ("groupnorm_f32.hip", "if (p.ok && p.slots <= max_slots) return p;"),
+    ],
+    "gnf_fwd_parts": [
+        ("groupnorm_f32.hip", "#define GNF_GROUPS 32"),
+        ("groupnorm_f32.hip", "const int groups = N * GNF_GROUPS, nvec = (C / GNF_GROUPS) * HW / 4;"),
+        ("groupnorm_f32.hip", "if (groups > 128 || nvec < 4096) return 1;"),
+        ("groupnorm_f32.hip", "int P = 512 / groups;"),
+        ("groupnorm_f32.hip", "if (P > 8) P = 8;"),
+        ("groupnorm_f32.hip", "while (P > 1 && nvec / P < 1024) --P; // at least 4 vectors per thread and part"),
+        ("groupnorm_f32.hip", "return P > 1 ? (size_t)N * GNF_GROUPS * P * 2 : 0;"),
+    ],
+    "gnf_fwd_variant": [
+        ("groupnorm_f32.hip", "#define GNF_SHIFT_FAR 0.96f"),
+        ("groupnorm_f32.hip", "if (__builtin_amdgcn_readfirstlane((int)(m1 * m1 > GNF_SHIFT_FAR * m2))) {"),
+        ("groupnorm_f32.hip", "#define GNF_RV_FWD_MAX 25"), ("groupnorm_f32.hip", "#define GNF_RV_BWD_MAX 13"),
+        ("groupnorm_f32.hip", "const int P = ws ? gnf_fwd_parts(N, C, HW) : 1;"),
+        ("groupnorm_f32.hip", "if (P > 1) { // small launch: every (sample, group) cut into P parts, two launches"),
+        ("groupnorm_f32.hip", "const int nvec = cg * HW / 4, vper = (nvec + P - 1) / P;"),
+        ("groupnorm_f32.hip", "const GnfRegPlan rp = gnf_reg_plan(cg, HW, GNF_RV_FWD_MAX, false);"),
+        ("groupnorm_f32.hip", "const bool big = (int64_t)cg * HW >= 32768; // >= 8 vectors per thread at 1024 threads"),
+        ("groupnorm_f32.hip", "if ((P).nt == 256) GNF_LAUNCH_REG(KERNEL, 256, GNF_RV, P, __VA_ARGS__) \\"),
+        ("groupnorm_f32.hip", "else if ((P).slots <= GNF_RV) GNF_LAUNCH_REG(KERNEL, 1024, GNF_RV, P, __VA_ARGS__) \\"),
+        ("groupnorm_f32.hip", "else if ((P).slots <= GNF_RV_BWD_MAX) GNF_LAUNCH_REG(KERNEL, 1024, GNF_RV_BWD_MAX, P, __VA_ARGS__) \\"),
+    ],
+    "gnf_bwd_variant": [
+        ("groupnorm_f32.hip", "const GnfRegPlan rp = gnf_reg_plan(cg, HW, GNF_RV_BWD_MAX, true);"),
+        ("groupnorm_f32.hip", "const bool big = (int64_t)HW >= 4096; // per-channel loops: 1024 threads only when a channel feeds them"),
+        ("groupnorm_f32.hip", "if ((P).slots <= GNF_RV) { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV, P, __VA_ARGS__) } \\"),
+        ("groupnorm_f32.hip", "else { GNF_LAUNCH_REG_NT(KERNEL, GNF_RV_BWD_MAX, P, __VA_ARGS__) }"),
     ],
 }
