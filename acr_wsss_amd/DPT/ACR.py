@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import _derived, ops
 from ..backbone import VisionTransformer
 
 # backbone name -> VisionTransformer kwargs, DPT scratch in_shape, the four hooks   (DPT/vit.py:548-632, DPT/blocks.py:26-83,
@@ -182,16 +182,10 @@ class ACR(DPT):
 
     def invalidate_caches(self):
         """After weights were written through ``.data`` (an EMA swap, ``p.data.copy_()``): drop everything derived from the
-        weights that is keyed on (version, address) and therefore cannot see such a write -- the cached split-product weight
-        images, the fp32 W^T copies and the captured inference prefixes."""
-        from .. import ops
-        from ..train import refresh_weight_transposes
-        refresh_weight_transposes(self)                   # also drops the weight images
-        for m in self.modules():
-            m.__dict__.pop("_prefix_graphs", None)
-            m.__dict__.pop("_pass_graphs", None)
-            if "_frozen" in m.__dict__:                    # ResNetV2's frozen standardised conv weights
-                m._frozen = None
+        weights, since its stamps cannot see such a write (_derived.py): weight images, W^T copies, the stem's frozen weights, the
+        captured graphs.  All of it is rebuilt on demand (the W^T copies by the next ``train.refresh_weight_transposes``)."""
+        _derived.invalidate(self)
+        _derived.drop_graphs(self.modules())
         return self
 
     def forward_mirror(self, x1, x2):

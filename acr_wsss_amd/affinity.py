@@ -276,7 +276,7 @@ def aff_train_step(model, head, optimizer, images, label_map, radius=5):
     ``segtrain.seg_train_step``.  images (B, 3, S, S') float32 on the GPU (multiples of 32), label_map (B, S, S') uint8 at image
     size (stride 8) or at the head's grid (stride 1).  The label of ``ChunkLoader.get_data_from_chunk_aff`` is a stride-1 grid.
     Returns (loss, bg, fg, neg)."""
-    from . import decoder, ops
+    from . import decoder
     from .train import refresh_weight_transposes
     optimizer.zero_grad(set_to_none=True)
     feat = head(decoder.layers_rn(model, images))
@@ -288,8 +288,7 @@ def aff_train_step(model, head, optimizer, images, label_map, radius=5):
     loss, bg, fg, neg = aff_loss(feat, codes, counts, radius)
     loss.backward()
     optimizer.step()
-    refresh_weight_transposes(model)
-    ops.invalidate_weight_images(head)
+    refresh_weight_transposes(model, head)
     return loss, bg, fg, neg
 
 

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _derived, ops
 
 
 def set_math(module, math):
@@ -225,17 +225,17 @@ class ResNetV2(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
-    _frozen = None                # (key, w_hats, transposed) of the last forward with frozen weights
-    frozen_generation = 0         # bumped whenever that cache is rebuilt (PrefixGraph holds pointers into it)
+    frozen_generation = 0         # bumped whenever the frozen cache is rebuilt (captured graphs hold pointers into it)
 
     def _standardised(self, convs, x):
         """The standardised weights of all convolutions: one launch per forward while training; with frozen weights
-        (CAM generation: requires_grad off) they are kept until a weight changes (tensor version or storage)."""
+        (CAM generation: requires_grad off) they are kept as form "frozen" (_derived.py) until the stamp of a weight moves."""
         frozen = not any(c.weight.requires_grad for c in convs)
         if frozen:
-            key = (x.dtype,) + tuple((c.weight.data_ptr(), c.weight._version, c.acr_math) for c in convs)
-            if self._frozen is not None and self._frozen[0] == key:
-                return self._frozen[1], self._frozen[2], self._frozen[3]
+            key = (x.dtype,) + tuple((_derived.stamp(c.weight), c.acr_math) for c in convs)
+            hit = _derived.entries(self).get("frozen")
+            if hit is not None and hit[0] == key:
+                return hit[1:]
         if torch.cuda.is_current_stream_capturing():
             # a miss of the frozen cache inside a hipGraph capture: the standardisation / image launches upload descriptor
             # tables from temporary pinned memory, which a replay would read again after it was recycled (ADVICE r5)
@@ -245,7 +245,7 @@ class ResNetV2(nn.Module):
         for idx in self._wstd_groups(convs):
             self._standardise_group(convs, idx, w_hats, wts, imgs)
         if frozen:
-            self._frozen = (key, w_hats, wts, imgs)
+            _derived.entries(self, create=True)["frozen"] = (key, w_hats, wts, imgs)
             self.frozen_generation += 1
         return w_hats, wts, imgs
 
@@ -479,14 +479,9 @@ class PrefixGraph:
     ~700 small launches per pass that the host cannot issue as fast as the GPU retires them at batch 2.  The graph owns
     its input, its MeanStack (the head-mean maps of blocks < k land in it on every replay) and the tokens it returns;
     the attention state the blocks expose (``get_attn`` / ``last_pm``) is re-pointed to this graph's buffers on replay.
-    What the captured launches READ is fixed at capture: parameter storages, the frozen standardised conv weights (a cached
-    copy, ResNetV2._standardised) and -- under split products -- the cached weight IMAGES of the prefix Linears
-    (ops.weight_image: the warm-up passes fill that cache, the capture hits it).  The graph keeps references to those images
-    (they cannot return to the allocator under it) and ``valid`` compares parameter addresses, every parameter's autograd
-    VERSION (an in-place update -- load_state_dict into the same storages, an optimizer step in eval mode -- makes the graph
-    stale: exact fp32 would have seen it through the storages, the images would not) and the stem cache's generation.
-    Writes through ``.data`` are invisible to all of these: ``ACR.invalidate_caches()`` / ``train.refresh_weight_transposes``
-    after such a write."""
+    What the captured launches READ is fixed at capture: parameter storages, the frozen standardised conv weights and -- under
+    split products -- the weight IMAGES of the prefix Linears (the warm-up passes store them, the capture hits them; the graph
+    holds them).  When the graph is stale, and what to do after a write through ``.data``: _derived.py (``weights_moved``)."""
 
     def __init__(self, vit, x, k):
         self.k = k
@@ -495,7 +490,6 @@ class PrefixGraph:
         T = (h // vit.patch_size[1]) * (w // vit.patch_size[0]) + vit.num_tokens
         self.stack = ops.MeanStack(b, vit.depth, T, x.device)
         self.taps = {}
-        stem = vit.patch_embed.backbone if isinstance(vit.patch_embed, HybridEmbed) else None
         side = torch.cuda.Stream(device=x.device)          # warm-up off the caller's stream, as torch.cuda.graph asks
         side.wait_stream(torch.cuda.current_stream(x.device))
         with torch.cuda.stream(side), torch.no_grad():
@@ -509,32 +503,12 @@ class PrefixGraph:
             self.out = vit.run_blocks(t, self.stack, self.taps, 0, k)
         self._blocks = list(vit.blocks[:k])
         self.state = [(blk.attn._saved, blk.attn.last_pm) for blk in self._blocks]
-        self.stem_generation = stem.frozen_generation if stem is not None else 0
-        self.addresses = self._addresses(vit)
-        self.versions = self._versions(vit)
-        # the weight images the captured products read (cache entries of the prefix Linears as the capture found them)
-        self._images = [m.__dict__[key][2] for blk in self._blocks for m in blk.modules() if isinstance(m, nn.Linear)
-                        for key in ("_acr_x3_w_img", "_acr_x3_wt_img") if key in m.__dict__]
-
-    @staticmethod
-    def _addresses(vit):
-        return tuple(p.data_ptr() for p in vit.parameters())
-
-    @staticmethod
-    def _versions(vit):
-        return tuple(p._version for p in vit.parameters())
+        self.stem = getattr(vit.patch_embed, "backbone", None)
+        self.stamped = _derived.weights_stamp(vit, self.stem)
+        self._images = _derived.held(m for blk in self._blocks for m in blk.modules())      # what the captured products read
 
     def valid(self, vit):
-        stem = vit.patch_embed.backbone if isinstance(vit.patch_embed, HybridEmbed) else None
-        if self.addresses != self._addresses(vit) or self.versions != self._versions(vit):
-            return False
-        if stem is not None:
-            # rebuilds the cache when a conv weight changed in place; then the generation moves and the graph is stale
-            convs = [m for m in stem.modules() if isinstance(m, StdConv2dSame)]
-            if all(c.weight.dtype == self.x.dtype for c in convs):
-                stem._standardised(convs, self.x)
-            return stem.frozen_generation == self.stem_generation
-        return True
+        return not _derived.weights_moved(self.stamped, vit, self.stem, self.x.dtype)
 
     def replay(self, x, taps):
         self.x.copy_(x)
@@ -561,15 +535,14 @@ class PassGraph:
     13 % of the span; now it is 1 + kmax replays per geometry.  The autograd graph of the captured forward (its saved
     activations live in the pool) is kept alive by ``cls_pred``; the class graph was captured against exactly those buffers.
     Same kernels in the same order as eager launches: results are bit-identical
-    (tests/test_model_gpu.py::test_infer_pass_graph_equals_eager_launches).  Validity is PrefixGraph's: parameter addresses
-    and versions, the stem cache's generation; the cached weight images the captured products read are held here."""
+    (tests/test_model_gpu.py::test_infer_pass_graph_equals_eager_launches).  Validity is PrefixGraph's, over the whole model's
+    parameters; the weight images the captured products read are held here."""
 
     def __init__(self, model, inp, start_layer, func):
         vit = model.pretrained.model
         dev = inp.device
         self.inp = inp.detach().clone(memory_format=torch.preserve_format)
         self.mask = torch.zeros((inp.shape[0], model.num_class), dtype=torch.float32, device=dev)
-        stem = vit.patch_embed.backbone if isinstance(vit.patch_embed, HybridEmbed) else None
 
         def forward():
             with torch.enable_grad():
@@ -599,24 +572,12 @@ class PassGraph:
         self._blocks = list(vit.blocks)
         self.state = [(blk.attn._saved, blk.attn.last_pm, blk.attn._saved_do) for blk in self._blocks]
         self.taps = dict(model.pretrained.activations)
-        self.stem_generation = stem.frozen_generation if stem is not None else 0
-        self.addresses = tuple(p.data_ptr() for p in model.parameters())
-        self.versions = tuple(p._version for p in model.parameters())
-        self._images = [m.__dict__[key][2] for m in model.modules() if isinstance(m, nn.Linear)
-                        for key in ("_acr_x3_w_img", "_acr_x3_wt_img") if key in m.__dict__]
+        self.stem = getattr(vit.patch_embed, "backbone", None)
+        self.stamped = _derived.weights_stamp(model, self.stem)
+        self._images = _derived.held(model.modules())
 
     def valid(self, model):
-        vit = model.pretrained.model
-        stem = vit.patch_embed.backbone if isinstance(vit.patch_embed, HybridEmbed) else None
-        if (self.addresses != tuple(p.data_ptr() for p in model.parameters())
-                or self.versions != tuple(p._version for p in model.parameters())):
-            return False
-        if stem is not None:
-            convs = [m for m in stem.modules() if isinstance(m, StdConv2dSame)]
-            if all(c.weight.dtype == self.inp.dtype for c in convs):
-                stem._standardised(convs, self.inp)
-            return stem.frozen_generation == self.stem_generation
-        return True
+        return not _derived.weights_moved(self.stamped, model, self.stem, self.inp.dtype)
 
     def run(self, model, inp, masks):
         """Replay the pass on ``inp`` and the class graph once per mask.  Returns (patch CAMs, head-mean stack, [rows per mask]):
@@ -648,46 +609,21 @@ def pass_graph(model, inp, start_layer, func):
         return None
     key = (tuple(inp.shape), inp.dtype, inp.device, inp.is_contiguous(memory_format=torch.channels_last), start_layer, func, model.training,
            vit.acr_math, vit.blocks[0].attn.acr_math, model.num_class)
-    cache = vit.__dict__.setdefault("_pass_graphs", OrderedDict())
-    g = cache.get(key)
-    if g is not None and g is not False and not g.valid(model):
-        del cache[key]
-        g = None
-    if g is None and not _sighted(vit, key):
-        return None                            # first pass of this geometry: eager launches (see VisionTransformer.graph_sightings)
-    if g is None:
-        keep = vit.graph_prefix
-        vit.graph_prefix = False               # the pass is captured whole: no nested replay of a prefix graph
+
+    def build():
+        keep, vit.graph_prefix = vit.graph_prefix, False      # the pass is captured whole: no nested replay of a prefix graph
         try:
-            g = PassGraph(model, inp, start_layer, func)
-        except RuntimeError as e:              # an op that cannot be captured on this build: stay on eager launches
-            import traceback
-            import warnings
-            where = [l.strip() for l in traceback.format_exc().splitlines() if l.strip().startswith("File")][-3:]
-            warnings.warn("hipGraph capture of the GETAM pass failed (%s; %s); running it eagerly" % (str(e).splitlines()[0], " <- ".join(reversed(where))))
-            torch.cuda.synchronize()
-            g = False
+            return PassGraph(model, inp, start_layer, func)
         finally:
             vit.graph_prefix = keep
-        cache[key] = g
-        while len(cache) > vit.max_pass_graphs:
-            cache.popitem(last=False)
-    cache.move_to_end(key)
-    return g or None
 
+    def failed(e):
+        import traceback
+        where = [l.strip() for l in traceback.format_exc().splitlines() if l.strip().startswith("File")][-3:]
+        return "hipGraph capture of the GETAM pass failed (%s; %s); running it eagerly" % (str(e).splitlines()[0], " <- ".join(reversed(where)))
 
-def _sighted(vit, key):
-    """True once ``key`` (an input geometry) has been asked for ``vit.graph_sightings`` times: a capture costs two warm-up passes,
-    the capture itself and a private pool holding the pass's activations -- about four passes of work -- so a geometry seen ONCE
-    (natural-size images, the last short batch of a list) runs eagerly and only a recurring one is captured.  The
-    record survives a graph's invalidation (a weight update re-captures at once) and is bounded."""
-    seen = vit.__dict__.setdefault("_graph_sightings", OrderedDict())
-    n = seen.get(key, 0) + 1
-    seen[key] = n
-    seen.move_to_end(key)
-    while len(seen) > 64:
-        seen.popitem(last=False)
-    return n >= vit.graph_sightings
+    return _derived.graph_lookup(vit, "_pass_graphs", key, vit.graph_sightings, vit.max_pass_graphs,
+                                 lambda g: g.valid(model), build, failed)
 
 
 class _PosEmbedResizeFn(torch.autograd.Function):
@@ -858,9 +794,7 @@ class VisionTransformer(nn.Module):
 
     def train(self, mode=True):
         if mode:                               # back to training: the captured prefixes' private pools (activations of every
-            self.__dict__.pop("_prefix_graphs", None)      # geometry seen) go back to the allocator
-            self.__dict__.pop("_pass_graphs", None)
-            self.__dict__.pop("_graph_sightings", None)
+            _derived.drop_graphs([self], sightings=True)   # geometry seen) go back to the allocator
         return super().train(mode)
 
     def prefix_graph(self, x, k):
@@ -873,26 +807,10 @@ class VisionTransformer(nn.Module):
             return None
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last), k, self.training,
                self.blocks[0].attn.keep_state_in_training, self.acr_math, self.blocks[0].attn.acr_math)
-        cache = self.__dict__.setdefault("_prefix_graphs", OrderedDict())
-        g = cache.get(key)
-        if g is not None and g is not False and not g.valid(self):
-            del cache[key]                     # the parameters moved (.to / .float / load into new storage): capture again
-            g = None
-        if g is None and not _sighted(self, ("prefix",) + key):
-            return None
-        if g is None:
-            try:
-                g = PrefixGraph(self, x, k)
-            except RuntimeError as e:          # an op that cannot be captured on this build: stay on eager launches
-                import warnings
-                warnings.warn("hipGraph capture of the inference prefix failed (%s); running it eagerly" % str(e).splitlines()[0])
-                torch.cuda.synchronize()
-                g = False
-            cache[key] = g
-            while len(cache) > self.max_prefix_graphs:
-                cache.popitem(last=False)
-        cache.move_to_end(key)
-        return g or None
+        return _derived.graph_lookup(
+            self, "_prefix_graphs", key, self.graph_sightings, self.max_prefix_graphs,
+            lambda g: g.valid(self), lambda: PrefixGraph(self, x, k),
+            lambda e: "hipGraph capture of the inference prefix failed (%s); running it eagerly" % str(e).splitlines()[0])
 
     tap1, tap2 = None, None
     tap3, tap4 = 8, 11

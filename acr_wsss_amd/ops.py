@@ -9,6 +9,7 @@ import torch
 from torch.autograd import Function
 
 from . import _abi
+from . import _derived
 from . import _lib as L
 
 HEAD_DIM = 64
@@ -367,12 +368,9 @@ class WeightTransposes:
     """(in, out) copies of Linear weights for the input-gradient GEMMs, refreshed in ONE launch (acr_transpose_many_bf16 /
     _f32; in fp32 the GEMM on the transposed copy is 12-17 % faster than on W as stored, scripts/lab/gemm_nn_vs_nt.py).
 
-    ``refresh()`` is called by the training step's owner right after the optimizer step; a copy is used only while the
-    weight's autograd version, storage address and device equal those recorded at refresh (an in-place update through the
-    parameter, a re-allocated storage or ``module.to(other_gpu)`` make the consumer fall back to W as stored / a transpose
-    on the fly).  What this CANNOT see: writes through ``.data`` (``p.data.mul_()``, ``p.data.copy_()``, an EMA swap) --
-    they do not move the parameter's version counter -- so code that updates weights that way must call ``refresh()``
-    itself (train.refresh_weight_transposes(model)); INTEGRATION.md says so."""
+    ``refresh()`` is called by the training step's owner right after the optimizer step and stores each copy as form "t" of
+    its Linear; a copy that is not current (_derived.py: the rule, and its blind spot for writes through ``.data``, after
+    which the writer calls ``refresh()`` itself) makes the consumer fall back to W as stored / a transpose on the fly."""
 
     def __init__(self, modules, dtype=torch.bfloat16):
         mult = 8 if dtype == torch.bfloat16 else 4
@@ -397,23 +395,19 @@ class WeightTransposes:
         if any(m.weight.data_ptr() != p for m, p in zip(self.lins, self._ptrs)):
             self.ok = False                                   # storages were re-allocated: stop serving copies
             for m in self.lins:
-                m._acr_wt = None
+                _derived.entries(m).pop("t", None)
             return
         fn = L.load().acr_transpose_many_bf16 if self.dtype == torch.bfloat16 else L.load().acr_transpose_many_f32
         L.check(fn(L.ptr(self.table), L.ptr(self.blk), self.nblocks, L.stream_ptr()), "acr_transpose_many")
         for m, wt in zip(self.lins, self.bufs):
-            m._acr_wt, m._acr_wt_ver, m._acr_wt_ptr = wt, m.weight._version, m.weight.data_ptr()
+            _derived.put(m, "t", m.weight, wt)             # same-stream contract: no event
 
 
 def weight_t(weight, owner=None, make=True):
     """weight^T contiguous: the cached copy of ``owner`` (an nn.Linear) when it is current, else a fresh transpose
     (``make`` = False: None instead, for callers that can work on W as stored)."""
-    wt = getattr(owner, "_acr_wt", None) if owner is not None else None
-    if (wt is not None and owner._acr_wt_ver == weight._version and wt.shape[0] == weight.shape[1] and wt.dtype == weight.dtype
-            and wt.device == weight.device and owner.weight.data_ptr() == weight.data_ptr()
-            and getattr(owner, "_acr_wt_ptr", None) == weight.data_ptr()):
-        return wt
-    return weight.t().contiguous() if make else None
+    wt = _derived.get(owner, "t", weight)
+    return weight.t().contiguous() if wt is None and make else wt
 
 
 F32_WT = True      # A/B switch: fp32 input gradients on the cached W^T (NT) vs W as stored (NN)
@@ -633,32 +627,21 @@ def x3_image_many(specs, device):
 
 
 def weight_image(weight, owner=None, transposed=False):
-    """Image of a Linear's weight (``transposed``: of W^T, what the input gradient multiplies by), cached on ``owner`` (the
-    nn.Linear) per weight version: inference makes each image once, a training step once per forward resp. backward (the
-    optimizers move the version counters on, train.py).  The cache entry remembers the stream that built the image and an
-    event behind the build: a consumer on ANOTHER stream (CAM generation runs each scale on a stream of its own) waits for
-    that event first -- a cache hit must not read an image whose split pass is still queued elsewhere.  What the key cannot see
-    -- as with WeightTransposes -- are writes through ``.data``: ``invalidate_weight_images(model)`` /
-    ``train.refresh_weight_transposes(model)`` drop the cached images."""
-    key = "_acr_x3_wt_img" if transposed else "_acr_x3_w_img"
-    c = getattr(owner, key, None) if owner is not None else None
-    if c is not None and c[0] == weight._version and c[1] == weight.data_ptr() and c[2].device == weight.device:
-        cur = torch.cuda.current_stream(weight.device)
-        if c[3] != cur and not torch.cuda.is_current_stream_capturing():
-            cur.wait_event(c[4])
-        return c[2]
-    w2 = weight.detach()
-    img = x3_image_t(w2) if transposed else x3_image(w2)
-    if owner is not None and not torch.cuda.is_current_stream_capturing():      # a captured pass would only be run at replay
-        cur = torch.cuda.current_stream(weight.device)
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        setattr(owner, key, (weight._version, weight.data_ptr(), img, cur, ev))
+    """Image of a Linear's weight (``transposed``: of W^T, what the input gradient multiplies by), kept on ``owner`` (the
+    nn.Linear) as form "img" / "img_t" while it is current (_derived.py; a hit on another stream waits for the build): inference
+    makes each image once, a training step once per forward resp. backward (the optimizers move the version counters on)."""
+    form = "img_t" if transposed else "img"
+    img = _derived.get(owner, form, weight)
+    if img is None:
+        w2 = weight.detach()
+        img = x3_image_t(w2) if transposed else x3_image(w2)
+        if owner is not None and not torch.cuda.is_current_stream_capturing():      # a captured pass would only be run at replay
+            _derived.put(owner, form, weight, img, _derived.built_here(weight.device))
     return img
 
 
 def prebuild_weight_images(linears):
-    """The images of W and of W^T of every given nn.Linear in ONE launch (ops.x3_image_many), stored in the per-owner caches
+    """The images of W and of W^T of every given nn.Linear in ONE launch (ops.x3_image_many), stored as the entries
     weight_image() reads -- a training step calls this once after the optimizer step instead of paying 8 small image launches per
     block when the forward / backward first ask for them (train.refresh_weight_transposes)."""
     lins = [m for m in linears if m.weight.is_cuda and m.weight.dtype == torch.float32 and m.weight.is_contiguous()
@@ -673,22 +656,16 @@ def prebuild_weight_images(linears):
         specs.append((w, 0, k, n, 1, n, 0, k))              # W^T (in x out): the input gradient's
     dev = lins[0].weight.device
     imgs = x3_image_many(specs, dev)
-    cur = torch.cuda.current_stream(dev)
-    ev = torch.cuda.Event()
-    ev.record(cur)
+    built = _derived.built_here(dev)                        # one event per build call
     for i, m in enumerate(lins):
-        m._acr_x3_w_img = (m.weight._version, m.weight.data_ptr(), imgs[2 * i], cur, ev)
-        m._acr_x3_wt_img = (m.weight._version, m.weight.data_ptr(), imgs[2 * i + 1], cur, ev)
+        _derived.put(m, "img", m.weight, imgs[2 * i], built)
+        _derived.put(m, "img_t", m.weight, imgs[2 * i + 1], built)
     return len(lins)
 
 
 def invalidate_weight_images(model):
-    """Drop every cached split-product weight image under ``model`` (after a weight was written through ``.data``, which moves
-    neither the version counter nor the address the cache is keyed on)."""
-    for m in model.modules():
-        for key in ("_acr_x3_w_img", "_acr_x3_wt_img"):
-            if key in m.__dict__:
-                delattr(m, key)
+    """Drop every cached split-product weight image under ``model``."""
+    _derived.invalidate(model, _derived.IMAGES)
 
 
 def gemm_x3(mode, a_img, b_img, c, K, bias=None, aux=None, act=0, c2=None, colsum=None, shape=None):

@@ -50,8 +50,7 @@ def seg_train_step(model, head, optimizer, images, ori_images, croppings, seg_la
     if grad_sync is not None:
         grad_sync.finish()
     optimizer.step()
-    refresh_weight_transposes(model)
-    ops.invalidate_weight_images(head)
+    refresh_weight_transposes(model, head)
     return loss, dict(terms, loss=loss)
 
 
@@ -86,7 +85,7 @@ def joint_train_step(model, head, optimizer, images, ori_images, croppings, labe
       ``traincam.training_cams`` -> ``saliency_labels``) -> ``head(decoder.decode_taps(first B rows))`` -> ``segloss.joint_loss``
       (``split_cross_entropy`` alone when ``dense_energy_layer`` is None) -> ``loss = acr + seg_weight * (celoss + dloss)`` ->
       one backward (``grad_sync.prepare`` / ``finish`` around it as in the other steps) -> ``optimizer.step`` ->
-      ``refresh_weight_transposes(model)``, ``ops.invalidate_weight_images(head)``.
+      ``refresh_weight_transposes(model, head)``.
     images (B,3,S,S) float32 on the GPU (S a multiple of 32), ori_images, croppings as in ``seg_train_step``; labels (B,C) the
     image-level labels; saliency (B,S,S) uint8.  ``cam_kw`` goes to ``training_cams`` (eps), ``label_kw`` to ``saliency_labels``
     (bg_alpha, cut, open_size).  bf16 images with a bf16 model and head (vitb_hybrid; ``train.MasterWeights`` over
@@ -127,8 +126,7 @@ def joint_train_step(model, head, optimizer, images, ori_images, croppings, labe
     if grad_sync is not None:
         grad_sync.finish()
     optimizer.step()
-    refresh_weight_transposes(model)
-    ops.invalidate_weight_images(head)
+    refresh_weight_transposes(model, head)
     terms = dict(terms, acr_loss=acr, celoss=celoss, dloss=dloss, loss=loss, seg_label=seg_label, saliency_out=saliency_out)
     return loss, terms
 

@@ -300,34 +300,33 @@ def train_step(model, optimizer, img, label, alpha, grad_sync=None, amp_dtype=No
     return loss, terms
 
 
-def refresh_weight_transposes(model):
-    """fp32 mode: the (in, out) copies of the block Linears' weights that the input-gradient GEMMs read (one launch; created on
-    first use).  Optional -- a loop that does not call this (the reference's own, train_acr.py:135-174) simply runs those GEMMs
-    on W as stored, since a copy is only ever used while its weight's version matches.  The bf16 mode's MasterWeights keeps its
-    own set."""
-    from . import ops as _ops
-    _ops.invalidate_weight_images(model)                  # split-product images are keyed like the transposes: same blind spot for .data writes
+def refresh_weight_transposes(model, *others):
+    """After the optimizer step, fp32 modes: drop the weight images of ``model`` and ``others`` (heads the step also updated), then
+    prebuild the block Linears' images (split products) or refresh their (in, out) copies for the input-gradient GEMMs (one
+    launch each; created on first use).  Optional -- a loop that does not call this (the reference's own, train_acr.py:135-174)
+    builds images on demand resp. runs on W as stored (_derived.py).  The bf16 mode's MasterWeights keeps its own copies."""
+    from . import _derived, ops as _ops
+    for m in (model,) + others:
+        _ops.invalidate_weight_images(m)                  # also what a write through .data needs: the blind spot of the stamps
+    kept = _derived.entries(model, create=True)
     if getattr(model, "math", "f32") == "f32_split" and _ops.X3_IMAGES:
-        # split products multiply by the IMAGES of W and W^T (ops.weight_image): no fp32 copies to keep; the images of every block
-        # Linear for the coming step are made here in one launch (96 image launches of a few microseconds per step otherwise)
-        lins = getattr(model, "_acr_x3_linears", None)
+        # no fp32 copies to keep; one launch here instead of 96 image launches of a few microseconds per step
+        lins = kept.get("linears")
         if lins is None:
             from .backbone import Attention, Mlp
-            lins = []
+            lins = kept["linears"] = []
             for m in model.modules():
                 if isinstance(m, Attention):
                     lins += [m.qkv, m.proj]
                 elif isinstance(m, Mlp):
                     lins += [m.fc1, m.fc2]
-            object.__setattr__(model, "_acr_x3_linears", lins)
         if lins and lins[0].weight.is_cuda and lins[0].weight.dtype == torch.float32:
             _ops.prebuild_weight_images(lins)
         return
-    wt = getattr(model, "_acr_wt_f32", None)
+    wt = kept.get("wt_f32")
     if wt is None:
         p0 = next(model.parameters(), None)
         if p0 is None or not p0.is_cuda or p0.dtype != torch.float32 or not _ops.F32_WT:
             return
-        wt = _ops.WeightTransposes(model.modules(), dtype=torch.float32)
-        object.__setattr__(model, "_acr_wt_f32", wt)       # not a submodule / parameter: plain attribute
+        wt = kept["wt_f32"] = _ops.WeightTransposes(model.modules(), dtype=torch.float32)
     wt.refresh()

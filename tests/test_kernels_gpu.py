@@ -491,28 +491,29 @@ def test_weight_transposes_cache():
     torch.manual_seed(3)
     lins = [torch.nn.Linear(i, o).to(dev).bfloat16() for i, o in ((768, 2304), (3072, 768), (72, 200), (64, 64))]
     cache = ops.WeightTransposes(lins)
+    assert cache.lins == lins
     cache.refresh()
-    for m in lins:
+    for m, buf in zip(lins, cache.bufs):                      # the buffer the cache owns for that Linear is what is served
         wt = ops.weight_t(m.weight, m)
-        assert wt is m._acr_wt and torch.equal(wt, m.weight.t().contiguous())
+        assert wt is buf and torch.equal(wt, m.weight.t().contiguous())
     with torch.no_grad():
         lins[0].weight.mul_(2.0)                              # in-place update bumps the version: the copy is stale
     wt0 = ops.weight_t(lins[0].weight, lins[0])
-    assert wt0 is not lins[0]._acr_wt and torch.equal(wt0, lins[0].weight.t().contiguous())
+    assert wt0 is not cache.bufs[0] and torch.equal(wt0, lins[0].weight.t().contiguous())
     cache.refresh()
-    assert ops.weight_t(lins[0].weight, lins[0]) is lins[0]._acr_wt
-    assert torch.equal(lins[0]._acr_wt, lins[0].weight.t().contiguous())
+    assert ops.weight_t(lins[0].weight, lins[0]) is cache.bufs[0]
+    assert torch.equal(cache.bufs[0], lins[0].weight.t().contiguous())
     # a re-allocated storage (`p.data = ...`, module.to(other device)) is seen through the recorded address ...
     lins[1].weight.data = lins[1].weight.data.clone() * 3.0
     wt1 = ops.weight_t(lins[1].weight, lins[1])
-    assert wt1 is not lins[1]._acr_wt and torch.equal(wt1, lins[1].weight.t().contiguous())
+    assert wt1 is not cache.bufs[1] and torch.equal(wt1, lins[1].weight.t().contiguous())
     # ... a write THROUGH .data is not (no version bump, same storage): the documented contract is an explicit refresh
     lins[2].weight.data.mul_(2.0)
-    assert ops.weight_t(lins[2].weight, lins[2]) is lins[2]._acr_wt and not torch.equal(lins[2]._acr_wt, lins[2].weight.t())
+    assert ops.weight_t(lins[2].weight, lins[2]) is cache.bufs[2] and not torch.equal(cache.bufs[2], lins[2].weight.t())
     cache2 = ops.WeightTransposes(lins)
     cache2.refresh()
-    for m in lins:
-        assert ops.weight_t(m.weight, m) is m._acr_wt and torch.equal(m._acr_wt, m.weight.t().contiguous())
+    for m, buf in zip(lins, cache2.bufs):
+        assert ops.weight_t(m.weight, m) is buf and torch.equal(buf, m.weight.t().contiguous())
 
 
 @pytest.mark.parametrize("M,N,K", [(1, 32, 32), (130, 200, 72), (785, 2304, 768), (2 * 785 + 3, 768, 3072), (333, 576, 192),
@@ -1428,10 +1429,10 @@ def test_f32_input_gradients_on_cached_transposes_are_bit_identical():
 
     base = grads()                                                           # no copies yet: NN on W as stored
     wt = ops.WeightTransposes([fc1, fc2, qkv, head], dtype=torch.float32)
-    assert len(wt.lins) == 3
+    assert wt.lins == [fc1, fc2, qkv]
     wt.refresh()
-    assert torch.equal(fc1._acr_wt, fc1.weight.t()) and torch.equal(qkv._acr_wt, qkv.weight.t())
-    assert ops.weight_t(fc2.weight, fc2, make=False) is fc2._acr_wt
+    assert torch.equal(wt.bufs[0], fc1.weight.t()) and torch.equal(wt.bufs[2], qkv.weight.t())
+    assert ops.weight_t(fc2.weight, fc2, make=False) is wt.bufs[1]
     cached = grads()
     for a, b in zip(base, cached):
         assert torch.equal(a, b)
@@ -1448,7 +1449,7 @@ def test_f32_input_gradients_on_cached_transposes_are_bit_identical():
         ops.F32_WT = True
     assert torch.equal(xa.grad, xr.grad) and not torch.equal(xa.grad, base[0])
     wt.refresh()
-    assert ops.weight_t(fc1.weight, fc1, make=False) is fc1._acr_wt and torch.equal(fc1._acr_wt, fc1.weight.t())
+    assert ops.weight_t(fc1.weight, fc1, make=False) is wt.bufs[0] and torch.equal(wt.bufs[0], fc1.weight.t())
 
 
 def test_kernel_timer_brackets_first_launch_per_step():
